@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- photons/s of the I3RC photon-tracing hot path on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--scaling weak|strong]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--scaling weak|strong] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints its line.  `--full` adds what the headline figure does not need:
+the CPU baseline (tools/cpu_baseline.py, run before any rank touches the GPU) and, for N > 1 without --scaling, the weak
+figure measured after the strong headline.  `--dump-outputs DIR` writes what the last timed step computed -- the arrays
+Integrator.finish hands a caller (fluxes, absorption, radiances; the work counters in binding.COUNTER_NAMES order) -- as
+DIR/<name>.npy: same arguments, same inputs (Philox key (10, batch)), so two builds can be compared output for output.
 
 `--gpus N` measures N GPUs BY ITSELF: called without a launcher (RANK unset) this process never touches the GPU; it
 starts N fresh rank processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, one per
@@ -51,10 +57,14 @@ def parse_args():
     ap.add_argument("--nlayers", type=int, default=16, help="step cloud: 16 = BASELINE.json label, 32 = reference generator (= --config step32)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default=None,
                     help="default: N = 1 -> the same thing; N > 1 -> strong (ONE batch of --photons photons per step sharded over the GPUs: the "
-                         "metric's case) as the headline, the weak figure measured after it and reported beside it")
+                         "metric's case) as the headline; with --full the weak figure is measured after it and reported beside it")
     ap.add_argument("--overlap", choices=("auto", "0", "1", "2", "3", "4"), default="auto",
                     help="k: k + 1 steps in flight (as many handles / streams / tally buffers); auto = three steps in flight for N > 1, else one")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline and (N > 1, no --scaling) the weak figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float32 / float64, 64 MB at most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--contact-timeout", type=float, default=float(os.environ.get("I3RC_BENCH_CONTACT_TIMEOUT", "300")),
                     help="N > 1: seconds every rank has for init_process_group and a first all-reduce before the run is called off (naming the rank)")
     ap.add_argument("--collective-timeout", type=float, default=float(os.environ.get("I3RC_BENCH_COLLECTIVE_TIMEOUT", "600")),
@@ -68,6 +78,10 @@ def parse_args():
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)
     if a.config == "step16" and a.nlayers == 32:
         a.config = "step32"
     return a
@@ -139,7 +153,7 @@ def wait_for_ranks(procs, poll_s=0.2, grace_s=10.0, contact=None):
 # ------------------------------------------------------------------------------------------------------------------
 def launcher(a):
     cpu_baseline = None
-    if a.gpus == 1 and not a.no_cpu_baseline:
+    if a.gpus == 1 and a.full and not a.no_cpu_baseline:
         cpu_baseline = run_cpu_baseline(a)   # before any rank exists: the host cores are free
     # Ranks rendezvous on a port found by bind-and-close: somebody else may take it before rank 0 binds it (EADDRINUSE in
     # its stderr) -- then the whole set is started again on a fresh port.  All children are polled: the first one that
@@ -200,6 +214,30 @@ def algorithmic_bytes_per_photon(c, n_dir=0, absorbing=False):
     K = c["scatterings"] / n
     E = (c["exitsTop"] + c["surfaceHits"]) / n
     return 16 * S + 20 * K + (16 * K if absorbing else 0) + 8 * E + 24 * K * n_dir, dict(S=S, K=K, E=E, D=n_dir)
+
+
+DUMP_LIMIT_BYTES = 63 << 20   # (64 MB in all with the .npy headers)
+
+
+def dump_outputs(directory, res):
+    """--dump-outputs: the arrays Integrator.finish gives a caller for the last timed step, as directory/<name>.npy -- float32 as
+    computed, the work counters as float64 in binding.COUNTER_NAMES order.  The packed raw tally buffer they are normalised from
+    is left out.  Should the whole exceed 64 MB, every array is cut to the same fraction by a fixed, seeded sample of its
+    flattened elements (indices in increasing order)."""
+    import numpy as np
+
+    from i3rc_monte_carlo_model_amd import binding as B
+
+    arrays = {k: v for k, v in res.items() if isinstance(v, np.ndarray) and k != "raw"}
+    arrays["counters"] = np.array([res["counters"][k] for k in B.COUNTER_NAMES], np.float64)
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        v = np.ascontiguousarray(v, np.float64 if v.dtype == np.float64 else np.float32)
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(v.size * DUMP_LIMIT_BYTES // total))
+            v = v.ravel()[np.sort(np.random.default_rng(12345).choice(v.size, keep, replace=False))]
+        np.save(os.path.join(directory, k + ".npy"), v)
 
 
 def load_pmc(config):
@@ -285,7 +323,7 @@ def worker(a):
     cpu_baseline = None
     if os.environ.get("I3RC_BENCH_CPU_BASELINE"):
         cpu_baseline = json.loads(os.environ["I3RC_BENCH_CPU_BASELINE"])   # measured by the launcher before any rank existed
-    elif n_gpus == 1 and not a.no_cpu_baseline and not os.environ.get("I3RC_BENCH_SPAWNED"):
+    elif n_gpus == 1 and a.full and not a.no_cpu_baseline and not os.environ.get("I3RC_BENCH_SPAWNED"):
         cpu_baseline = run_cpu_baseline(a)
 
     import numpy as np
@@ -443,31 +481,37 @@ def worker(a):
                     kernel_ms=kernel_ms, launches_per_step=n_launches / steps, last=last, ranks=ranks)
 
     # N = 1: weak and strong are the same run.  N > 1 without --scaling: the metric's case -- ONE batch of the workload's
-    # photons per step, sharded over the GPUs (strong) -- is the headline; the weak figure (every GPU the whole batch) is
-    # measured after it and reported beside it.
+    # photons per step, sharded over the GPUs (strong) -- is the headline; with --full the weak figure (every GPU the whole
+    # batch) is measured after it and reported beside it.
     headline = a.scaling or ("strong" if n_gpus > 1 else "weak")
     m = measure(headline, a.steps, a.warmup)
+    elapsed, mine, per_step, total_per_step = m["elapsed"], m["mine"], m["per_step"], m["total_per_step"]
+    kernel_ms, launches_per_step = m["kernel_ms"], m["launches_per_step"]
+
+    def last_results(run):
+        """The results of a run's last step (already all-reduced across ranks), or None where its tallies are not those of exactly
+        one step: every photon leaves through the top, ends at the surface / by roulette or is dropped by the tracer -- a wrong
+        count or a lost / doubled tally shows here."""
+        r = integ.finish(run["last"]["tally"].cpu().numpy())
+        if r["counters"]["photons"] != float(run["total_per_step"]):
+            sys.stderr.write(f"bench: inconsistent results (photons {r['counters']['photons']:.0f}, expected {run['total_per_step']})\n")
+            return None
+        return r
+
+    res = last_results(m)
+    if res is None:
+        return 4
+    counters = res["counters"]
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, res)
     weak = None
-    if a.scaling is None and n_gpus > 1:
+    if a.full and a.scaling is None and n_gpus > 1:
         mw = measure("weak", a.steps, 1)
         weak = {"value": float(mw["total_per_step"]) * mw["steps"] / mw["elapsed"], "unit": "photons/s", "ms_per_step": mw["elapsed"] / mw["steps"] * 1e3,
                 "photons_per_step": mw["total_per_step"], "photons_per_gpu_per_step": mw["mine"], "steps": mw["steps"],
                 "note": "weak scaling measured after the headline run: every GPU traces the workload's whole batch per step"}
-        m["last"] = None   # (the lanes now hold the weak run's tallies: the result check below uses what it left)
-        check = mw
-    else:
-        check = m
-    elapsed, mine, per_step, total_per_step = m["elapsed"], m["mine"], m["per_step"], m["total_per_step"]
-    kernel_ms, launches_per_step = m["kernel_ms"], m["launches_per_step"]
-    # ---- results of the last step (already all-reduced across ranks) ------------------------------------
-    raw = check["last"]["tally"].cpu().numpy()
-    res = integ.finish(raw)
-    counters = res["counters"]
-    # the last step's tallies must be those of exactly one step: every photon leaves through the top, ends at the
-    # surface / by roulette or is dropped by the tracer -- a wrong count or a lost / doubled tally shows here
-    if counters["photons"] != float(check["total_per_step"]):
-        sys.stderr.write(f"bench: inconsistent results (photons {counters['photons']:.0f}, expected {check['total_per_step']})\n")
-        return 4
+        if last_results(mw) is None:
+            return 4
     albedo = w.get("surface", w.get("albedo", 0.0))
     if albedo == 0.0 and "surface_grid" not in w and not absorbing:
         closure = float(res["fluxUp"].mean() + res["fluxDown"].mean()) + counters["dropped"] / counters["photons"]
@@ -481,8 +525,7 @@ def worker(a):
         devices = gathered
 
     if rank == 0:
-        share = check["mine"] / float(check["total_per_step"])   # this rank's share of the (all-reduced) work counters
-        local = {k: v * share / check["mine"] * mine for k, v in counters.items()}   # ... scaled to a headline step's photons
+        local = {k: v * mine / float(total_per_step) for k, v in counters.items()}   # this rank's share of the (all-reduced) work counters
         avg_ms = float(np.mean(kernel_ms)) * launches_per_step     # kernel time per step on this rank
         kbpp, kskd = algorithmic_bytes_per_photon(local, nd, absorbing)        # what this kernel actually did
         # roofline.achieved: SURVEY.md 8(d)'s byte formula evaluated with THE KERNEL'S OWN work counters.  With the local

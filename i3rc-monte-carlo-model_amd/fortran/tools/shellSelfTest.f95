@@ -1,5 +1,5 @@
 ! Self test of the Fortran shell.  "cpu": everything that needs no GPU (status object, RNG known answers, tables,
-! domain file round trip), prints key numbers for tests/test_fortran_shell.py.  "gpu": plane-parallel slab through
+! domain file round trip, in the current directory), prints key numbers for tests/test_fortran_shell.py.  "gpu": plane-parallel slab through
 ! new_Integrator / specifyParameters / computeRadiativeTransfer / reportResults on the device.
 program shellSelfTest
   use ErrorMessages
@@ -30,7 +30,7 @@ contains
     type(domain)               :: d, d2
     real    :: inverse(10001, 1), forward(10001, 1), angles(10001)
     real    :: ext(3, 2, 4), ssa(3, 2, 4), total(3, 2, 4), cum(3, 2, 4, 2), alb(3, 2, 4, 2), total2(3, 2, 4), cum2(3, 2, 4, 2)
-    integer :: idx(3, 2, 4), pfi(3, 2, 4, 2), i, nx, ny, nz, nc
+    integer :: idx(3, 2, 4), pfi(3, 2, 4, 2), i, nx, ny, nz, nc, u
     character(len = 64) :: names(2)
 
     r = new_RandomNumberSequence(100)
@@ -55,8 +55,10 @@ contains
     call addOpticalComponent(d, "cloud", ext, ssa, idx, table, status = status)
     call addOpticalComponent(d, "gas", (/ 0.001, 0.002 /), (/ 0.5, 0.5 /), (/ 1, 1 /), table, zLevelBase = 2, status = status)
     call getOpticalPropertiesByComponent(d, total, cum, alb, pfi, status = status)
-    call write_Domain(d, "/tmp/i3rc_shell_selftest.dom", status)
-    call read_Domain("/tmp/i3rc_shell_selftest.dom", d2, status)
+    call write_Domain(d, "i3rc_shell_selftest.dom", status)
+    call read_Domain("i3rc_shell_selftest.dom", d2, status)
+    open(newunit = u, file = "i3rc_shell_selftest.dom", status = "old", iostat = i)
+    if(i == 0) close(u, status = "delete")
     if(stateIsFailure(status)) print *, "domain round trip FAILED"
     call getInfo_Domain(d2, numX = nx, numY = ny, numZ = nz, numberOfComponents = nc, componentNames = names, status = status)
     call getOpticalPropertiesByComponent(d2, total2, cum2, alb, pfi, status = status)

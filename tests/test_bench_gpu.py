@@ -36,6 +36,28 @@ def test_gpus_1_goes_through_the_spawn_path():
     assert cf["matches_this_run"] in (True, None), cf
 
 
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    # a plain run measures the headline only (no CPU baseline); --dump-outputs writes what the last timed step computed, and the
+    # same arguments give the same inputs: a second run agrees array for array
+    import numpy as np
+
+    from i3rc_monte_carlo_model_amd import binding as B
+
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        j = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--photons", "2000000", "--dump-outputs", str(d)])
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["cpu_baseline"] is None and "weak" not in j
+        runs.append({f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))})
+    a, b = runs
+    assert sorted(a) == ["counters", "fluxAbsorbed", "fluxDown", "fluxUp", "volumeAbsorption"], sorted(a)
+    assert a["fluxUp"].dtype == np.float32 and a["fluxUp"].shape == (1, 32) and a["volumeAbsorption"].shape == (16, 1, 32)
+    assert a["counters"].dtype == np.float64 and a["counters"][B.COUNTER_NAMES.index("photons")] == 2000000
+    assert abs(float(a["fluxUp"].mean()) - j["result_check"]["meanFluxUp"]) < 2e-3
+    for k in a:
+        assert np.allclose(a[k], b[k], rtol=1e-5, atol=1e-7), k
+
+
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_two_ranks_end_to_end_in_rehearsal_mode(scaling):
     n = 1000001
@@ -57,9 +79,9 @@ def test_two_ranks_end_to_end_in_rehearsal_mode(scaling):
 
 def test_two_ranks_default_is_the_metrics_case_with_the_weak_figure_beside_it():
     # no --scaling: N > 1 reports ONE batch of --photons photons per step sharded over the ranks (strong) as the headline,
-    # three steps in flight, and the weak figure beside it
+    # three steps in flight, and (--full) the weak figure beside it
     n = 1000001
-    j = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--photons", str(n)], env=dict(I3RC_BENCH_REHEARSAL="1"))
+    j = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--photons", str(n), "--full"], env=dict(I3RC_BENCH_REHEARSAL="1"))
     assert j["scaling"] == "strong" and j["config"]["photons_per_step"] == n and j["config"]["steps_in_flight"] == 3
     assert j["weak"]["photons_per_step"] == 2 * n and j["weak"]["value"] > 1e6
     assert abs(j["result_check"]["meanFluxUp"] - 0.3253) < 3e-3
@@ -71,7 +93,8 @@ def test_configs_3_and_4_shard_the_nodes_batch_with_three_steps_in_flight(config
     # sharded over the ranks, three steps in flight (--overlap 2: three handles / streams / tally buffers whose all-reduces are
     # issued in step order), the weak figure beside it; every run starts with the first-contact check (process group up, one
     # all-reduce on every rank, under a watchdog).  Rehearsal mode: both ranks on GPU 0, tallies through gloo.
-    j = _bench(["--gpus", "2", "--config", config, "--steps", "4", "--warmup", "1", "--overlap", "2", "--scale-photons", str(scale), "--contact-timeout", "120"],
+    j = _bench(["--gpus", "2", "--config", config, "--steps", "4", "--warmup", "1", "--overlap", "2", "--scale-photons", str(scale), "--contact-timeout", "120",
+                "--full"],
                env=dict(I3RC_BENCH_REHEARSAL="1"))
     node = int(round(1_000_000_000 * scale))
     assert j["scaling"] == "strong" and j["config"]["photons_per_step"] == node and j["config"]["photons_per_gpu_per_step"] == node // 2

@@ -32,7 +32,7 @@ counters)
     # the profiled program is the rank itself (RANK set: bench.py's main() runs worker() at once), never bench.py's launcher
     ( export RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533
       rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$w -- python3 $R/bench.py --config $w --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_prof_$w.json 2> $O/bench_prof_$w.err ) || echo "stats $w failed"
-    python3 $R/bench.py --config $w > $O/bench_$w.json 2> $O/bench_$w.err || echo "bench $w failed"
+    python3 $R/bench.py --config $w --full > $O/bench_$w.json 2> $O/bench_$w.err || echo "bench $w failed"
     echo "$w done: $(python3 -c "import json;j=json.load(open('$O/bench_$w.json'));print('%.3e photons/s'%j['value'], j['roofline']['kernel'])")"
   done
   echo "evidence $TAG: counters done";;
