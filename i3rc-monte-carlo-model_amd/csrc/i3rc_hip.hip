@@ -1014,10 +1014,35 @@ int upload_source(i3rc_hip_integrator *h, const i3rc_source *src, int64_t n, Run
   return 0;
 }
 
+// A dispatch-table entry: the instantiation and its name, formatted from the same template arguments in the form
+// tools/kernel_resources.demangle_photon_kernel gives the code object's symbol.  lastKernelName is set from the entry that
+// is launched, so a name a test asserts on is the kernel that ran.
+using Kernel = void (*)(DevProblem, RunArgs, int, int);
+struct KernelEntry {
+  Kernel fn = nullptr;
+  const char *name = nullptr;
+};
+
+template <class Rng>
+constexpr const char *rng_name() {
+  if constexpr (Rng::kReplay) return "ReplayStream";
+  else if constexpr (Rng::kBatched) return "PhiloxBatchStream";
+  else return "PhiloxStream";
+}
+
+template <class Rng, bool INTENSITY, bool GENERAL, int GRID, bool TBL = false, bool DIRECT = false, bool MULTI = false>
+KernelEntry entry() {
+  static const char *const placeName[5] = {"GRID_LDS", "GRID_GLOBAL", "GRID_BRICKS", "GRID_COLUMNS", "GRID_COLBASE"};
+  static const std::string name = std::string("photon_kernel<") + rng_name<Rng>() + (INTENSITY ? ", true" : ", false") +
+                                  (GENERAL ? ", true, " : ", false, ") + placeName[GRID] + (TBL ? ", table in LDS" : "") +
+                                  (DIRECT ? ", one direction" : "") + (MULTI ? ", wide" : "") + ">";
+  return {photon_kernel<Rng, INTENSITY, GENERAL, GRID, TBL, DIRECT, MULTI>, name.c_str()};
+}
+
 template <class Rng, bool INTENSITY, bool GENERAL, bool DIRECT, bool MULTI>
-constexpr void (*colbase_kernel())(DevProblem, RunArgs, int, int) {
-  if constexpr (Rng::kReplay) return nullptr;
-  else return photon_kernel<Rng, INTENSITY, GENERAL, GRID_COLBASE, false, DIRECT, MULTI>;
+KernelEntry colbase_entry() {
+  if constexpr (Rng::kReplay) return {};
+  else return entry<Rng, INTENSITY, GENERAL, GRID_COLBASE, false, DIRECT, MULTI>();
 }
 
 template <class Rng>
@@ -1025,18 +1050,17 @@ int launch(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, boo
   // fast specialisations when the problem is in the common class (see photon_kernel), else the general kernel
   const bool simple = !Rng::kReplay && common_class(h, A.srcKind) && h->kernelVariant != I3RC_KERNEL_GENERAL && !(kNestedBuild && plan.intensity);
   // the specialised kernels exist once per place of the extinction grid (LDS / global / global in bricks)
-  using Kernel = void (*)(DevProblem, RunArgs, int, int);
   const int place = plan.place;
   // (GRID_COLBASE -- column records over a base profile -- exists for the kernels that run domains of several components: the general
   // ones and the several-components ones; make_problem never plans it for anything else)
-  static const Kernel general[2][5] = {
-      {photon_kernel<Rng, false, true, GRID_LDS>, photon_kernel<Rng, false, true, GRID_GLOBAL>, photon_kernel<Rng, false, true, GRID_BRICKS>, photon_kernel<Rng, false, true, GRID_COLUMNS>, colbase_kernel<Rng, false, true, false, false>()},
-      {photon_kernel<Rng, true, true, GRID_LDS>, photon_kernel<Rng, true, true, GRID_GLOBAL>, photon_kernel<Rng, true, true, GRID_BRICKS>, photon_kernel<Rng, true, true, GRID_COLUMNS>, colbase_kernel<Rng, true, true, false, false>()}};
-  Kernel kern = general[plan.intensity ? 1 : 0][place];
+  static const KernelEntry general[2][5] = {
+      {entry<Rng, false, true, GRID_LDS>(), entry<Rng, false, true, GRID_GLOBAL>(), entry<Rng, false, true, GRID_BRICKS>(), entry<Rng, false, true, GRID_COLUMNS>(), colbase_entry<Rng, false, true, false, false>()},
+      {entry<Rng, true, true, GRID_LDS>(), entry<Rng, true, true, GRID_GLOBAL>(), entry<Rng, true, true, GRID_BRICKS>(), entry<Rng, true, true, GRID_COLUMNS>(), colbase_entry<Rng, true, true, false, false>()}};
+  KernelEntry kern = general[plan.intensity ? 1 : 0][place];
   if constexpr (!Rng::kReplay) {   // (the replay build always runs the general kernel)
-    static const Kernel special[2][5] = {
-        {photon_kernel<Rng, false, false, GRID_LDS>, photon_kernel<Rng, false, false, GRID_GLOBAL>, photon_kernel<Rng, false, false, GRID_BRICKS>, photon_kernel<Rng, false, false, GRID_COLUMNS>, nullptr},
-        {photon_kernel<Rng, true, false, GRID_LDS>, photon_kernel<Rng, true, false, GRID_GLOBAL>, photon_kernel<Rng, true, false, GRID_BRICKS>, photon_kernel<Rng, true, false, GRID_COLUMNS>, nullptr}};
+    static const KernelEntry special[2][5] = {
+        {entry<Rng, false, false, GRID_LDS>(), entry<Rng, false, false, GRID_GLOBAL>(), entry<Rng, false, false, GRID_BRICKS>(), entry<Rng, false, false, GRID_COLUMNS>(), KernelEntry{}},
+        {entry<Rng, true, false, GRID_LDS>(), entry<Rng, true, false, GRID_GLOBAL>(), entry<Rng, true, false, GRID_BRICKS>(), entry<Rng, true, false, GRID_COLUMNS>(), KernelEntry{}}};
     if (simple) kern = special[plan.intensity ? 1 : 0][place];
     // several components, otherwise the common class: RADIANCE problems run photon_kernel<..., MULTI> (+20 % on the Landsat scene + gas
     // with seven directions against the general radiance kernels' 166 registers and three waves per SIMD).  Flux problems stay with
@@ -1045,15 +1069,15 @@ int launch(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, boo
     // reads do not show (profiles/r05_ab_experiments.txt) -- and is not in the tree.
     const bool multi = !simple && plan.intensity && multi_class(h, A.srcKind) && h->kernelVariant != I3RC_KERNEL_GENERAL && !kNestedBuild;
     if (multi) {
-      static const Kernel several[2][5] = {
-          {photon_kernel<Rng, true, false, GRID_LDS, false, false, true>, photon_kernel<Rng, true, false, GRID_GLOBAL, false, false, true>, photon_kernel<Rng, true, false, GRID_BRICKS, false, false, true>, photon_kernel<Rng, true, false, GRID_COLUMNS, false, false, true>, photon_kernel<Rng, true, false, GRID_COLBASE, false, false, true>},
-          {photon_kernel<Rng, true, false, GRID_LDS, false, true, true>, photon_kernel<Rng, true, false, GRID_GLOBAL, false, true, true>, photon_kernel<Rng, true, false, GRID_BRICKS, false, true, true>, photon_kernel<Rng, true, false, GRID_COLUMNS, false, true, true>, photon_kernel<Rng, true, false, GRID_COLBASE, false, true, true>}};
+      static const KernelEntry several[2][5] = {
+          {entry<Rng, true, false, GRID_LDS, false, false, true>(), entry<Rng, true, false, GRID_GLOBAL, false, false, true>(), entry<Rng, true, false, GRID_BRICKS, false, false, true>(), entry<Rng, true, false, GRID_COLUMNS, false, false, true>(), entry<Rng, true, false, GRID_COLBASE, false, false, true>()},
+          {entry<Rng, true, false, GRID_LDS, false, true, true>(), entry<Rng, true, false, GRID_GLOBAL, false, true, true>(), entry<Rng, true, false, GRID_BRICKS, false, true, true>(), entry<Rng, true, false, GRID_COLUMNS, false, true, true>(), entry<Rng, true, false, GRID_COLBASE, false, true, true>()}};
       kern = several[direct_rays(h) ? 1 : 0][place];
     } else
     if (plan.intensity && direct_rays(h)) {   // (the replay build keeps the nested local estimate: no queue at all)
-      static const Kernel direct[2][5] = {
-          {photon_kernel<Rng, true, true, GRID_LDS, false, true>, photon_kernel<Rng, true, true, GRID_GLOBAL, false, true>, photon_kernel<Rng, true, true, GRID_BRICKS, false, true>, photon_kernel<Rng, true, true, GRID_COLUMNS, false, true>, colbase_kernel<Rng, true, true, true, false>()},
-          {photon_kernel<Rng, true, false, GRID_LDS, false, true>, photon_kernel<Rng, true, false, GRID_GLOBAL, false, true>, photon_kernel<Rng, true, false, GRID_BRICKS, false, true>, photon_kernel<Rng, true, false, GRID_COLUMNS, false, true>, nullptr}};
+      static const KernelEntry direct[2][5] = {
+          {entry<Rng, true, true, GRID_LDS, false, true>(), entry<Rng, true, true, GRID_GLOBAL, false, true>(), entry<Rng, true, true, GRID_BRICKS, false, true>(), entry<Rng, true, true, GRID_COLUMNS, false, true>(), colbase_entry<Rng, true, true, true, false>()},
+          {entry<Rng, true, false, GRID_LDS, false, true>(), entry<Rng, true, false, GRID_GLOBAL, false, true>(), entry<Rng, true, false, GRID_BRICKS, false, true>(), entry<Rng, true, false, GRID_COLUMNS, false, true>(), KernelEntry{}}};
       kern = direct[simple ? 1 : 0][place];
     }
   }
@@ -1070,33 +1094,17 @@ int launch(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, boo
     static const int tblPlaces = std::getenv("I3RC_TABLE_LDS_PLACES") ? std::atoi(std::getenv("I3RC_TABLE_LDS_PLACES")) : 11;
     if (tblOn && simple && !plan.intensity && place != GRID_COLBASE && ((tblPlaces >> place) & 1) && (plan.P.uniformPf >= 1 || h->nInvEntries[0] == 1) && h->kernelVariant == I3RC_KERNEL_AUTO &&
         plan.ldsBytes + sizeof(float) * (size_t)plan.P.comp0.nInv <= 79 * 1024) {
-      static const Kernel tbl[4] = {photon_kernel<Rng, false, false, GRID_LDS, true>, photon_kernel<Rng, false, false, GRID_GLOBAL, true>,
-                                    photon_kernel<Rng, false, false, GRID_BRICKS, true>, photon_kernel<Rng, false, false, GRID_COLUMNS, true>};
+      static const KernelEntry tbl[4] = {entry<Rng, false, false, GRID_LDS, true>(), entry<Rng, false, false, GRID_GLOBAL, true>(),
+                                         entry<Rng, false, false, GRID_BRICKS, true>(), entry<Rng, false, false, GRID_COLUMNS, true>()};
       kern = tbl[place];
       threads = 1024;
       ldsBytes = lds_bytes<Rng>(h, plan, true);
     }
   }
   if (ldsBytes > 160 * 1024 - 256) return h->fail("the launch needs more LDS than a compute unit has");
-  if (!kern) return h->fail("internal: no kernel for this problem at this place of the extinction field");
-  const void *fn = (const void *)kern;
-  {
-    static const char *const placeName[5] = {"GRID_LDS", "GRID_GLOBAL", "GRID_BRICKS", "GRID_COLUMNS", "GRID_COLBASE"};
-    static thread_local char name[96];
-    std::snprintf(name, sizeof(name), "photon_kernel<%s, %s, %s, %s>", Rng::kReplay ? "ReplayStream" : "PhiloxStream",
-                       plan.intensity ? "true" : "false", (simple ? "false" : "true"), placeName[place]);
-    h->lastKernelName = name;
-    if (threads == 1024) { std::snprintf(name, sizeof(name), "photon_kernel<PhiloxStream, false, false, %s, table in LDS>", placeName[place]); h->lastKernelName = name; }
-    if (!Rng::kReplay && plan.intensity && direct_rays(h)) {
-      std::snprintf(name, sizeof(name), "photon_kernel<PhiloxStream, true, %s, %s, one direction>", (simple ? "false" : "true"), placeName[place]);
-      h->lastKernelName = name;
-    }
-    if (!Rng::kReplay && !simple && plan.intensity && multi_class(h, A.srcKind) && h->kernelVariant != I3RC_KERNEL_GENERAL && !kNestedBuild) {
-      std::snprintf(name, sizeof(name), "photon_kernel<PhiloxStream, %s, false, %s%s, wide>", plan.intensity ? "true" : "false", placeName[place],
-                    plan.intensity && direct_rays(h) ? ", one direction" : "");
-      h->lastKernelName = name;
-    }
-  }
+  if (!kern.fn) return h->fail("internal: no kernel for this problem at this place of the extinction field");
+  const void *fn = (const void *)kern.fn;
+  h->lastKernelName = kern.name;
   int perCU = h->blocksPerCU;
   if (perCU <= 0) {
     int occ = 0;
@@ -1159,7 +1167,7 @@ int launch(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, boo
     // thresholds the caller did not fix are adapted per wave (photon_kernel); negative = adaptive, starting value
     const int evThreshold = h->evThreshold > 0 ? h->evThreshold : -40;
     const int lightThreshold = h->lightThreshold > 0 ? h->lightThreshold : -24;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), ldsBytes, h->stream, plan.P, B, evThreshold, lightThreshold);
+    hipLaunchKernelGGL(kern.fn, dim3((unsigned)blocks), dim3(threads), ldsBytes, h->stream, plan.P, B, evThreshold, lightThreshold);
   }
   HIPCHK(h, hipGetLastError());
   if (timeIt) { HIPCHK(h, hipEventRecord(h->evStop[slot], h->stream)); h->timedLaunches++; }
@@ -1397,52 +1405,45 @@ int launch_fused_group(i3rc_hip_integrator *h, i3rc_hip_integrator::FusedSlot &g
   A.abortFlag = g.abortFlag;
   A.counterBlocks = (double *)g.counterBlocks.p;
   if ((uint64_t)count * R >= ((uint64_t)1 << 31)) return h->fail("fused launch: too many tally blocks");
-  using Kernel = void (*)(DevProblem, RunArgs, int, int);
-  static const Kernel kernels[5] = {photon_kernel<PhiloxBatchStream, false, false, GRID_LDS>, photon_kernel<PhiloxBatchStream, false, false, GRID_GLOBAL>,
-                                    photon_kernel<PhiloxBatchStream, false, false, GRID_BRICKS>, photon_kernel<PhiloxBatchStream, false, false, GRID_COLUMNS>, nullptr};
+  static const KernelEntry kernels[5] = {entry<PhiloxBatchStream, false, false, GRID_LDS>(), entry<PhiloxBatchStream, false, false, GRID_GLOBAL>(),
+                                         entry<PhiloxBatchStream, false, false, GRID_BRICKS>(), entry<PhiloxBatchStream, false, false, GRID_COLUMNS>(), KernelEntry{}};
   const int place = plan.place;
   // the widened class (several components, irregular x / y, a gridded surface): its own fused kernels, flux ones too -- a driver's loop
   // of 1e6-photon batches on Landsat-36 + gas then costs 1.1 ms per batch instead of 2.6 (profiles/r05_fused_wide.txt)
   const bool wide = !common_class(h, 0);
-  static const Kernel wideKernels[3][5] = {
-      {photon_kernel<PhiloxBatchStream, false, false, GRID_LDS, false, false, true>, photon_kernel<PhiloxBatchStream, false, false, GRID_GLOBAL, false, false, true>, photon_kernel<PhiloxBatchStream, false, false, GRID_BRICKS, false, false, true>, photon_kernel<PhiloxBatchStream, false, false, GRID_COLUMNS, false, false, true>, photon_kernel<PhiloxBatchStream, false, false, GRID_COLBASE, false, false, true>},
-      {photon_kernel<PhiloxBatchStream, true, false, GRID_LDS, false, false, true>, photon_kernel<PhiloxBatchStream, true, false, GRID_GLOBAL, false, false, true>, photon_kernel<PhiloxBatchStream, true, false, GRID_BRICKS, false, false, true>, photon_kernel<PhiloxBatchStream, true, false, GRID_COLUMNS, false, false, true>, photon_kernel<PhiloxBatchStream, true, false, GRID_COLBASE, false, false, true>},
-      {photon_kernel<PhiloxBatchStream, true, false, GRID_LDS, false, true, true>, photon_kernel<PhiloxBatchStream, true, false, GRID_GLOBAL, false, true, true>, photon_kernel<PhiloxBatchStream, true, false, GRID_BRICKS, false, true, true>, photon_kernel<PhiloxBatchStream, true, false, GRID_COLUMNS, false, true, true>, photon_kernel<PhiloxBatchStream, true, false, GRID_COLBASE, false, true, true>}};
+  static const KernelEntry wideKernels[3][5] = {
+      {entry<PhiloxBatchStream, false, false, GRID_LDS, false, false, true>(), entry<PhiloxBatchStream, false, false, GRID_GLOBAL, false, false, true>(), entry<PhiloxBatchStream, false, false, GRID_BRICKS, false, false, true>(), entry<PhiloxBatchStream, false, false, GRID_COLUMNS, false, false, true>(), entry<PhiloxBatchStream, false, false, GRID_COLBASE, false, false, true>()},
+      {entry<PhiloxBatchStream, true, false, GRID_LDS, false, false, true>(), entry<PhiloxBatchStream, true, false, GRID_GLOBAL, false, false, true>(), entry<PhiloxBatchStream, true, false, GRID_BRICKS, false, false, true>(), entry<PhiloxBatchStream, true, false, GRID_COLUMNS, false, false, true>(), entry<PhiloxBatchStream, true, false, GRID_COLBASE, false, false, true>()},
+      {entry<PhiloxBatchStream, true, false, GRID_LDS, false, true, true>(), entry<PhiloxBatchStream, true, false, GRID_GLOBAL, false, true, true>(), entry<PhiloxBatchStream, true, false, GRID_BRICKS, false, true, true>(), entry<PhiloxBatchStream, true, false, GRID_COLUMNS, false, true, true>(), entry<PhiloxBatchStream, true, false, GRID_COLBASE, false, true, true>()}};
   // (the inverse table's cosines in LDS, workgroups of 1024 threads: as in launch(); these instantiations are planned for eight
   // waves per SIMD -- two workgroups per compute unit -- and pay for it with two vector registers in scratch)
-  Kernel kern = kernels[place];
+  KernelEntry kern = kernels[place];
   int threads = 256;
   size_t ldsBytes = lds_bytes<PhiloxBatchStream>(h, plan, false);
   if (wide) kern = wideKernels[plan.intensity ? (direct_rays(h) ? 2 : 1) : 0][place];
   else
   if (plan.intensity) {   // radiance problems: through the event ring, or (one direction) without it -- as in launch()
-    static const Kernel ring[4] = {photon_kernel<PhiloxBatchStream, true, false, GRID_LDS>, photon_kernel<PhiloxBatchStream, true, false, GRID_GLOBAL>,
-                                   photon_kernel<PhiloxBatchStream, true, false, GRID_BRICKS>, photon_kernel<PhiloxBatchStream, true, false, GRID_COLUMNS>};
-    static const Kernel direct[4] = {photon_kernel<PhiloxBatchStream, true, false, GRID_LDS, false, true>, photon_kernel<PhiloxBatchStream, true, false, GRID_GLOBAL, false, true>,
-                                     photon_kernel<PhiloxBatchStream, true, false, GRID_BRICKS, false, true>, photon_kernel<PhiloxBatchStream, true, false, GRID_COLUMNS, false, true>};
+    static const KernelEntry ring[4] = {entry<PhiloxBatchStream, true, false, GRID_LDS>(), entry<PhiloxBatchStream, true, false, GRID_GLOBAL>(),
+                                        entry<PhiloxBatchStream, true, false, GRID_BRICKS>(), entry<PhiloxBatchStream, true, false, GRID_COLUMNS>()};
+    static const KernelEntry direct[4] = {entry<PhiloxBatchStream, true, false, GRID_LDS, false, true>(), entry<PhiloxBatchStream, true, false, GRID_GLOBAL, false, true>(),
+                                          entry<PhiloxBatchStream, true, false, GRID_BRICKS, false, true>(), entry<PhiloxBatchStream, true, false, GRID_COLUMNS, false, true>()};
     kern = direct_rays(h) ? direct[place] : ring[place];
   } else {
     static const bool tblOn = !(std::getenv("I3RC_TABLE_LDS") && std::atoi(std::getenv("I3RC_TABLE_LDS")) == 0);
     static const int tblPlaces = std::getenv("I3RC_FUSED_TABLE_LDS_PLACES") ? std::atoi(std::getenv("I3RC_FUSED_TABLE_LDS_PLACES")) : 11;   // (measured: Landsat-36 +13 %, radar 640 +12 %, step cloud +1.5 ... 3 % in the kernels' own time; on column records +1 ... 2.5 %)
     if (!wide && tblOn && ((tblPlaces >> place) & 1) && place != GRID_BRICKS && (plan.P.uniformPf >= 1 || h->nInvEntries[0] == 1) &&
         plan.ldsBytes + sizeof(float) * (size_t)plan.P.comp0.nInv <= 79 * 1024) {
-      static const Kernel tbl[4] = {photon_kernel<PhiloxBatchStream, false, false, GRID_LDS, true>, photon_kernel<PhiloxBatchStream, false, false, GRID_GLOBAL, true>,
-                                    nullptr, photon_kernel<PhiloxBatchStream, false, false, GRID_COLUMNS, true>};
+      static const KernelEntry tbl[4] = {entry<PhiloxBatchStream, false, false, GRID_LDS, true>(), entry<PhiloxBatchStream, false, false, GRID_GLOBAL, true>(),
+                                         KernelEntry{}, entry<PhiloxBatchStream, false, false, GRID_COLUMNS, true>()};
       kern = tbl[place];
       threads = 1024;
       ldsBytes = lds_bytes<PhiloxBatchStream>(h, plan, true);
     }
   }
   if (ldsBytes > 160 * 1024 - 256) return h->fail("the launch needs more LDS than a compute unit has");
-  if (!kern) return h->fail("internal: no fused kernel for this problem at this place of the extinction field");
-  const void *fn = (const void *)kern;
-  {
-    static const char *const placeName[5] = {"GRID_LDS", "GRID_GLOBAL", "GRID_BRICKS", "GRID_COLUMNS", "GRID_COLBASE"};
-    static thread_local char name[112];
-    std::snprintf(name, sizeof(name), "photon_kernel<PhiloxBatchStream, %s, false, %s%s%s>", plan.intensity ? "true" : "false", placeName[place],
-                  threads == 1024 ? ", table in LDS" : (plan.intensity && direct_rays(h) ? ", one direction" : ""), wide ? ", wide" : "");
-    h->lastKernelName = name;
-  }
+  if (!kern.fn) return h->fail("internal: no fused kernel for this problem at this place of the extinction field");
+  const void *fn = (const void *)kern.fn;
+  h->lastKernelName = kern.name;
   int perCU = h->blocksPerCU;
   if (perCU <= 0) {
     int occ = 0;
@@ -1465,7 +1466,7 @@ int launch_fused_group(i3rc_hip_integrator *h, i3rc_hip_integrator::FusedSlot &g
   {
     const int evThreshold = h->evThreshold > 0 ? h->evThreshold : -40;
     const int lightThreshold = h->lightThreshold > 0 ? h->lightThreshold : -24;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), ldsBytes, g.stream, plan.P, A, evThreshold, lightThreshold);
+    hipLaunchKernelGGL(kern.fn, dim3((unsigned)blocks), dim3(threads), ldsBytes, g.stream, plan.P, A, evThreshold, lightThreshold);
   }
   HIPCHK(h, hipGetLastError());
   if (timeIt) { HIPCHK(h, hipEventRecord(h->evStop[slot], g.stream)); h->timedLaunches++; }
