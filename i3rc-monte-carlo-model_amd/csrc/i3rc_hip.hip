@@ -170,6 +170,8 @@ struct i3rc_hip_integrator {
   int blocksPerCU = 0;  // 0 = from occupancy query
   int kernelVariant = I3RC_KERNEL_AUTO;  // test / tuning knob (i3rc_hip_select_kernel)
   std::string lastKernelName;            // kernel the most recent launch ran (i3rc_hip_last_kernel_name)
+  static constexpr int kPlanWords = 10;
+  int32_t lastPlan[kPlanWords] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // ... and its plan (i3rc_hip_last_plan)
   int64_t launchLimit = 0;               // photons per kernel launch (i3rc_hip_set_launch_limit); 0 = numCU * 2^22
   std::string err;
 
@@ -440,7 +442,22 @@ int i3rc_hip_create(i3rc_hip_integrator **out, int device, int nx, int ny, int n
     for (size_t i = 0; i < ncell; ++i) m = std::max(m, pfIndex[(size_t)c * ncell + i]);
     h->maxPfIndex[c] = m;
   }
-  for (size_t i = 0; i < ncell * (size_t)ncomp && !h->absorbing; ++i) h->absorbing = ssa[i] < 1.0f;
+  // Absorbing: some component has omega < 1 in a cell where the kernels can select it -- the rule of uniformSsa below, for several
+  // components.  They pick component 1 + (the number of k < ncomp - 1 with rc >= cumExt[k]) for a deviate rc in [0, 1] -- 1.0 itself
+  // included (u32_to_unit_float rounds the largest words up to it) --, so component c is selected on [cumExt[c - 1], cumExt[c]), the
+  // first from below 0 and the last up to above 1: it can be selected where that interval meets [0, 1].  A component without
+  // extinction in a cell is never selected there unless it is the last one, which a deviate of 1.0 selects wherever the slices before
+  // it reach 1.  (So a gas that is zero in some cells with omega = 0 there does not make a conservative domain absorbing as the first
+  // component, and does as the last: its omega is then used, rarely, and the absorbed weight must reach fluxAbsorbed.)
+  for (size_t i = 0; i < ncell && !h->absorbing; ++i) {
+    if (totalExt[i] == 0.0f) continue;
+    for (int c = 0; c < ncomp && !h->absorbing; ++c) {
+      const float lo = c == 0 ? -INFINITY : cumExt[(size_t)(c - 1) * ncell + i];
+      const float hi = c == ncomp - 1 ? INFINITY : cumExt[(size_t)c * ncell + i];
+      const bool selectable = lo <= 1.0f && hi > 0.0f && hi > lo;
+      h->absorbing = selectable && ssa[(size_t)c * ncell + i] < 1.0f;
+    }
+  }
   if (ncomp == 1) {
     // Values that every cell WITH EXTINCTION shares travel in the kernel arguments (specialised kernels: ray tracing, where a
     // photon can only be scattered in a cell of positive extinction -- the tracer never stops in any other --, so what the
@@ -923,6 +940,13 @@ int make_problem(i3rc_hip_integrator *h, LaunchPlan &plan, bool fused = false, b
     for (int c = 0; c < h->ncomp; ++c)
       if (h->maxPfIndex[c] >= 65536) return h->fail("radiance runs take at most 65535 phase-function table entries per component");
   if (lds > kLdsHard) return h->fail("domain edge vectors do not fit in LDS (nx + ny + nz beyond about 39 000)");
+  // (records over a base profile keep the profile in LDS as well: where edges and profile together are beyond what a launch may
+  // have, the automatic place reads the field as it would without the records -- in bricks beyond 4 MB, else linearly -- instead of
+  // planning a launch that launch's own check refuses)
+  if (P.colBase && h->gridPlace == I3RC_GRID_AUTO && lds + sizeof(float) * (size_t)h->nz > kLdsHard) {
+    P.colRec = nullptr; P.colBase = nullptr;
+    if (ncell_bytes(h) > ((size_t)4 << 20) && h->nz <= 65534) P.extBrick = (const float *)h->dExtBrick.p;
+  }
   const size_t budget = kLdsBudget;
   P.ldsTallies = 0;
   // (a fused multi-batch launch tallies per batch, straight into global memory: no partial sums in LDS)
@@ -1023,6 +1047,15 @@ struct KernelEntry {
   const char *name = nullptr;
 };
 
+// what i3rc_hip_last_plan reports of a launch: recorded where lastKernelName is, from the values the launch goes on with
+void record_plan(i3rc_hip_integrator *h, const LaunchPlan &plan, bool tableInLds, size_t ldsBytes, int fusedBatches) {
+  const DevProblem &P = plan.P;
+  const int rec = P.cellRec == nullptr ? 0 : (h->ncomp == 1 ? 8 : (h->ncomp == 2 ? 16 : 32));
+  const int32_t v[i3rc_hip_integrator::kPlanWords] = {P.ldsGrid ? 1 : 0, P.ldsTallies ? 1 : 0, P.ldsVolume ? 1 : 0, P.ldsIntensity ? 1 : 0,
+                                                      tableInLds ? 1 : 0, (int32_t)ldsBytes, h->absorbing ? 1 : 0, rec, fusedBatches, plan.place};
+  std::memcpy(h->lastPlan, v, sizeof(v));
+}
+
 template <class Rng>
 constexpr const char *rng_name() {
   if constexpr (Rng::kReplay) return "ReplayStream";
@@ -1088,6 +1121,7 @@ int launch(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, boo
   // I3RC_TABLE_LDS=0 switches it off.
   int threads = 256;
   size_t ldsBytes = lds_bytes<Rng>(h, plan, false);
+  bool tableInLds = false;
   if constexpr (!Rng::kReplay) {
     static const bool tblOn = !(std::getenv("I3RC_TABLE_LDS") && std::atoi(std::getenv("I3RC_TABLE_LDS")) == 0);
     // (grid places as a bit mask: LDS and global memory.  Bricked fields: Landsat-119 -2.5 %, the scene tiled 2 x 2 +10 %: left out)
@@ -1099,12 +1133,14 @@ int launch(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, boo
       kern = tbl[place];
       threads = 1024;
       ldsBytes = lds_bytes<Rng>(h, plan, true);
+      tableInLds = true;
     }
   }
   if (ldsBytes > 160 * 1024 - 256) return h->fail("the launch needs more LDS than a compute unit has");
   if (!kern.fn) return h->fail("internal: no kernel for this problem at this place of the extinction field");
   const void *fn = (const void *)kern.fn;
   h->lastKernelName = kern.name;
+  record_plan(h, plan, tableInLds, ldsBytes, 0);
   int perCU = h->blocksPerCU;
   if (perCU <= 0) {
     int occ = 0;
@@ -1444,6 +1480,7 @@ int launch_fused_group(i3rc_hip_integrator *h, i3rc_hip_integrator::FusedSlot &g
   if (!kern.fn) return h->fail("internal: no fused kernel for this problem at this place of the extinction field");
   const void *fn = (const void *)kern.fn;
   h->lastKernelName = kern.name;
+  record_plan(h, plan, threads == 1024, ldsBytes, count);
   int perCU = h->blocksPerCU;
   if (perCU <= 0) {
     int occ = 0;
@@ -2126,6 +2163,12 @@ int i3rc_hip_last_kernel_ms(i3rc_hip_integrator *h, float *ms) { return i3rc_hip
 int64_t i3rc_hip_timed_launch_count(const i3rc_hip_integrator *h) { return h ? (int64_t)h->timedLaunches : 0; }
 
 const char *i3rc_hip_last_kernel_name(const i3rc_hip_integrator *h) { return h ? h->lastKernelName.c_str() : ""; }
+
+int i3rc_hip_last_plan(const i3rc_hip_integrator *h, int32_t *out, int n) {
+  if (!h || !out) return 1;
+  for (int k = 0; k < std::min(n, i3rc_hip_integrator::kPlanWords); ++k) out[k] = h->lastPlan[k];
+  return 0;
+}
 
 int i3rc_hip_normalise(const i3rc_hip_integrator *h, const double *t, float *fluxUp, float *fluxDown, float *fluxAbsorbed,
                        float *volumeAbsorption, float *intensity, float *intensityByComponent) {

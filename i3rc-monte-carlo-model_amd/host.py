@@ -483,6 +483,12 @@ class Integrator:
             return "?"
         return self._lib.i3rc_hip_last_kernel_name(self._h).decode()
 
+    def last_plan(self):
+        """The plan of the most recent launch (i3rc_hip_last_plan) as a dict of B.PLAN_NAMES; every value -1 before the first."""
+        out = (C.c_int32 * len(B.PLAN_NAMES))()
+        self._check(self._lib.i3rc_hip_last_plan(self._h, out, len(B.PLAN_NAMES)), "last_plan")
+        return dict(zip(B.PLAN_NAMES, (int(v) for v in out)))
+
     def kernel_ms_history(self, n):
         ms = np.zeros(n, np.float32)
         self._check(self._lib.i3rc_hip_kernel_ms_history(self._h, int(n), pf(ms)), "kernel_ms_history")

@@ -286,6 +286,13 @@ int64_t i3rc_hip_timed_launch_count(const i3rc_hip_integrator *h);
  * (e.g. "photon_kernel<PhiloxStream, false, false, GRID_LDS>"); "" before the first launch. */
 const char *i3rc_hip_last_kernel_name(const i3rc_hip_integrator *h);
 
+/* Test hook: the plan of the most recent launch (recorded with i3rc_hip_last_kernel_name; reads state, decides nothing).
+ * out[0 .. min(n, 10) - 1]: field in LDS, flux tallies in LDS, volume tallies in LDS, radiance tallies in LDS, inverse table in
+ * LDS (0 / 1 each); dynamic LDS bytes; absorbing (0 / 1); cell records passed to the kernel (0: none, else their bytes: 8, 16 or 32); batches of
+ * the launch if it was a fused group (else 0); place of the extinction field (0 LDS, 1 global, 2 bricks, 3 column records,
+ * 4 column records over a base profile).  All -1 before the first launch.  Returns 0, or 1 on a null argument. */
+int i3rc_hip_last_plan(const i3rc_hip_integrator *h, int32_t *out, int n);
+
 /* Experiment knobs (not part of the reference API): lanes that must be waiting before a wavefront runs its
  * event phase (1..64; 0 = default: every wave adapts it to its photons' voxel steps per event, 44 - 2 steps per event
  * -- radiance kernels 44 - 1.2 steps per event -- within 12..44) and workgroups per CU (0 = occupancy query). */
