@@ -11,6 +11,7 @@
 #include <cstring>
 #include <ctime>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "kernels.hpp"
@@ -33,6 +34,13 @@ double trace_ms() {
   static const double t0 = ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
   return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6 - t0;
 }
+
+// Environment knobs (I3RC_*, read once per process where they are used): a switch that is on unless set to 0, ...
+bool env_on(const char *name) { const char *v = std::getenv(name); return !(v && std::atoi(v) == 0); }
+// ... an integer with a default, ...
+long long env_int(const char *name, long long dflt) { const char *v = std::getenv(name); return v ? std::atoll(v) : dflt; }
+// ... and a pair of integers "a,b" (false where unset or not of that form)
+bool env_pair(const char *name, int &a, int &b) { const char *v = std::getenv(name); return v && std::sscanf(v, "%d,%d", &a, &b) == 2; }
 
 
 struct DevBuf {
@@ -344,10 +352,8 @@ int i3rc_hip_create(i3rc_hip_integrator **out, int device, int nx, int ny, int n
     auto log2le = [](int n, int cap) { int s = 0; while ((2 << s) <= n && s + 1 <= cap) ++s; return s; };
     h->bsz = log2le(nz, 3);
     h->bsy = log2le(ny, (5 - h->bsz) / 2);
-    if (const char *e = std::getenv("I3RC_BRICK")) {   // tuning knob: "<log2 depth>,<log2 width in y>" (the rest of the 32 cells in x)
-      int bz = 3, by = 1;
-      if (std::sscanf(e, "%d,%d", &bz, &by) == 2 && bz >= 0 && by >= 0 && bz + by <= 5) { h->bsz = log2le(nz, bz); h->bsy = log2le(ny, by); }
-    }
+    int bz, by;   // tuning knob: "<log2 depth>,<log2 width in y>" (the rest of the 32 cells in x)
+    if (env_pair("I3RC_BRICK", bz, by) && bz >= 0 && by >= 0 && bz + by <= 5) { h->bsz = log2le(nz, bz); h->bsy = log2le(ny, by); }
     h->bsx = 5 - h->bsz - h->bsy;
     h->nbx = (nx + (1 << h->bsx) - 1) >> h->bsx; h->nby = (ny + (1 << h->bsy) - 1) >> h->bsy;
     h->nbz = (nz + 1 + (1 << h->bsz) - 1) >> h->bsz;   // (room for the layer nz + 1 of zeros, as in dExt)
@@ -396,9 +402,9 @@ int i3rc_hip_create(i3rc_hip_integrator **out, int device, int nx, int ny, int n
   CCHK(h->dCum.upload(cumExt, sizeof(float) * ncell * ncomp));
   CCHK(h->dSsa.upload(ssa, sizeof(float) * ncell * ncomp));
   CCHK(h->dPf.upload(pfIndex, sizeof(int32_t) * ncell * ncomp));
-  if (ncomp == 2 || ncomp == 3) {   // (DevProblem::cellRec)
-    static const bool recOn = !(std::getenv("I3RC_CELL_RECORDS") && std::atoi(std::getenv("I3RC_CELL_RECORDS")) == 0);
-    bool fits = recOn;
+  static const bool cellRecordsOn = env_on("I3RC_CELL_RECORDS");   // (DevProblem::cellRec; 0: the kernels read the plain arrays)
+  if (ncomp == 2 || ncomp == 3) {
+    bool fits = cellRecordsOn;
     for (size_t i = 0; i < 2 * ncell && fits; ++i) fits = pfIndex[i] >= 0 && pfIndex[i] < 65536;   // (the first two entries share a word)
     if (fits) {
       auto bits = [](float v) { uint32_t b; std::memcpy(&b, &v, 4); return b; };
@@ -475,13 +481,10 @@ int i3rc_hip_create(i3rc_hip_integrator **out, int device, int nx, int ny, int n
     h->uniformSsa = (sameSsa && ssa0 >= 0.f) ? ssa0 : -1.f;
     h->uniformPf = (samePf && pf0 >= 1) ? pf0 : 0;
   }
-  if (ncomp == 1 && h->uniformSsa < 0.0f && h->uniformPf < 1) {   // one component, neither albedo nor entry shared: {ssa, pfIndex}, 8 bytes a cell
-    static const bool recOn1 = !(std::getenv("I3RC_CELL_RECORDS") && std::atoi(std::getenv("I3RC_CELL_RECORDS")) == 0);
-    if (recOn1) {
-      std::vector<uint32_t> rec(2 * ncell);
-      for (size_t i = 0; i < ncell; ++i) { std::memcpy(&rec[2 * i], &ssa[i], 4); rec[2 * i + 1] = (uint32_t)pfIndex[i]; }
-      if (h->dCellRec.upload(rec.data(), sizeof(uint32_t) * rec.size()) != hipSuccess) { g_createError = "i3rc_hip_create: device allocation of the cell records failed"; delete h; return 1; }
-    }
+  if (ncomp == 1 && h->uniformSsa < 0.0f && h->uniformPf < 1 && cellRecordsOn) {   // one component, neither albedo nor entry shared: {ssa, pfIndex}, 8 bytes a cell
+    std::vector<uint32_t> rec(2 * ncell);
+    for (size_t i = 0; i < ncell; ++i) { std::memcpy(&rec[2 * i], &ssa[i], 4); rec[2 * i + 1] = (uint32_t)pfIndex[i]; }
+    if (h->dCellRec.upload(rec.data(), sizeof(uint32_t) * rec.size()) != hipSuccess) { g_createError = "i3rc_hip_create: device allocation of the cell records failed"; delete h; return 1; }
   }
   // defaults of type(integrator) :54-129
   h->params.surfaceAlbedo = 0.f; h->params.useSurfaceBDRF = 0; h->params.useRayTracing = 1; h->params.useRussianRoulette = 1;
@@ -508,11 +511,12 @@ int i3rc_hip_destroy(i3rc_hip_integrator *h) {
   }
   for (auto &g : h->fused) if (g.abortFlag) __atomic_store_n(g.abortFlag, 1, __ATOMIC_RELEASE);
   if (tracing()) std::fprintf(stderr, "[i3rc %9.3f ms] destroy: abort words set\n", trace_ms());
-  for (int k = 0; k < i3rc_hip_integrator::kFusedSlots; ++k) {
-    auto &g = h->fused[k];
-    bool shared = false;   // (the slots normally share the first one's stream)
-    for (int j = 0; j < k; ++j) shared = shared || (g.stream && g.stream == h->fused[j].stream);
-    if (g.stream && !shared) { (void)hipStreamSynchronize(g.stream); if (tracing()) std::fprintf(stderr, "[i3rc %9.3f ms] destroy: fused stream drained\n", trace_ms()); (void)hipStreamDestroy(g.stream); }
+  if (const hipStream_t s = h->fused[0].stream) {   // (the slots share the first one's stream)
+    (void)hipStreamSynchronize(s);
+    if (tracing()) std::fprintf(stderr, "[i3rc %9.3f ms] destroy: fused stream drained\n", trace_ms());
+    (void)hipStreamDestroy(s);
+  }
+  for (auto &g : h->fused) {
     if (g.done) (void)hipEventDestroy(g.done);
     if (g.traced) (void)hipEventDestroy(g.traced);
     if (g.pinned) (void)hipHostFree(g.pinned);
@@ -839,12 +843,9 @@ bool common_class(const i3rc_hip_integrator *h, int srcKind) {
   const bool gridSurface = h->params.useSurfaceBDRF && !uniform_surface(h);
   return h->xyRegular && traced(h) && !gridSurface && h->ncomp == 1 && srcKind == 0;
 }
-// ... and the same class widened: several components (photon_kernel, MULTI; round 5).  I3RC_MULTI=0 leaves such problems to the general kernels.
+// ... and the same class widened: several components (photon_kernel, MULTI; round 5).
 // (... and, since the kernels that run it keep those two paths behind run-time switches, with an irregular x / y grid or a gridded surface)
-bool multi_class(const i3rc_hip_integrator *h, int srcKind) {
-  static const bool on = !(std::getenv("I3RC_MULTI") && std::atoi(std::getenv("I3RC_MULTI")) == 0);
-  return on && traced(h) && srcKind == 0;
-}
+bool multi_class(const i3rc_hip_integrator *h, int srcKind) { return traced(h) && srcKind == 0; }
 
 // One radiance direction (nadir views: BASELINE.json's radar case): the radiance kernels without an event ring (photon_kernel,
 // DIRECT).  I3RC_DIRECT=0 keeps the ring for them too.
@@ -854,13 +855,14 @@ constexpr bool kNestedBuild = true;
 constexpr bool kNestedBuild = false;
 #endif
 bool direct_rays(const i3rc_hip_integrator *h) {
-  static const bool on = !(std::getenv("I3RC_DIRECT") && std::atoi(std::getenv("I3RC_DIRECT")) == 0);
+  static const bool on = env_on("I3RC_DIRECT");
   return on && h->nDir == 1 && h->kernelVariant != I3RC_KERNEL_RING && !kNestedBuild;
 }
 
 size_t ncell_bytes(const i3rc_hip_integrator *h) { return sizeof(float) * (size_t)h->nx * h->ny * h->nz; }
 
-int make_problem(i3rc_hip_integrator *h, LaunchPlan &plan, bool fused = false, bool replay = false) {
+// (stream: where the launch goes, tally: the buffer it adds to)
+int make_problem(i3rc_hip_integrator *h, LaunchPlan &plan, hipStream_t stream, double *tally, bool fused = false, bool replay = false) {
   DevProblem &P = plan.P;
   std::memset(&P, 0, sizeof(P));
   for (int c = 0; c < h->ncomp; ++c)
@@ -879,7 +881,7 @@ int make_problem(i3rc_hip_integrator *h, LaunchPlan &plan, bool fused = false, b
   // (the clear-air map of a bricked field holds layer numbers in 16 bits: domains of more layers than that keep the linear field)
   // Column records where the field has them (and does not fit in LDS, below): the whole field in 8 bytes per column.  Measured:
   // I3RC_COLUMNS=0 switches them off for the process.
-  static const bool columnsOn = !(std::getenv("I3RC_COLUMNS") && std::atoi(std::getenv("I3RC_COLUMNS")) == 0);
+  static const bool columnsOn = env_on("I3RC_COLUMNS");
   // (records over a base profile -- GRID_COLBASE -- are read by the kernels of domains with several components, the general and the
   // several-components ones: the one-component specialisations and the replay build are not instantiated for them)
   const bool baseForm = h->dColBase.p != nullptr;
@@ -898,7 +900,7 @@ int make_problem(i3rc_hip_integrator *h, LaunchPlan &plan, bool fused = false, b
     // the device copy of the table descriptors follows the host copy when a table was (re)set: a blocking copy after
     // the stream has drained (launches in flight read the old descriptors), not an asynchronous copy from the
     // pageable handle per launch
-    if (hipStreamSynchronize(h->stream) != hipSuccess ||
+    if (hipStreamSynchronize(stream) != hipSuccess ||
         hipMemcpy(h->dComp.p, h->comp.data(), sizeof(CompTables) * h->ncomp, hipMemcpyHostToDevice) != hipSuccess)
       return h->fail("copying the component table descriptors failed");
     h->compDirty = false;
@@ -923,7 +925,7 @@ int make_problem(i3rc_hip_integrator *h, LaunchPlan &plan, bool fused = false, b
   P.dirCos = (const float *)h->dDir.p;
   P.uniformSsa = h->uniformSsa; P.uniformPf = h->uniformPf;
   if (h->layout.total >= ((int64_t)1 << 31)) return h->fail("tally buffer too large (2^31 elements or more)");
-  P.tally = h->tally;
+  P.tally = tally;
   P.oUp = (int)h->layout.fluxUp; P.oDown = (int)h->layout.fluxDown; P.oAbs = (int)h->layout.fluxAbsorbed;
   P.oVol = (int)h->layout.volumeAbsorption; P.oInt = (int)h->layout.intensityByComponent;
   P.oExc = (int)h->layout.intensityExcess; P.oCnt = (int)h->layout.counters;
@@ -952,7 +954,7 @@ int make_problem(i3rc_hip_integrator *h, LaunchPlan &plan, bool fused = false, b
   // (a fused multi-batch launch tallies per batch, straight into global memory: no partial sums in LDS)
   // (float64 partial sums: tracer.hpp, tally_t; + 4: their 8-byte alignment.  I3RC_LDS_TALLIES=0 / i3rc_hip_set_lds_tallies(h, 0): every
   // tally straight to the float64 buffer in global memory -- a measurement knob, and one more order of the same float64 additions)
-  static const bool ldsTalliesEnv = !(std::getenv("I3RC_LDS_TALLIES") && std::atoi(std::getenv("I3RC_LDS_TALLIES")) == 0);
+  static const bool ldsTalliesEnv = env_on("I3RC_LDS_TALLIES");
   const bool privatise = !fused && ldsTalliesEnv && h->ldsTalliesOn;
   if (privatise && lds + 2 * ncol * sizeof(tally_t) + 4 <= kLdsBudget / 2) { P.ldsTallies = 1; lds += 2 * ncol * sizeof(tally_t) + 4; }
   // (an absorbing domain of few cells -- the step cloud's 512 or 1024 --: its volume-absorption tallies, which every scattering adds to)
@@ -1038,13 +1040,22 @@ int upload_source(i3rc_hip_integrator *h, const i3rc_source *src, int64_t n, Run
   return 0;
 }
 
-// A dispatch-table entry: the instantiation and its name, formatted from the same template arguments in the form
-// tools/kernel_resources.demangle_photon_kernel gives the code object's symbol.  lastKernelName is set from the entry that
-// is launched, so a name a test asserts on is the kernel that ran.
+// A production instantiation of photon_kernel: its template arguments after the stream -- the key a launch looks it up by --, the kernel
+// and its name, formatted from the same arguments in the form tools/kernel_resources.demangle_photon_kernel gives the code object's
+// symbol.  lastKernelName is set from the entry that is launched, so a name a test asserts on is the kernel that ran.
 using Kernel = void (*)(DevProblem, RunArgs, int, int);
+struct KernelKey {
+  bool intensity, general;
+  int place;                 // GridPlace
+  bool tbl, direct, wide;    // (the inverse table in LDS; one radiance direction without the event ring; the widened class, MULTI)
+  bool operator==(const KernelKey &o) const {
+    return intensity == o.intensity && general == o.general && place == o.place && tbl == o.tbl && direct == o.direct && wide == o.wide;
+  }
+};
 struct KernelEntry {
-  Kernel fn = nullptr;
-  const char *name = nullptr;
+  KernelKey key;
+  Kernel fn;
+  const char *name;
 };
 
 // what i3rc_hip_last_plan reports of a launch: recorded where lastKernelName is, from the values the launch goes on with
@@ -1063,84 +1074,130 @@ constexpr const char *rng_name() {
   else return "PhiloxStream";
 }
 
-template <class Rng, bool INTENSITY, bool GENERAL, int GRID, bool TBL = false, bool DIRECT = false, bool MULTI = false>
+template <class Rng, bool INTENSITY, bool GENERAL, int GRID, bool TBL, bool DIRECT, bool MULTI>
 KernelEntry entry() {
   static const char *const placeName[5] = {"GRID_LDS", "GRID_GLOBAL", "GRID_BRICKS", "GRID_COLUMNS", "GRID_COLBASE"};
   static const std::string name = std::string("photon_kernel<") + rng_name<Rng>() + (INTENSITY ? ", true" : ", false") +
                                   (GENERAL ? ", true, " : ", false, ") + placeName[GRID] + (TBL ? ", table in LDS" : "") +
                                   (DIRECT ? ", one direction" : "") + (MULTI ? ", wide" : "") + ">";
-  return {photon_kernel<Rng, INTENSITY, GENERAL, GRID, TBL, DIRECT, MULTI>, name.c_str()};
+  return {{INTENSITY, GENERAL, GRID, TBL, DIRECT, MULTI}, photon_kernel<Rng, INTENSITY, GENERAL, GRID, TBL, DIRECT, MULTI>, name.c_str()};
 }
 
-template <class Rng, bool INTENSITY, bool GENERAL, bool DIRECT, bool MULTI>
-KernelEntry colbase_entry() {
-  if constexpr (Rng::kReplay) return {};
-  else return entry<Rng, INTENSITY, GENERAL, GRID_COLBASE, false, DIRECT, MULTI>();
+// the instantiation at each of the places GRID... of the extinction field
+template <class Rng, bool INTENSITY, bool GENERAL, bool TBL, bool DIRECT, bool MULTI, int... GRID>
+void add(std::vector<KernelEntry> &v, std::integer_sequence<int, GRID...>) {
+  (..., v.push_back(entry<Rng, INTENSITY, GENERAL, GRID, TBL, DIRECT, MULTI>()));
 }
+using AllPlaces = std::integer_sequence<int, GRID_LDS, GRID_GLOBAL, GRID_BRICKS, GRID_COLUMNS, GRID_COLBASE>;
+// (GRID_COLBASE -- column records over a base profile -- exists for the kernels that run domains of several components: the general
+// ones and the widened ones; make_problem never plans it for anything else, nor for the replay build)
+using NoColbase = std::integer_sequence<int, GRID_LDS, GRID_GLOBAL, GRID_BRICKS, GRID_COLUMNS>;
 
+// The production instantiations, once per stream.  Template arguments after the stream: INTENSITY, GENERAL, TBL, DIRECT, MULTI.
 template <class Rng>
-int launch(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, bool timeIt) {
-  // fast specialisations when the problem is in the common class (see photon_kernel), else the general kernel
-  const bool simple = !Rng::kReplay && common_class(h, A.srcKind) && h->kernelVariant != I3RC_KERNEL_GENERAL && !(kNestedBuild && plan.intensity);
-  // the specialised kernels exist once per place of the extinction grid (LDS / global / global in bricks)
+const std::vector<KernelEntry> &stream_kernels() {
+  static const std::vector<KernelEntry> list = [] {
+    std::vector<KernelEntry> v;
+    if constexpr (Rng::kBatched) {   // fused multi-batch launches
+      add<Rng, false, false, false, false, false>(v, NoColbase{});   // flux, the common class
+      add<Rng, false, false, false, false, true>(v, AllPlaces{});    // the widened class: flux, ...
+      add<Rng, true, false, false, false, true>(v, AllPlaces{});     // ... radiance through the event ring, ...
+      add<Rng, true, false, false, true, true>(v, AllPlaces{});      // ... one radiance direction
+      add<Rng, true, false, false, false, false>(v, NoColbase{});    // radiance through the event ring
+      add<Rng, true, false, false, true, false>(v, NoColbase{});     // one radiance direction
+      add<Rng, false, false, true, false, false>(v, std::integer_sequence<int, GRID_LDS, GRID_GLOBAL, GRID_COLUMNS>{});   // flux, table in LDS
+    } else if constexpr (!Rng::kReplay) {
+      add<Rng, false, true, false, false, false>(v, AllPlaces{});    // the general kernels: flux, ...
+      add<Rng, true, true, false, false, false>(v, AllPlaces{});     // ... radiance through the event ring
+      add<Rng, false, false, false, false, false>(v, NoColbase{});   // the common class: flux, ...
+      add<Rng, true, false, false, false, false>(v, NoColbase{});    // ... radiance through the event ring
+      add<Rng, true, false, false, false, true>(v, AllPlaces{});     // the widened class: radiance through the event ring, ...
+      add<Rng, true, false, false, true, true>(v, AllPlaces{});      // ... one radiance direction
+      add<Rng, true, true, false, true, false>(v, AllPlaces{});      // one radiance direction: general, ...
+      add<Rng, true, false, false, true, false>(v, NoColbase{});     // ... the common class
+      add<Rng, false, false, true, false, false>(v, NoColbase{});    // flux, the common class, table in LDS
+    } else {   // (the replay build runs the general kernels only)
+      add<Rng, false, true, false, false, false>(v, NoColbase{});
+      add<Rng, true, true, false, false, false>(v, NoColbase{});
+    }
+    return v;
+  }();
+  return list;
+}
+
+struct KernelChoice {
+  const KernelEntry *kern;   // nullptr: the stream has no instantiation for the key
+  int threads;
+  bool tableInLds;
+};
+
+// Which kernel runs a launch (see photon_kernel).  Fused launches (PhiloxBatchStream) are made for the specialised problems only
+// (fuse_loop): the common class, or the widened one.  Plain launches run the specialised kernels when the problem is in the common
+// class, the widened radiance kernels for radiance problems of the widened class, else the general kernel.
+template <class Rng>
+KernelChoice choose_kernel(const i3rc_hip_integrator *h, const LaunchPlan &plan, int srcKind) {
+  constexpr bool fused = Rng::kBatched;
   const int place = plan.place;
-  // (GRID_COLBASE -- column records over a base profile -- exists for the kernels that run domains of several components: the general
-  // ones and the several-components ones; make_problem never plans it for anything else)
-  static const KernelEntry general[2][5] = {
-      {entry<Rng, false, true, GRID_LDS>(), entry<Rng, false, true, GRID_GLOBAL>(), entry<Rng, false, true, GRID_BRICKS>(), entry<Rng, false, true, GRID_COLUMNS>(), colbase_entry<Rng, false, true, false, false>()},
-      {entry<Rng, true, true, GRID_LDS>(), entry<Rng, true, true, GRID_GLOBAL>(), entry<Rng, true, true, GRID_BRICKS>(), entry<Rng, true, true, GRID_COLUMNS>(), colbase_entry<Rng, true, true, false, false>()}};
-  KernelEntry kern = general[plan.intensity ? 1 : 0][place];
-  if constexpr (!Rng::kReplay) {   // (the replay build always runs the general kernel)
-    static const KernelEntry special[2][5] = {
-        {entry<Rng, false, false, GRID_LDS>(), entry<Rng, false, false, GRID_GLOBAL>(), entry<Rng, false, false, GRID_BRICKS>(), entry<Rng, false, false, GRID_COLUMNS>(), KernelEntry{}},
-        {entry<Rng, true, false, GRID_LDS>(), entry<Rng, true, false, GRID_GLOBAL>(), entry<Rng, true, false, GRID_BRICKS>(), entry<Rng, true, false, GRID_COLUMNS>(), KernelEntry{}}};
-    if (simple) kern = special[plan.intensity ? 1 : 0][place];
-    // several components, otherwise the common class: RADIANCE problems run photon_kernel<..., MULTI> (+20 % on the Landsat scene + gas
-    // with seven directions against the general radiance kernels' 166 registers and three waves per SIMD).  Flux problems stay with
-    // the general flux kernel: its several-components specialisation was built and measured -- 5.78 against 5.71e8 photons/s on
-    // Landsat-119 + gas, 9.13 against 9.08e8 on Landsat-36 + gas: the voxel steps are the same code, and a flux event's few extra
-    // reads do not show (profiles/r05_ab_experiments.txt) -- and is not in the tree.
-    const bool multi = !simple && plan.intensity && multi_class(h, A.srcKind) && h->kernelVariant != I3RC_KERNEL_GENERAL && !kNestedBuild;
-    if (multi) {
-      static const KernelEntry several[2][5] = {
-          {entry<Rng, true, false, GRID_LDS, false, false, true>(), entry<Rng, true, false, GRID_GLOBAL, false, false, true>(), entry<Rng, true, false, GRID_BRICKS, false, false, true>(), entry<Rng, true, false, GRID_COLUMNS, false, false, true>(), entry<Rng, true, false, GRID_COLBASE, false, false, true>()},
-          {entry<Rng, true, false, GRID_LDS, false, true, true>(), entry<Rng, true, false, GRID_GLOBAL, false, true, true>(), entry<Rng, true, false, GRID_BRICKS, false, true, true>(), entry<Rng, true, false, GRID_COLUMNS, false, true, true>(), entry<Rng, true, false, GRID_COLBASE, false, true, true>()}};
-      kern = several[direct_rays(h) ? 1 : 0][place];
-    } else
-    if (plan.intensity && direct_rays(h)) {   // (the replay build keeps the nested local estimate: no queue at all)
-      static const KernelEntry direct[2][5] = {
-          {entry<Rng, true, true, GRID_LDS, false, true>(), entry<Rng, true, true, GRID_GLOBAL, false, true>(), entry<Rng, true, true, GRID_BRICKS, false, true>(), entry<Rng, true, true, GRID_COLUMNS, false, true>(), colbase_entry<Rng, true, true, true, false>()},
-          {entry<Rng, true, false, GRID_LDS, false, true>(), entry<Rng, true, false, GRID_GLOBAL, false, true>(), entry<Rng, true, false, GRID_BRICKS, false, true>(), entry<Rng, true, false, GRID_COLUMNS, false, true>(), KernelEntry{}}};
-      kern = direct[simple ? 1 : 0][place];
-    }
-  }
-  // Flux problems of the common class with ONE phase-function entry keep the inverse table's cosines (40 KB) in LDS, in
-  // workgroups of 1024 threads, two per compute unit (photon_kernel, TBL): the two dependent table reads of a scattering come
-  // from LDS instead of L2 -- or, where the extinction field fills the L2 (Landsat-36: 2.4 MB of 4), instead of the fabric.
-  // Step cloud 29.75 -> 29.29 ms per 1e8 photons (+1.6 %), radar 640 +2 %, Landsat-36 87.0 -> 71.0 ms (+22 %).
-  // I3RC_TABLE_LDS=0 switches it off.
+  KernelKey key{plan.intensity, true, place, false, false, false};
   int threads = 256;
-  size_t ldsBytes = lds_bytes<Rng>(h, plan, false);
-  bool tableInLds = false;
-  if constexpr (!Rng::kReplay) {
-    static const bool tblOn = !(std::getenv("I3RC_TABLE_LDS") && std::atoi(std::getenv("I3RC_TABLE_LDS")) == 0);
-    // (grid places as a bit mask: LDS and global memory.  Bricked fields: Landsat-119 -2.5 %, the scene tiled 2 x 2 +10 %: left out)
-    static const int tblPlaces = std::getenv("I3RC_TABLE_LDS_PLACES") ? std::atoi(std::getenv("I3RC_TABLE_LDS_PLACES")) : 11;
-    if (tblOn && simple && !plan.intensity && place != GRID_COLBASE && ((tblPlaces >> place) & 1) && (plan.P.uniformPf >= 1 || h->nInvEntries[0] == 1) && h->kernelVariant == I3RC_KERNEL_AUTO &&
+  if constexpr (!Rng::kReplay) {   // (the replay build always runs the general kernel: it keeps the nested local estimate, no queue at all)
+    bool simple, wide;
+    if (fused) {
+      // the widened class (several components, irregular x / y, a gridded surface): its own fused kernels, flux ones too -- a driver's
+      // loop of 1e6-photon batches on Landsat-36 + gas then costs 1.1 ms per batch instead of 2.6 (profiles/r05_fused_wide.txt)
+      simple = common_class(h, srcKind);
+      wide = !simple;
+    } else {
+      simple = common_class(h, srcKind) && h->kernelVariant != I3RC_KERNEL_GENERAL && !(kNestedBuild && plan.intensity);
+      // several components, otherwise the common class: RADIANCE problems run photon_kernel<..., MULTI> (+20 % on the Landsat scene + gas
+      // with seven directions against the general radiance kernels' 166 registers and three waves per SIMD).  Flux problems stay with
+      // the general flux kernel: its several-components specialisation was built and measured -- 5.78 against 5.71e8 photons/s on
+      // Landsat-119 + gas, 9.13 against 9.08e8 on Landsat-36 + gas: the voxel steps are the same code, and a flux event's few extra
+      // reads do not show (profiles/r05_ab_experiments.txt) -- and is not in the tree.
+      wide = !simple && plan.intensity && multi_class(h, srcKind) && h->kernelVariant != I3RC_KERNEL_GENERAL && !kNestedBuild;
+    }
+    key.general = !simple && !wide;
+    key.wide = wide;
+    key.direct = plan.intensity && direct_rays(h);
+    // Flux problems of the common class with ONE phase-function entry keep the inverse table's cosines (40 KB) in LDS, in
+    // workgroups of 1024 threads, two per compute unit (photon_kernel, TBL): the two dependent table reads of a scattering come
+    // from LDS instead of L2 -- or, where the extinction field fills the L2 (Landsat-36: 2.4 MB of 4), instead of the fabric.
+    // Step cloud 29.75 -> 29.29 ms per 1e8 photons (+1.6 %), radar 640 +2 %, Landsat-36 87.0 -> 71.0 ms (+22 %).  The fused
+    // instantiations are planned for eight waves per SIMD -- two workgroups per compute unit -- and pay for it with two vector
+    // registers in scratch.  I3RC_TABLE_LDS=0 switches both off.
+    static const bool tblOn = env_on("I3RC_TABLE_LDS");
+    // (grid places as a bit mask: LDS, global memory and column records.  Plain launches on bricked fields: Landsat-119 -2.5 %, the
+    // scene tiled 2 x 2 +10 %: left out.  Fused: Landsat-36 +13 %, radar 640 +12 %, step cloud +1.5 ... 3 % in the kernels' own time;
+    // on column records +1 ... 2.5 %)
+    static const int plainPlaces = (int)env_int("I3RC_TABLE_LDS_PLACES", 11);
+    static const int fusedPlaces = (int)env_int("I3RC_FUSED_TABLE_LDS_PLACES", 11);
+    const bool placeOk = fused ? ((fusedPlaces >> place) & 1) && place != GRID_BRICKS
+                               : ((plainPlaces >> place) & 1) && place != GRID_COLBASE && h->kernelVariant == I3RC_KERNEL_AUTO;
+    if (tblOn && simple && !plan.intensity && placeOk && (plan.P.uniformPf >= 1 || h->nInvEntries[0] == 1) &&
         plan.ldsBytes + sizeof(float) * (size_t)plan.P.comp0.nInv <= 79 * 1024) {
-      static const KernelEntry tbl[4] = {entry<Rng, false, false, GRID_LDS, true>(), entry<Rng, false, false, GRID_GLOBAL, true>(),
-                                         entry<Rng, false, false, GRID_BRICKS, true>(), entry<Rng, false, false, GRID_COLUMNS, true>()};
-      kern = tbl[place];
+      key.tbl = true;
       threads = 1024;
-      ldsBytes = lds_bytes<Rng>(h, plan, true);
-      tableInLds = true;
     }
   }
+  for (const KernelEntry &e : stream_kernels<Rng>())
+    if (e.key == key) return {&e, threads, key.tbl};
+  return {nullptr, threads, key.tbl};
+}
+
+// One grid of the kernel chosen for `plan` on `stream`: the LDS check, the record of the launch (lastKernelName, i3rc_hip_last_plan),
+// occupancy and block count, then `prepare(blocks, threads)` -- what the caller puts on the stream in front of the kernel, and may
+// change A -- and the launch between the events of the timing ring.  fusedBatches: the batches of a fused launch (0: a plain one).
+template <class Rng, class Prepare>
+int launch_grid(i3rc_hip_integrator *h, const LaunchPlan &plan, RunArgs &A, hipStream_t stream, int fusedBatches, bool timeIt, Prepare &&prepare) {
+  const KernelChoice c = choose_kernel<Rng>(h, plan, A.srcKind);
+  const int threads = c.threads;
+  const size_t ldsBytes = lds_bytes<Rng>(h, plan, c.tableInLds);
   if (ldsBytes > 160 * 1024 - 256) return h->fail("the launch needs more LDS than a compute unit has");
-  if (!kern.fn) return h->fail("internal: no kernel for this problem at this place of the extinction field");
-  const void *fn = (const void *)kern.fn;
-  h->lastKernelName = kern.name;
-  record_plan(h, plan, tableInLds, ldsBytes, 0);
+  if (!c.kern) return h->fail(Rng::kBatched ? "internal: no fused kernel for this problem at this place of the extinction field"
+                                            : "internal: no kernel for this problem at this place of the extinction field");
+  const void *fn = (const void *)c.kern->fn;
+  h->lastKernelName = c.kern->name;
+  record_plan(h, plan, c.tableInLds, ldsBytes, fusedBatches);
   int perCU = h->blocksPerCU;
   if (perCU <= 0) {
     int occ = 0;
@@ -1151,65 +1208,75 @@ int launch(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, boo
     // kernels have the registers for five at most; fields within L2 gain up to 7.)
     // With the XCD-aware photon order: Landsat-119 5 ... 8 alike (6.5e8); the scene tiled 2 x 2 (31 MB): 4 workgroups 5.41e8,
     // 5 5.02e8, 6-8 4.6e8.
-    if (place == GRID_BRICKS) perCU = std::min(perCU, ncell_bytes(h) > ((size_t)16 << 20) ? 4 : 5);
+    if (plan.place == GRID_BRICKS) perCU = std::min(perCU, ncell_bytes(h) > ((size_t)16 << 20) ? 4 : 5);
   }
   if (ldsBytes > 48 * 1024)
     HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
   long long blocks = (long long)h->numCU * perCU;
-  const long long need = (A.nPhotons + threads - 1) / threads;
+  const long long photons = fusedBatches > 0 ? (long long)fusedBatches * A.nPhotons : A.nPhotons;
+  const long long need = (photons + threads - 1) / threads;
   if (blocks > need) blocks = std::max(1ll, need);
-  RunArgs B = A;   // photon indices are handed to waves in chunks (one returning atomic per chunk)
-  // XCD-aware photon order.  A field beyond an XCD's L2 (bricks) is shared by eight L2s that each see all of it: when
-  // the photons a wave traces start in "its" eighth of the domain -- workgroups are dealt round-robin over the XCDs, the
-  // kernel reads its XCC id -- an XCD's L2 has an eighth of the field (and its surroundings) to hold.  The launch's
-  // photons are sorted by start slab first (their start position is their own first Philox block): two passes over the
-  // photon numbers, about 1 % of the launch.  Radiance runs: local-estimate rays cross much of the domain, but from one
-  // tile they keep to a tube per direction -- nothing gained on the 7.8 MB Landsat field (9.49 against 9.45e7 photons/s:
-  // left in index order), +20 % on a 31 MB field (6.9 -> 8.3e7 with 7 directions).
-  // Measured ceiling (tools/locality_experiment.py): +9 ... 14 % on the 7.8 MB Landsat field, +36 % on a 62 MB field.
-  // I3RC_SLABS=0 switches it off.
-  static const bool slabsOn = !(std::getenv("I3RC_SLABS") && std::atoi(std::getenv("I3RC_SLABS")) == 0);
-  B.slabIds = nullptr; B.slabMeta = nullptr;
-  if constexpr (!Rng::kReplay) {
-    if (slabsOn && place == GRID_BRICKS && (!plan.intensity || ncell_bytes(h) > ((size_t)16 << 20)) && A.srcKind == 0 && A.nPhotons >= 1024 && A.nPhotons < ((long long)1 << 32)) {
-      auto &sb = h->slabBufs[h->stream];
-      if (sb.ids.bytes < (size_t)A.nPhotons * sizeof(uint32_t)) HIPCHK(h, sb.ids.alloc((size_t)A.nPhotons * sizeof(uint32_t)));
-      if (!sb.meta.p || sb.meta.bytes != sizeof(SlabMeta)) HIPCHK(h, sb.meta.alloc(sizeof(SlabMeta)));
-      const size_t tableBytes = sizeof(unsigned) * 8 * kSlabSortBlocks;
-      if (sb.blockCounts.bytes != tableBytes) { HIPCHK(h, sb.blockCounts.alloc(tableBytes)); HIPCHK(h, sb.blockBase.alloc(tableBytes)); }
-      const long long span = ((A.nPhotons + kSlabSortBlocks - 1) / kSlabSortBlocks + 255) / 256 * 256;   // photons per workgroup of the sort
-      int tx = 1, ty = 8;   // the squarest of the four tilings (ties: more cuts in y, whose rows are further apart in memory)
-      for (int cx = 2; cx <= 8; cx *= 2)
-        if ((double)h->nx / cx + (double)h->ny / (8 / cx) < (double)h->nx / tx + (double)h->ny / ty) { tx = cx; ty = 8 / cx; }
-      hipLaunchKernelGGL(slab_count_kernel, dim3(kSlabSortBlocks), dim3(256), 0, h->stream, A.seed0, A.seed1, A.firstPhoton, A.nPhotons, span,
-                         tx, ty, (unsigned *)sb.blockCounts.p);
-      hipLaunchKernelGGL(slab_scan_kernel, dim3(1), dim3(8), 0, h->stream, (int)kSlabSortBlocks, (const unsigned *)sb.blockCounts.p,
-                         (SlabMeta *)sb.meta.p, (unsigned *)sb.blockBase.p);
-      hipLaunchKernelGGL(slab_fill_kernel, dim3(kSlabSortBlocks), dim3(256), 0, h->stream, A.seed0, A.seed1, A.firstPhoton, A.nPhotons, span,
-                         tx, ty, (const unsigned *)sb.blockBase.p, (uint32_t *)sb.ids.p);
-      HIPCHK(h, hipGetLastError());
-      B.slabIds = (const uint32_t *)sb.ids.p; B.slabMeta = (SlabMeta *)sb.meta.p;
-    }
-  }
-  // at most 256 photons per visit of the work counter: four photon generations of a wave.  Measured (I3RC_CHUNK_MAX, a
-  // tuning knob): 128 loses a third (a returning atomic every other generation), 256...448 are equal, 1024 loses
-  // 0.5 % on the step cloud and 2-5 % on the radar / Landsat cases to the imbalance at the end of a launch.
-  static const long long chunkMax = std::getenv("I3RC_CHUNK_MAX") ? std::max(64ll, std::atoll(std::getenv("I3RC_CHUNK_MAX"))) : 256;
-  B.chunk = (int)std::min<long long>(chunkMax, std::max<long long>(64, A.nPhotons / (blocks * (threads / 64) * 8)));
-  HIPCHK(h, hipMemsetAsync(A.workCounter, 0, sizeof(unsigned long long), h->stream));
+  if (prepare(blocks, threads)) return 1;
   const int slot = (int)(h->timedLaunches % i3rc_hip_integrator::kEventRing);
-  if (timeIt) HIPCHK(h, hipEventRecord(h->evStart[slot], h->stream));
+  if (timeIt) HIPCHK(h, hipEventRecord(h->evStart[slot], stream));
   {
     // thresholds the caller did not fix are adapted per wave (photon_kernel); negative = adaptive, starting value
     const int evThreshold = h->evThreshold > 0 ? h->evThreshold : -40;
     const int lightThreshold = h->lightThreshold > 0 ? h->lightThreshold : -24;
-    hipLaunchKernelGGL(kern.fn, dim3((unsigned)blocks), dim3(threads), ldsBytes, h->stream, plan.P, B, evThreshold, lightThreshold);
+    hipLaunchKernelGGL(c.kern->fn, dim3((unsigned)blocks), dim3(threads), ldsBytes, stream, plan.P, A, evThreshold, lightThreshold);
   }
   HIPCHK(h, hipGetLastError());
-  if (timeIt) { HIPCHK(h, hipEventRecord(h->evStop[slot], h->stream)); h->timedLaunches++; }
-  return absorbed_columns(h, h->stream, plan.P.tally, 1, 0);
+  if (timeIt) { HIPCHK(h, hipEventRecord(h->evStop[slot], stream)); h->timedLaunches++; }
+  return 0;
 }
 
+template <class Rng>
+int launch(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
+  RunArgs B = A;   // photon indices are handed to waves in chunks (one returning atomic per chunk)
+  const int rc = launch_grid<Rng>(h, plan, B, stream, 0, timeIt, [&](long long blocks, int threads) -> int {
+    // XCD-aware photon order.  A field beyond an XCD's L2 (bricks) is shared by eight L2s that each see all of it: when
+    // the photons a wave traces start in "its" eighth of the domain -- workgroups are dealt round-robin over the XCDs, the
+    // kernel reads its XCC id -- an XCD's L2 has an eighth of the field (and its surroundings) to hold.  The launch's
+    // photons are sorted by start slab first (their start position is their own first Philox block): two passes over the
+    // photon numbers, about 1 % of the launch.  Radiance runs: local-estimate rays cross much of the domain, but from one
+    // tile they keep to a tube per direction -- nothing gained on the 7.8 MB Landsat field (9.49 against 9.45e7 photons/s:
+    // left in index order), +20 % on a 31 MB field (6.9 -> 8.3e7 with 7 directions).
+    // Measured ceiling (tools/locality_experiment.py): +9 ... 14 % on the 7.8 MB Landsat field, +36 % on a 62 MB field.
+    // I3RC_SLABS=0 switches it off.
+    static const bool slabsOn = env_on("I3RC_SLABS");
+    B.slabIds = nullptr; B.slabMeta = nullptr;
+    if constexpr (!Rng::kReplay) {
+      if (slabsOn && plan.place == GRID_BRICKS && (!plan.intensity || ncell_bytes(h) > ((size_t)16 << 20)) && A.srcKind == 0 && A.nPhotons >= 1024 && A.nPhotons < ((long long)1 << 32)) {
+        auto &sb = h->slabBufs[stream];
+        if (sb.ids.bytes < (size_t)A.nPhotons * sizeof(uint32_t)) HIPCHK(h, sb.ids.alloc((size_t)A.nPhotons * sizeof(uint32_t)));
+        if (!sb.meta.p || sb.meta.bytes != sizeof(SlabMeta)) HIPCHK(h, sb.meta.alloc(sizeof(SlabMeta)));
+        const size_t tableBytes = sizeof(unsigned) * 8 * kSlabSortBlocks;
+        if (sb.blockCounts.bytes != tableBytes) { HIPCHK(h, sb.blockCounts.alloc(tableBytes)); HIPCHK(h, sb.blockBase.alloc(tableBytes)); }
+        const long long span = ((A.nPhotons + kSlabSortBlocks - 1) / kSlabSortBlocks + 255) / 256 * 256;   // photons per workgroup of the sort
+        int tx = 1, ty = 8;   // the squarest of the four tilings (ties: more cuts in y, whose rows are further apart in memory)
+        for (int cx = 2; cx <= 8; cx *= 2)
+          if ((double)h->nx / cx + (double)h->ny / (8 / cx) < (double)h->nx / tx + (double)h->ny / ty) { tx = cx; ty = 8 / cx; }
+        hipLaunchKernelGGL(slab_count_kernel, dim3(kSlabSortBlocks), dim3(256), 0, stream, A.seed0, A.seed1, A.firstPhoton, A.nPhotons, span,
+                           tx, ty, (unsigned *)sb.blockCounts.p);
+        hipLaunchKernelGGL(slab_scan_kernel, dim3(1), dim3(8), 0, stream, (int)kSlabSortBlocks, (const unsigned *)sb.blockCounts.p,
+                           (SlabMeta *)sb.meta.p, (unsigned *)sb.blockBase.p);
+        hipLaunchKernelGGL(slab_fill_kernel, dim3(kSlabSortBlocks), dim3(256), 0, stream, A.seed0, A.seed1, A.firstPhoton, A.nPhotons, span,
+                           tx, ty, (const unsigned *)sb.blockBase.p, (uint32_t *)sb.ids.p);
+        HIPCHK(h, hipGetLastError());
+        B.slabIds = (const uint32_t *)sb.ids.p; B.slabMeta = (SlabMeta *)sb.meta.p;
+      }
+    }
+    // at most 256 photons per visit of the work counter: four photon generations of a wave.  Measured (I3RC_CHUNK_MAX, a
+    // tuning knob): 128 loses a third (a returning atomic every other generation), 256...448 are equal, 1024 loses
+    // 0.5 % on the step cloud and 2-5 % on the radar / Landsat cases to the imbalance at the end of a launch.
+    static const long long chunkMax = std::max(64ll, env_int("I3RC_CHUNK_MAX", 256));
+    B.chunk = (int)std::min<long long>(chunkMax, std::max<long long>(64, A.nPhotons / (blocks * (threads / 64) * 8)));
+    HIPCHK(h, hipMemsetAsync(A.workCounter, 0, sizeof(unsigned long long), stream));
+    return 0;
+  });
+  if (rc) return 1;
+  return absorbed_columns(h, stream, plan.P.tally, 1, 0);
+}
 
 // ---- fused multi-batch launches ---------------------------------------------------------------------------------------
 // out[b][e] = sum over the replicas r of blocks[b * R + r][e]
@@ -1339,18 +1406,20 @@ __global__ void __launch_bounds__(256) moments_means_kernel(MomentsDev M, const 
   if (q == 0 && threadIdx.x < I3RC_NUM_COUNTERS) unsafeAtomicAdd(counterTotals + threadIdx.x, raw[M.oCnt + threadIdx.x]);
 }
 
-// Can the batches of a driver's loop share one grid?  The specialised kernels -- the common problem class, production streams --,
-// with or (round 4) without radiance directions: a local-estimate ray carries its batch in its info word (photon_kernel).
-bool fusable(const i3rc_hip_integrator *h, int64_t nPhotons) {
-  static const bool envOff = std::getenv("I3RC_FUSED") && std::atoi(std::getenv("I3RC_FUSED")) == 0;
+// Do the batches of a driver's loop -- nBatches of nPhotons each -- share one grid, group by group (see FusedSlot)?  The specialised
+// kernels -- the common problem class, production streams --, with or (round 4) without radiance directions: a local-estimate ray
+// carries its batch in its info word (photon_kernel).  One long batch alone, or batches of a size at which a launch's tail no longer
+// matters, go one launch each.
+bool fuse_loop(const i3rc_hip_integrator *h, int64_t nPhotons, int nBatches) {
+  static const bool envOff = !env_on("I3RC_FUSED");
   if (envOff || h->fusion == 0) return false;
   // (a batch's tally block beyond 256 MiB -- 3e7 cells -- would make a slot's pinned copy and its blocks unreasonably large: such
   // domains keep one launch per batch, whose tail is a small part of a launch that long anyway)
-  static const bool radianceOff = std::getenv("I3RC_FUSED_RADIANCE") && std::atoi(std::getenv("I3RC_FUSED_RADIANCE")) == 0;
+  static const bool radianceOff = !env_on("I3RC_FUSED_RADIANCE");
   if (h->nDir > 0 && (radianceOff || kNestedBuild)) return false;
   // (round 5: the widened class too -- several components, an irregular x / y grid, a gridded surface: photon_kernel<PhiloxBatchStream, ..., MULTI>)
   return (common_class(h, 0) || multi_class(h, 0)) && h->kernelVariant != I3RC_KERNEL_GENERAL && nPhotons < ((int64_t)1 << 31) &&
-         h->layout.total * (int64_t)sizeof(double) <= ((int64_t)256 << 20);
+         h->layout.total * (int64_t)sizeof(double) <= ((int64_t)256 << 20) && (h->fusion == 1 || (nBatches >= 2 && nPhotons <= 20000000));
 }
 
 // Replicas of a batch's tally block: enough that the hot words of a small domain (fluxUp / fluxDown of nx * ny columns) are
@@ -1368,7 +1437,7 @@ int fused_group_size(const i3rc_hip_integrator *h, int nBatches, int64_t nPhoton
   const int64_t blockBytes = h->layout.total * 8, R = fused_replicas(h);
   int64_t g = ((int64_t)1 << 30) / (blockBytes * R);
   if (!moments) g = std::min<int64_t>(g, ((int64_t)256 << 20) / blockBytes);   // (moments mode: no pinned copy of the blocks)
-  static const int64_t target = std::getenv("I3RC_FUSED_GROUP_PHOTONS") ? std::atoll(std::getenv("I3RC_FUSED_GROUP_PHOTONS")) : 250000000ll;
+  static const int64_t target = env_int("I3RC_FUSED_GROUP_PHOTONS", 250000000ll);
   g = std::min<int64_t>(g, (target + nPhotons - 1) / nPhotons);
   if (h->nDir > 0) g = std::min<int64_t>(g, 8192);   // (a local-estimate ray carries its batch in 13 bits of its info word: photon_kernel, make_ray)
   return (int)std::max<int64_t>(1, std::min<int64_t>(g, nBatches));
@@ -1384,14 +1453,8 @@ int ready_fused_slot(i3rc_hip_integrator *h, i3rc_hip_integrator::FusedSlot &g, 
   // launches overlapping by 2 ms only -- the next kernel gets its first workgroup slots when the one before drains -- while
   // every launch took 5 ms longer than it does alone: with work pending in a second hardware queue the persistent kernel's
   // waves are time-sliced against it.  One queue exposes a launch's 1.4 ms tail per group and nothing else.
-  static const bool ownStreams = std::getenv("I3RC_FUSED_STREAMS") && std::atoi(std::getenv("I3RC_FUSED_STREAMS")) != 0;
-  if (!g.stream) {
-    if (ownStreams || &g == &h->fused[0]) HIPCHK(h, hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-    else {
-      if (!h->fused[0].stream) HIPCHK(h, hipStreamCreateWithFlags(&h->fused[0].stream, hipStreamNonBlocking));
-      g.stream = h->fused[0].stream;
-    }
-  }
+  if (!h->fused[0].stream) HIPCHK(h, hipStreamCreateWithFlags(&h->fused[0].stream, hipStreamNonBlocking));
+  g.stream = h->fused[0].stream;
   if (!g.done) HIPCHK(h, hipEventCreateWithFlags(&g.done, hipEventDisableTiming));
   if (!g.traced) HIPCHK(h, hipEventCreateWithFlags(&g.traced, hipEventDisableTiming));
   if (!h->fusedCopyStream) HIPCHK(h, hipStreamCreateWithFlags(&h->fusedCopyStream, hipStreamNonBlocking));
@@ -1418,21 +1481,16 @@ int launch_fused_group(i3rc_hip_integrator *h, i3rc_hip_integrator::FusedSlot &g
                        int64_t nPhotons, const i3rc_source *src, bool timeIt, int reserve = 0, bool moments = false) {
   const int R = fused_replicas(h);
   if (ready_fused_slot(h, g, count, R, reserve, !moments)) return 1;
-  hipStream_t const callerStream = h->stream;
-  double *const callerTally = h->tally;
-  h->stream = g.stream; h->tally = (double *)g.blocks.p;   // (make_problem reads these two)
   LaunchPlan plan;
   RunArgs A;
   std::memset(&A, 0, sizeof(A));
   A.seed0 = seed0; A.seed1 = seed1; A.firstPhoton = 0; A.nPhotons = nPhotons;
   A.workCounter = (unsigned long long *)g.counter.p;
-  int rc = make_problem(h, plan, true) || upload_source(h, src, nPhotons, A);
-  h->stream = callerStream; h->tally = callerTally;
-  if (rc) return 1;
+  if (make_problem(h, plan, g.stream, (double *)g.blocks.p, true) || upload_source(h, src, nPhotons, A)) return 1;
   // (chunks: a wave takes this many photons of ONE batch per visit of the work counter; a lane hands its counts over when
   // its batch changes, so longer chunks mean fewer atomics, shorter ones a shorter end of the launch)
-  static const int chunkEnv = std::getenv("I3RC_FUSED_CHUNK") ? std::max(64, std::atoi(std::getenv("I3RC_FUSED_CHUNK"))) : 0;
-  A.chunk = chunkEnv > 0 ? chunkEnv : 512;
+  static const int chunk = (int)std::max(64ll, env_int("I3RC_FUSED_CHUNK", 512));
+  A.chunk = chunk;
   if ((int64_t)A.chunk > nPhotons) A.chunk = (int)std::max<int64_t>(64, nPhotons);
   A.nBatches = (unsigned)count;
   A.chunksPerBatch = (unsigned)((nPhotons + A.chunk - 1) / A.chunk);
@@ -1441,72 +1499,15 @@ int launch_fused_group(i3rc_hip_integrator *h, i3rc_hip_integrator::FusedSlot &g
   A.abortFlag = g.abortFlag;
   A.counterBlocks = (double *)g.counterBlocks.p;
   if ((uint64_t)count * R >= ((uint64_t)1 << 31)) return h->fail("fused launch: too many tally blocks");
-  static const KernelEntry kernels[5] = {entry<PhiloxBatchStream, false, false, GRID_LDS>(), entry<PhiloxBatchStream, false, false, GRID_GLOBAL>(),
-                                         entry<PhiloxBatchStream, false, false, GRID_BRICKS>(), entry<PhiloxBatchStream, false, false, GRID_COLUMNS>(), KernelEntry{}};
-  const int place = plan.place;
-  // the widened class (several components, irregular x / y, a gridded surface): its own fused kernels, flux ones too -- a driver's loop
-  // of 1e6-photon batches on Landsat-36 + gas then costs 1.1 ms per batch instead of 2.6 (profiles/r05_fused_wide.txt)
-  const bool wide = !common_class(h, 0);
-  static const KernelEntry wideKernels[3][5] = {
-      {entry<PhiloxBatchStream, false, false, GRID_LDS, false, false, true>(), entry<PhiloxBatchStream, false, false, GRID_GLOBAL, false, false, true>(), entry<PhiloxBatchStream, false, false, GRID_BRICKS, false, false, true>(), entry<PhiloxBatchStream, false, false, GRID_COLUMNS, false, false, true>(), entry<PhiloxBatchStream, false, false, GRID_COLBASE, false, false, true>()},
-      {entry<PhiloxBatchStream, true, false, GRID_LDS, false, false, true>(), entry<PhiloxBatchStream, true, false, GRID_GLOBAL, false, false, true>(), entry<PhiloxBatchStream, true, false, GRID_BRICKS, false, false, true>(), entry<PhiloxBatchStream, true, false, GRID_COLUMNS, false, false, true>(), entry<PhiloxBatchStream, true, false, GRID_COLBASE, false, false, true>()},
-      {entry<PhiloxBatchStream, true, false, GRID_LDS, false, true, true>(), entry<PhiloxBatchStream, true, false, GRID_GLOBAL, false, true, true>(), entry<PhiloxBatchStream, true, false, GRID_BRICKS, false, true, true>(), entry<PhiloxBatchStream, true, false, GRID_COLUMNS, false, true, true>(), entry<PhiloxBatchStream, true, false, GRID_COLBASE, false, true, true>()}};
-  // (the inverse table's cosines in LDS, workgroups of 1024 threads: as in launch(); these instantiations are planned for eight
-  // waves per SIMD -- two workgroups per compute unit -- and pay for it with two vector registers in scratch)
-  KernelEntry kern = kernels[place];
-  int threads = 256;
-  size_t ldsBytes = lds_bytes<PhiloxBatchStream>(h, plan, false);
-  if (wide) kern = wideKernels[plan.intensity ? (direct_rays(h) ? 2 : 1) : 0][place];
-  else
-  if (plan.intensity) {   // radiance problems: through the event ring, or (one direction) without it -- as in launch()
-    static const KernelEntry ring[4] = {entry<PhiloxBatchStream, true, false, GRID_LDS>(), entry<PhiloxBatchStream, true, false, GRID_GLOBAL>(),
-                                        entry<PhiloxBatchStream, true, false, GRID_BRICKS>(), entry<PhiloxBatchStream, true, false, GRID_COLUMNS>()};
-    static const KernelEntry direct[4] = {entry<PhiloxBatchStream, true, false, GRID_LDS, false, true>(), entry<PhiloxBatchStream, true, false, GRID_GLOBAL, false, true>(),
-                                          entry<PhiloxBatchStream, true, false, GRID_BRICKS, false, true>(), entry<PhiloxBatchStream, true, false, GRID_COLUMNS, false, true>()};
-    kern = direct_rays(h) ? direct[place] : ring[place];
-  } else {
-    static const bool tblOn = !(std::getenv("I3RC_TABLE_LDS") && std::atoi(std::getenv("I3RC_TABLE_LDS")) == 0);
-    static const int tblPlaces = std::getenv("I3RC_FUSED_TABLE_LDS_PLACES") ? std::atoi(std::getenv("I3RC_FUSED_TABLE_LDS_PLACES")) : 11;   // (measured: Landsat-36 +13 %, radar 640 +12 %, step cloud +1.5 ... 3 % in the kernels' own time; on column records +1 ... 2.5 %)
-    if (!wide && tblOn && ((tblPlaces >> place) & 1) && place != GRID_BRICKS && (plan.P.uniformPf >= 1 || h->nInvEntries[0] == 1) &&
-        plan.ldsBytes + sizeof(float) * (size_t)plan.P.comp0.nInv <= 79 * 1024) {
-      static const KernelEntry tbl[4] = {entry<PhiloxBatchStream, false, false, GRID_LDS, true>(), entry<PhiloxBatchStream, false, false, GRID_GLOBAL, true>(),
-                                         KernelEntry{}, entry<PhiloxBatchStream, false, false, GRID_COLUMNS, true>()};
-      kern = tbl[place];
-      threads = 1024;
-      ldsBytes = lds_bytes<PhiloxBatchStream>(h, plan, true);
-    }
-  }
-  if (ldsBytes > 160 * 1024 - 256) return h->fail("the launch needs more LDS than a compute unit has");
-  if (!kern.fn) return h->fail("internal: no fused kernel for this problem at this place of the extinction field");
-  const void *fn = (const void *)kern.fn;
-  h->lastKernelName = kern.name;
-  record_plan(h, plan, threads == 1024, ldsBytes, count);
-  int perCU = h->blocksPerCU;
-  if (perCU <= 0) {
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, threads, ldsBytes) != hipSuccess || occ < 1) occ = 2;
-    perCU = std::min(occ, 8);
-    if (place == GRID_BRICKS) perCU = std::min(perCU, ncell_bytes(h) > ((size_t)16 << 20) ? 4 : 5);   // (as in launch())
-  }
-  if (ldsBytes > 48 * 1024)
-    HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
-  long long blocks = (long long)h->numCU * perCU;
-  const long long need = ((long long)count * nPhotons + threads - 1) / threads;
-  if (blocks > need) blocks = std::max(1ll, need);
   const size_t outBytes = (size_t)count * h->layout.total * sizeof(double);
-  *g.abortFlag = 0;
-  HIPCHK(h, hipMemsetAsync(g.blocks.p, 0, outBytes * R, g.stream));
-  HIPCHK(h, hipMemsetAsync(g.counter.p, 0, sizeof(unsigned long long), g.stream));
-  HIPCHK(h, hipMemsetAsync(g.counterBlocks.p, 0, (size_t)count * kCounterReplicas * I3RC_NUM_COUNTERS * sizeof(double), g.stream));
-  const int slot = (int)(h->timedLaunches % i3rc_hip_integrator::kEventRing);
-  if (timeIt) HIPCHK(h, hipEventRecord(h->evStart[slot], g.stream));
-  {
-    const int evThreshold = h->evThreshold > 0 ? h->evThreshold : -40;
-    const int lightThreshold = h->lightThreshold > 0 ? h->lightThreshold : -24;
-    hipLaunchKernelGGL(kern.fn, dim3((unsigned)blocks), dim3(threads), ldsBytes, g.stream, plan.P, A, evThreshold, lightThreshold);
-  }
-  HIPCHK(h, hipGetLastError());
-  if (timeIt) { HIPCHK(h, hipEventRecord(h->evStop[slot], g.stream)); h->timedLaunches++; }
+  const int rc = launch_grid<PhiloxBatchStream>(h, plan, A, g.stream, count, timeIt, [&](long long, int) -> int {
+    *g.abortFlag = 0;
+    HIPCHK(h, hipMemsetAsync(g.blocks.p, 0, outBytes * R, g.stream));
+    HIPCHK(h, hipMemsetAsync(g.counter.p, 0, sizeof(unsigned long long), g.stream));
+    HIPCHK(h, hipMemsetAsync(g.counterBlocks.p, 0, (size_t)count * kCounterReplicas * I3RC_NUM_COUNTERS * sizeof(double), g.stream));
+    return 0;
+  });
+  if (rc) return 1;
   const double *result = (const double *)g.blocks.p;
   if (R > 1) {
     const long long n = (long long)count * h->layout.total;
@@ -1526,12 +1527,10 @@ int launch_fused_group(i3rc_hip_integrator *h, i3rc_hip_integrator::FusedSlot &g
     if (accumulate_moments(h, g.stream, result, count, g.excess)) return 1;
     HIPCHK(h, hipEventRecord(g.done, g.stream));
   } else {
-    static const bool copyInLine = std::getenv("I3RC_FUSED_COPY_INLINE") && std::atoi(std::getenv("I3RC_FUSED_COPY_INLINE")) != 0;   // (measurement knob: the copy on the groups' own stream, as before round 4)
-    hipStream_t const cs = copyInLine ? g.stream : h->fusedCopyStream;
     HIPCHK(h, hipEventRecord(g.traced, g.stream));
-    if (!copyInLine) HIPCHK(h, hipStreamWaitEvent(cs, g.traced, 0));
-    HIPCHK(h, hipMemcpyAsync(g.pinned, result, outBytes, hipMemcpyDeviceToHost, cs));
-    HIPCHK(h, hipEventRecord(g.done, cs));
+    HIPCHK(h, hipStreamWaitEvent(h->fusedCopyStream, g.traced, 0));
+    HIPCHK(h, hipMemcpyAsync(g.pinned, result, outBytes, hipMemcpyDeviceToHost, h->fusedCopyStream));
+    HIPCHK(h, hipEventRecord(g.done, h->fusedCopyStream));
   }
   g.count = count; g.seed1 = seed1; g.next = 0;
   if (tracing()) std::fprintf(stderr, "[i3rc %9.3f ms] fused group launched: seed words %u .. %u (%d batches of %lld photons, %d replicas, chunk %d)\n", trace_ms(),
@@ -1679,6 +1678,41 @@ void top_up_groups(i3rc_hip_integrator *h, uint32_t seed0, uint32_t nextIfNone, 
   }
 }
 
+// Workgroups keep their partial flux / radiance sums in float32 (LDS): a workgroup must not see so many photons
+// that a column's sum could leave the range where float32 still counts (2^24).  Per-photon random streams make a
+// long batch the same as several launches over consecutive photon ranges, so very long Directional batches are cut
+// into launches of at most 2^22 photons per compute unit (about 1e9 photons on an MI355X).
+int launch_batch_parts(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
+  const int64_t perLaunch = h->launchLimit > 0 ? h->launchLimit : (int64_t)h->numCU << 22;
+  if (A.srcKind != 0) return launch<PhiloxStream>(h, plan, A, stream, timeIt);
+  for (int64_t done = 0; done < A.nPhotons; done += perLaunch) {
+    RunArgs part = A;
+    part.firstPhoton = A.firstPhoton + done;
+    part.nPhotons = std::min<int64_t>(perLaunch, A.nPhotons - done);
+    if (launch<PhiloxStream>(h, plan, part, stream, timeIt)) return 1;
+  }
+  return 0;
+}
+
+// One Directional batch into pipeline slot `sl`: zeroed, traced and (copyBack) copied to the slot's pinned buffer, all asynchronous on
+// the slot's stream.  `who` names the caller in the error texts.
+int run_batch_in_slot(i3rc_hip_integrator *h, i3rc_hip_integrator::PipeSlot &sl, uint32_t seed0, uint32_t seed1, int64_t nPhotons,
+                      const i3rc_source *src, bool timeIt, bool copyBack, const char *who) {
+  LaunchPlan plan;
+  RunArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.seed0 = seed0; A.seed1 = seed1; A.firstPhoton = 0; A.nPhotons = nPhotons;
+  A.workCounter = (unsigned long long *)sl.counter.p;
+  if (make_problem(h, plan, sl.stream, (double *)sl.tally.p) || upload_source(h, src, nPhotons, A)) return 1;
+  const size_t bytes = (size_t)h->layout.total * sizeof(double);
+  if (hipMemsetAsync(sl.tally.p, 0, bytes, sl.stream) != hipSuccess) return h->fail(std::string(who) + ": clearing a tally buffer failed");
+  if (launch_batch_parts(h, plan, A, sl.stream, timeIt)) return 1;
+  if (copyBack && (hipMemcpyAsync(sl.pinned, sl.tally.p, bytes, hipMemcpyDeviceToHost, sl.stream) != hipSuccess ||
+                   hipEventRecord(sl.done, sl.stream) != hipSuccess))
+    return h->fail(std::string(who) + ": copying a batch's tallies back failed");
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1690,25 +1724,13 @@ int i3rc_hip_launch_batch(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");  // illumination :78-79
   HIPCHK(h, hipSetDevice(h->device));
   LaunchPlan plan;
-  if (make_problem(h, plan)) return 1;
+  if (make_problem(h, plan, h->stream, h->tally)) return 1;
   RunArgs A;
   std::memset(&A, 0, sizeof(A));
   A.seed0 = seed0; A.seed1 = seed1; A.firstPhoton = firstPhoton; A.nPhotons = nPhotons;
   A.workCounter = (unsigned long long *)h->workCounter.p;
   if (upload_source(h, src, nPhotons, A)) return 1;
-  // Workgroups keep their partial flux / radiance sums in float32 (LDS): a workgroup must not see so many photons
-  // that a column's sum could leave the range where float32 still counts (2^24).  Per-photon random streams make a
-  // long batch the same as several launches over consecutive photon ranges, so very long Directional batches are cut
-  // into launches of at most 2^22 photons per compute unit (about 1e9 photons on an MI355X).
-  const int64_t perLaunch = h->launchLimit > 0 ? h->launchLimit : (int64_t)h->numCU << 22;
-  if (src->kind != 0 || nPhotons <= perLaunch) return launch<PhiloxStream>(h, plan, A, true);
-  for (int64_t done = 0; done < nPhotons; done += perLaunch) {
-    RunArgs part = A;
-    part.firstPhoton = firstPhoton + done;
-    part.nPhotons = std::min(perLaunch, nPhotons - done);
-    if (launch<PhiloxStream>(h, plan, part, true)) return 1;
-  }
-  return 0;
+  return launch_batch_parts(h, plan, A, h->stream, true);
 }
 
 // The batch loop of a driver (Example-Drivers/monteCarloDriver.f95:283-326) as one call: see include/i3rc_hip.h
@@ -1719,10 +1741,7 @@ int i3rc_hip_run_batches(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1,
   if (src->kind != 0) return h->fail("i3rc_hip_run_batches: Directional photon streams only (explicit streams differ from batch to batch)");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
   HIPCHK(h, hipSetDevice(h->device));
-  // batches that the specialised flux kernels run share one grid, group by group (see FusedSlot); one long batch alone, or
-  // batches of a size at which a launch's tail no longer matters, go one launch each as before
-  if (fusable(h, nPhotons) && (h->fusion == 1 || (nBatches >= 2 && nPhotons <= 20000000)))
-    return run_batches_fused(h, seed0, seed1, nBatches, nPhotons, src, hostTallies);
+  if (fuse_loop(h, nPhotons, nBatches)) return run_batches_fused(h, seed0, seed1, nBatches, nPhotons, src, hostTallies);
   const int K = std::min(nBatches, inFlight <= 0 ? 6 : std::min(inFlight, (int)i3rc_hip_integrator::kMaxInFlight));
   const size_t bytes = (size_t)h->layout.total * sizeof(double);
   drop_lookahead(h);               // (i3rc_hip_compute_batch shares the slots)
@@ -1732,8 +1751,6 @@ int i3rc_hip_run_batches(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1,
     h->pipe[k].batch = -1;
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));   // whatever the caller had in flight on the handle's stream comes first
-  hipStream_t const callerStream = h->stream;
-  double *const callerTally = h->tally;
   int rc = 0;
   auto collect = [&](i3rc_hip_integrator::PipeSlot &sl) -> int {
     if (sl.batch < 0) return 0;
@@ -1742,35 +1759,15 @@ int i3rc_hip_run_batches(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1,
     sl.batch = -1;
     return 0;
   };
-  const int64_t perLaunch = h->launchLimit > 0 ? h->launchLimit : (int64_t)h->numCU << 22;
   for (int b = 0; b < nBatches && !rc; ++b) {
     auto &sl = h->pipe[b % K];
-    if ((rc = collect(sl))) break;
-    h->stream = sl.stream; h->tally = (double *)sl.tally.p;   // (make_problem and launch read these two)
-    LaunchPlan plan;
-    if ((rc = make_problem(h, plan))) break;
-    RunArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.seed0 = seed0; A.seed1 = seed1 + (uint32_t)b; A.firstPhoton = 0; A.nPhotons = nPhotons;
-    A.workCounter = (unsigned long long *)sl.counter.p;
-    if ((rc = upload_source(h, src, nPhotons, A))) break;
-    if (hipMemsetAsync(sl.tally.p, 0, bytes, sl.stream) != hipSuccess) { rc = h->fail("i3rc_hip_run_batches: clearing a tally buffer failed"); break; }
-    for (int64_t done = 0; done < nPhotons && !rc; done += perLaunch) {   // (very long batches: see i3rc_hip_launch_batch)
-      RunArgs part = A;
-      part.firstPhoton = done;
-      part.nPhotons = std::min(perLaunch, nPhotons - done);
-      rc = launch<PhiloxStream>(h, plan, part, true);
-    }
-    if (rc) break;
-    if (hipMemcpyAsync(sl.pinned, sl.tally.p, bytes, hipMemcpyDeviceToHost, sl.stream) != hipSuccess ||
-        hipEventRecord(sl.done, sl.stream) != hipSuccess) { rc = h->fail("i3rc_hip_run_batches: copying a batch's tallies back failed"); break; }
+    if ((rc = collect(sl)) || (rc = run_batch_in_slot(h, sl, seed0, seed1 + (uint32_t)b, nPhotons, src, true, true, "i3rc_hip_run_batches"))) break;
     sl.batch = b;
   }
   for (int k = 0; k < K; ++k) {   // drain (also after a failure: nothing of this call stays in flight)
     if (rc) { (void)hipStreamSynchronize(h->pipe[k].stream); h->pipe[k].batch = -1; }
     else rc = collect(h->pipe[k]);
   }
-  h->stream = callerStream; h->tally = callerTally;
   return rc;
 }
 
@@ -1792,7 +1789,7 @@ int i3rc_hip_run_batches_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (begin_moments(h)) return 1;
   int rc = 0;
-  if (fusable(h, nPhotons) && (h->fusion == 1 || (nBatches >= 2 && nPhotons <= 20000000)))
+  if (fuse_loop(h, nPhotons, nBatches))
     rc = run_batches_fused(h, seed0, seed1, nBatches, nPhotons, src, nullptr);
   else {
     // other problems (the general kernels; long batches): one launch per batch, several in flight as in i3rc_hip_run_batches, each
@@ -1800,30 +1797,12 @@ int i3rc_hip_run_batches_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_
     const int K = std::min(nBatches, 6);
     if (reset_slots_if_layout_changed(h)) return 1;
     for (int k = 0; k < K; ++k) { if (ready_slot(h, k)) return 1; h->pipe[k].batch = -1; }
-    hipStream_t const callerStream = h->stream;
-    double *const callerTally = h->tally;
-    const size_t bytes = (size_t)h->layout.total * sizeof(double);
-    const int64_t perLaunch = h->launchLimit > 0 ? h->launchLimit : (int64_t)h->numCU << 22;
     for (int b = 0; b < nBatches && !rc; ++b) {
       auto &sl = h->pipe[b % K];
-      h->stream = sl.stream; h->tally = (double *)sl.tally.p;
-      LaunchPlan plan;
-      RunArgs A;
-      std::memset(&A, 0, sizeof(A));
-      A.seed0 = seed0; A.seed1 = seed1 + (uint32_t)b; A.firstPhoton = 0; A.nPhotons = nPhotons;
-      A.workCounter = (unsigned long long *)sl.counter.p;
-      rc = make_problem(h, plan) || upload_source(h, src, nPhotons, A);
-      if (!rc && hipMemsetAsync(sl.tally.p, 0, bytes, sl.stream) != hipSuccess) rc = h->fail("i3rc_hip_run_batches_moments: clearing a tally buffer failed");
-      for (int64_t done = 0; done < nPhotons && !rc; done += perLaunch) {
-        RunArgs part = A;
-        part.firstPhoton = done;
-        part.nPhotons = std::min(perLaunch, nPhotons - done);
-        rc = launch<PhiloxStream>(h, plan, part, true);
-      }
-      if (!rc) rc = accumulate_moments(h, sl.stream, (const double *)sl.tally.p, 1, sl.excess);
+      rc = run_batch_in_slot(h, sl, seed0, seed1 + (uint32_t)b, nPhotons, src, true, false, "i3rc_hip_run_batches_moments") ||
+           accumulate_moments(h, sl.stream, (const double *)sl.tally.p, 1, sl.excess);
     }
     for (int k = 0; k < K; ++k) if (h->pipe[k].stream && hipStreamSynchronize(h->pipe[k].stream) != hipSuccess && !rc) rc = h->fail("i3rc_hip_run_batches_moments: waiting for the batches failed");
-    h->stream = callerStream; h->tally = callerTally;
   }
   if (rc) return 1;
   i3rc_moments_layout L;
@@ -1849,42 +1828,18 @@ int i3rc_hip_compute_batch(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed
     for (int k = 0; k < i3rc_hip_integrator::kMaxInFlight; ++k) if (h->pipe[k].batch < 0) return k;
     return -1;
   };
-  hipStream_t const callerStream = h->stream;
-  double *const callerTally = h->tally;
-  auto start = [&](int k, uint32_t s1, bool timed) -> int {   // zero, trace, copy back: asynchronous on the slot's stream (batches launched
-                                                               // ahead of the caller are not recorded in the ring of timed launches)
-    if (ready_slot(h, k)) return 1;
-    auto &sl = h->pipe[k];
-    h->stream = sl.stream; h->tally = (double *)sl.tally.p;
-    int rc = 0;
-    LaunchPlan plan;
-    RunArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.seed0 = seed0; A.seed1 = s1; A.firstPhoton = 0; A.nPhotons = nPhotons;
-    A.workCounter = (unsigned long long *)sl.counter.p;
-    rc = make_problem(h, plan) || upload_source(h, src, nPhotons, A);
-    if (!rc && hipMemsetAsync(sl.tally.p, 0, bytes, sl.stream) != hipSuccess) rc = h->fail("i3rc_hip_compute_batch: clearing a tally buffer failed");
-    const int64_t perLaunch = h->launchLimit > 0 ? h->launchLimit : (int64_t)h->numCU << 22;
-    for (int64_t done = 0; done < nPhotons && !rc; done += perLaunch) {
-      RunArgs part = A;
-      part.firstPhoton = done;
-      part.nPhotons = std::min(perLaunch, nPhotons - done);
-      rc = launch<PhiloxStream>(h, plan, part, timed);
-    }
-    if (!rc && (hipMemcpyAsync(sl.pinned, sl.tally.p, bytes, hipMemcpyDeviceToHost, sl.stream) != hipSuccess ||
-                hipEventRecord(sl.done, sl.stream) != hipSuccess))
-      rc = h->fail("i3rc_hip_compute_batch: copying a batch's tallies back failed");
-    h->stream = callerStream; h->tally = callerTally;
-    if (!rc) sl.batch = 0;   // in use (any value >= 0; i3rc_hip_run_batches keeps a batch number here)
-    return rc;
+  auto start = [&](int k, uint32_t s1, bool timed) -> int {   // (batches launched ahead of the caller are not recorded in the ring of timed launches)
+    if (ready_slot(h, k) || run_batch_in_slot(h, h->pipe[k], seed0, s1, nPhotons, src, timed, true, "i3rc_hip_compute_batch")) return 1;
+    h->pipe[k].batch = 0;   // in use (any value >= 0; i3rc_hip_run_batches keeps a batch number here)
+    return 0;
   };
   i3rc_hip_integrator::BatchSignature sig;
   sig.seed0 = seed0; sig.n = nPhotons; sig.mu = src->solarMu; sig.az = src->solarAzimuth; sig.set = true;
-  // Problems whose batches can share a grid (fusable) are looked ahead in GROUPS: 8, 16, 32 ... 256 batches per fused
+  // Problems whose batches can share a grid (fuse_loop) are looked ahead in GROUPS: 8, 16, 32 ... 256 batches per fused
   // launch, up to three groups under way (one after the other on the device), the caller served from the oldest.  Such launches are not timed (the ring of
   // i3rc_hip_kernel_ms_history holds launches the caller asked for), and a group that is not wanted after all is called
   // off through its abort word: its waves stop at their next visit of the work counter.
-  const bool fuse = depth > 0 && fusable(h, nPhotons) && (h->fusion == 1 || nPhotons <= 20000000);
+  const bool fuse = depth > 0 && fuse_loop(h, nPhotons, 2);   // (a loop of unknown length: fused as any loop of several batches)
   // (a group that could not be launched -- memory -- is not tried again at every call: groups under way are still handed out)
   auto top_up = [&]() { if (!h->fusedAheadFailed) top_up_groups(h, seed0, seed1 + 1u, nPhotons, src); };
   if (!h->aheadGroups.empty()) {
@@ -1947,10 +1902,10 @@ int i3rc_hip_expect_batches(i3rc_hip_integrator *h, uint32_t seed0, uint32_t see
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
   HIPCHK(h, hipSetDevice(h->device));
   drop_lookahead(h);
-  if (!(fusable(h, nPhotons) && (h->fusion == 1 || (nBatches >= 2 && nPhotons <= 20000000)))) return 0;   // (the caller goes on as it would have)
+  if (!fuse_loop(h, nPhotons, nBatches)) return 0;   // (the caller goes on as it would have)
   {   // the problem must be complete before anything is launched (as i3rc_hip_compute_batch would find out)
     LaunchPlan plan;
-    if (make_problem(h, plan, true)) return 1;
+    if (make_problem(h, plan, h->stream, h->tally, true)) return 1;
   }
   i3rc_hip_integrator::BatchSignature sig;
   sig.seed0 = seed0; sig.n = nPhotons; sig.mu = src->solarMu; sig.az = src->solarAzimuth; sig.set = true;
@@ -1973,7 +1928,7 @@ int i3rc_hip_run_replay(i3rc_hip_integrator *h, int64_t nPhotons, const i3rc_sou
   if (!src || !randoms || !drawStart || nPhotons <= 0) return h->fail("i3rc_hip_run_replay: bad arguments");
   HIPCHK(h, hipSetDevice(h->device));
   LaunchPlan plan;
-  if (make_problem(h, plan, false, true)) return 1;
+  if (make_problem(h, plan, h->stream, h->tally, false, true)) return 1;
   RunArgs A;
   std::memset(&A, 0, sizeof(A));
   A.nPhotons = nPhotons;
@@ -1991,7 +1946,7 @@ int i3rc_hip_run_replay(i3rc_hip_integrator *h, int64_t nPhotons, const i3rc_sou
     A.fate = (int32_t *)dFate.p; A.fateColumn = (int32_t *)dCol.p; A.fateWeight = (float *)dW.p;
     A.fateOrder = (int32_t *)dOrd.p; A.drawsUsed = (int32_t *)dUsed.p;
   }
-  if (launch<ReplayStream>(h, plan, A, false)) return 1;
+  if (launch<ReplayStream>(h, plan, A, h->stream, false)) return 1;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (rec) {
     HIPCHK(h, hipMemcpy(fate, dFate.p, sizeof(int32_t) * nPhotons, hipMemcpyDeviceToHost));
@@ -2020,7 +1975,7 @@ int i3rc_hip_trace_rays(i3rc_hip_integrator *h, int64_t n, const float *dir, flo
   for (int c = 0; c < h->ncomp; ++c) if (!h->comp[c].inv) h->comp[c].inv = &dummy;
   const int savedDir = h->nDir;
   h->nDir = 0;
-  const int rc = make_problem(h, plan);
+  const int rc = make_problem(h, plan, h->stream, h->tally);
   h->nDir = savedDir;
   h->comp = saved;
   h->compDirty = true;

@@ -318,7 +318,8 @@ int i3rc_hip_set_batch_fusion(i3rc_hip_integrator *h, int mode);
  * problem class (regular x / y grid, ray tracing, one component, no BRDF grid, Directional source) when the problem is
  * in it, else the general kernel.  All kernels trace the same photon paths from the same per-photon random streams,
  * so tests run one against the other.
- *   GENERAL: always the general kernel;  LANE: same choice as AUTO;  RING: as AUTO, but a radiance problem with ONE
+ *   GENERAL: always the general kernel;  LANE: as AUTO, but plain flux launches never run the kernels that keep the inverse
+ *   table in LDS (the kernel matrix reaches the plain specialised flux kernels through it);  RING: as AUTO, but a radiance problem with ONE
  *   direction goes through the event ring like any other (AUTO gives such problems the kernels without a ring, in which
  *   the event phase itself makes the event's ray ready and a ready store of two wavefronts gathers the survivors). */
 enum { I3RC_KERNEL_AUTO = 0, I3RC_KERNEL_GENERAL = 1, I3RC_KERNEL_LANE = 2, I3RC_KERNEL_RING = 3 };
