@@ -29,6 +29,7 @@
 #pragma once
 #include <cstddef>
 #include "tracer.hpp"
+#include "tuning.hpp"
 
 namespace i3rc {
 
@@ -42,6 +43,15 @@ struct WaveCounters {   // 32 bits are enough: a wave hands its counts over ever
   uint32_t photons = 0, dropped = 0, steps = 0, scat = 0, surf = 0, top = 0, roul = 0, shadow = 0, calls = 0;
 };
 struct NestedCounters { uint32_t shadow = 0, calls = 0; };
+// Two 16-bit counts in one register: what a lane of a fused flux launch counts for its photon's batch (photon_kernel, LANE_COUNTS).
+// One event adds at most one to each count; a lane hands its counts over before either could leave its 16 bits.
+struct LanePairs {
+  uint32_t word = 0u;
+  __device__ __forceinline__ void add(bool low, bool high) { word += (low ? 1u : 0u) + (high ? 1u << 16 : 0u); }
+  __device__ __forceinline__ uint32_t low() const { return word & 0xffffu; }
+  __device__ __forceinline__ uint32_t high() const { return word >> 16; }
+  static __device__ __forceinline__ bool about_to_overflow(LanePairs a, LanePairs b) { return ((a.word | b.word) & ((1u << 15) | (1u << 31))) != 0u; }
+};
 
 __device__ __forceinline__ unsigned count_lanes(bool p) { return (unsigned)__popcll(__ballot(p)); }
 // number of lanes below this one whose bit is set in a wave-uniform mask
@@ -339,34 +349,20 @@ __global__ void __launch_bounds__(256) slab_fill_kernel(uint32_t seed0, uint32_t
   }
 }
 
-#ifndef I3RC_RADIANCE_WAVES
-#define I3RC_RADIANCE_WAVES 5   /* (the Landsat + 7 directions case gains 9 % over 4; 6 would spill) */
-#endif
-#ifndef I3RC_MIN_WAVES
-#define I3RC_MIN_WAVES 5
-#endif
-// The specialised flux kernels need 54 vector registers: told to plan for eight waves per SIMD (instead of five) the
-// compiler schedules them differently -- step cloud 3.13 -> 3.27e9 photons/s on the same box, 32 layers 2.56 -> 2.67e9,
-// radar 640 flux 1.24 -> 1.29e9, Landsat-36 -0.5 %; the bricked kernels (at most five workgroups per CU anyway) lose 1 %.
-#ifndef I3RC_FLUX_WAVES
-#define I3RC_FLUX_WAVES 8
-#endif
-// (the fused multi-batch kernels carry five more vector registers per lane -- the batch and the per-lane counts -- and want 66:
-// planned for seven waves per SIMD they keep them all; for eight, two go to scratch and nothing is gained: 2.97 against
-// 2.83 ... 3.06e9 photons/s on the step cloud, 1.22 against 1.08e9 on the radar field, within the noise elsewhere)
-#ifndef I3RC_FUSED_WAVES
-#define I3RC_FUSED_WAVES 7
-#endif
-// (the radiance kernels for several components carry the stream's cursor and the component on top of the one-component kernels' 96
-// registers: planned for five waves per SIMD they keep 4 ... 14 of them in scratch; measured against four waves: DESIGN.md section 8)
-#ifndef I3RC_MULTI_WAVES
-#define I3RC_MULTI_WAVES 4
-#endif
+// Waves per SIMD an instantiation of photon_kernel is compiled for (its __launch_bounds__; the knobs and their measurements: tuning.hpp)
+template <class Rng, bool INTENSITY, bool GENERAL, int GRID, bool TBL, bool MULTI>
+constexpr int planned_waves() {
+  // (radiance kernels keep two rays per lane live -- the photon's and a shadow ray's: 4 waves per SIMD give them 128 vector registers)
+  if (INTENSITY && GENERAL) return 3;
+  if (INTENSITY) return MULTI ? I3RC_MULTI_WAVES : I3RC_RADIANCE_WAVES;
+  if (GENERAL || GRID == GRID_BRICKS) return I3RC_MIN_WAVES;   // (the bricked kernels: at most five workgroups per CU anyway)
+  if (Rng::kBatched && !TBL) return MULTI ? I3RC_FUSED_WAVES - 2 : I3RC_FUSED_WAVES;
+  return I3RC_FLUX_WAVES;   // (the specialised flux kernels; the fused table-in-LDS ones: 1024 threads, two workgroups per CU)
+}
 // GENERAL = false is the specialisation for the common problem class -- regular grid, ray tracing, one component,
 // Lambertian albedo (no BRDF grid), Directional source, production RNG: the rare paths (grid searches, periodic
 // re-wrapping loops, max-cross-section moves, BRDF lookups, component selection) are compiled out, which shrinks the
 // loop's code and its scalar-register pressure.  GENERAL = true keeps every path behind run-time switches.
-// (radiance kernels keep two rays per lane live -- the photon's and a shadow ray's: 4 waves per SIMD give them 128 vector registers)
 // TBL (round 3, specialised flux kernels): workgroups of 1024 threads, two per compute unit, that also keep the 40 KB of the
 // inverse table's cosines (one entry) in LDS: the two dependent table reads of a scattering then come from LDS instead of
 // L2 or beyond (+1.6 % on the step cloud, +22 % on Landsat-36; the launch chooses it: i3rc_hip.hip).
@@ -384,7 +380,8 @@ __global__ void __launch_bounds__(256) slab_fill_kernel(uint32_t seed0, uint32_t
 // tracing, no BRDF grid, Directional source -- as compiled out as in the one-component kernels; the deviates are drawn as the general
 // kernels draw them (the component's from the stream's cursor), so that a MULTI launch traces the general kernels' photons.
 template <class Rng, bool INTENSITY, bool GENERAL, int GRID, bool TBL = false, bool DIRECT = false, bool MULTI = false>
-__global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (MULTI ? I3RC_MULTI_WAVES : I3RC_RADIANCE_WAVES)) : ((GENERAL || GRID == GRID_BRICKS) ? I3RC_MIN_WAVES : ((Rng::kBatched && !TBL) ? (MULTI ? I3RC_FUSED_WAVES - 2 : I3RC_FUSED_WAVES) : I3RC_FLUX_WAVES))) photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const int lightThreshold) {
+__global__ void __launch_bounds__(TBL ? 1024 : 256, (planned_waves<Rng, INTENSITY, GENERAL, GRID, TBL, MULTI>()))
+photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const int lightThreshold) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   Lds L;
   {
@@ -475,9 +472,6 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
   // another batch's block).  In clouds whose cells are optically thick (an LES field: 55 m cells, free paths of 10 m) a photon is
   // scattered several times in a row in the cell it is in; the memory side takes some 2e10 scattered atomics a second, which one per
   // scattering reaches at 1.1e9 photons/s (Tally::absorbed).  The sum is float64: the same additions in another grouping.
-#ifndef I3RC_MERGE_ABSORPTION
-#define I3RC_MERGE_ABSORPTION 1
-#endif
   // (flux kernels: the radiance kernels, the general ones at three waves per SIMD and the fused table-in-LDS kernels at eight have no
   // three registers to spare -- with them they spilled 6 ... 20 bytes a lane)
   constexpr bool MERGE = I3RC_MERGE_ABSORPTION != 0 && !INTENSITY && !(Rng::kBatched && TBL);
@@ -505,7 +499,8 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
   // (top, surface, roulette, tracer error) and every event that does not end it starts a trace, so a batch's calls are its
   // scatterings + surface arrivals + exits through the top + dropped photons.  Photons are counted where they are handed
   // out (wave-uniform: resTaken), dropped ones at once (rare).
-  uint32_t accSteps = 0u, accA = 0u, accB = 0u;   // steps; scatterings | roulette << 16; surface arrivals | exits top << 16
+  uint32_t accSteps = 0u;                         // voxel steps
+  LanePairs accA, accB;                           // scatterings (low) | roulette plays (high); surface arrivals | exits through the top
   uint32_t resTaken = 0u;                         // photons of the reservoir's batch handed out since the last hand-over
   const unsigned rep = BATCHED ? blockIdx.x % (unsigned)A.replicas : 0u;
   auto lane_block = [&](uint32_t b) -> double * {   // tally block of batch b for this workgroup (RunArgs)
@@ -532,8 +527,8 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
           return (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
         };
         const uint32_t steps = wave_total(sel ? accSteps : 0u);
-        const uint32_t scat = wave_total(sel ? (accA & 0xffffu) : 0u), roul = wave_total(sel ? (accA >> 16) : 0u);
-        const uint32_t surf = wave_total(sel ? (accB & 0xffffu) : 0u), top = wave_total(sel ? (accB >> 16) : 0u);
+        const uint32_t scat = wave_total(sel ? accA.low() : 0u), roul = wave_total(sel ? accA.high() : 0u);
+        const uint32_t surf = wave_total(sel ? accB.low() : 0u), top = wave_total(sel ? accB.high() : 0u);
         const uint32_t draws = wave_total(sel ? rng.take_used() : 0u);
         if ((threadIdx.x & 63) == 0) {
           double *const c = counter_block(b);
@@ -545,7 +540,7 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
           if (scat + surf + top) unsafeAtomicAdd(c + I3RC_CNT_TRACER_CALLS, (double)(scat + surf + top));
           if (draws) unsafeAtomicAdd(c + I3RC_CNT_RNG_DRAWS, (double)draws);
         }
-        if (sel) accSteps = accA = accB = 0u;
+        if (sel) { accSteps = 0u; accA = accB = LanePairs(); }
         todo &= ~__ballot(sel);
       }
     }
@@ -588,44 +583,10 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
   const bool defer = DEFER && rayTracing;
 #endif
   enum { R_EMPTY = 0, R_TRACE = 1, R_ENDED = 2 };
-#ifndef I3RC_STEP_AHEAD
-#define I3RC_STEP_AHEAD 2
-#endif
-#ifndef I3RC_LOW_WATER
-#define I3RC_LOW_WATER 64   /* = the ready buffer: with nothing left to expand, a wave leaves its rays unless a whole wavefront of them is in hand */
-#endif
-#ifndef I3RC_THIRD_STEP
-#define I3RC_THIRD_STEP 4   /* a third ray step per pass when the service phase is this much further away: Landsat + 7 directions +2.4 % */
-#endif
-#ifndef I3RC_TURN_MIN
-#define I3RC_TURN_MIN 4
-#endif
-#ifndef I3RC_TURN_FORCE
-#define I3RC_TURN_FORCE 12
-#endif
-#ifndef I3RC_PHOTON_STEP_AHEAD
-#define I3RC_PHOTON_STEP_AHEAD 64   /* off: measured -1.6 % (step cloud) ... +2.8 % (Landsat-36), -3 % on the radar field */
-#endif
-  // measured (Landsat + 7 directions, 2e7 photons, before the lazy roulette): low water 16 / 32 / 48 / 56 / 64 -> 3.1 / 4.2 / 4.6 / 4.7 /
-  // 4.7e7 photons/s; two steps per pass +8 %.  With the lazy roulette (most rays end in EXPAND): low water 40 / 48 / 56 / 64 ->
-  // 8.2 / 9.1 / 9.2 / 9.4e7 (radar-64 + nadir 5.8 / 5.9 / 6.1 / 6.2e8); expand batch 16 / 32 / 48 / 64 -> radar-64 5.8 / 6.1 /
-  // 6.3 / 6.4e8; both at 64: +5.5 % (radar-64), +3 % (Landsat + 7 directions), +4 % (radar 640 + nadir)
+  // (the schedule's levels and their measurements: tuning.hpp)
   constexpr int kTurnMin = Rng::kReplay ? 1 : I3RC_TURN_MIN, kTurnForce = Rng::kReplay ? 1 : I3RC_TURN_FORCE;
-#ifndef I3RC_EXPAND_BATCH
-#define I3RC_EXPAND_BATCH 64   /* = the ready buffer: expand when it is empty, a whole wavefront at a time */
-#endif
   constexpr int kExpandBatch = I3RC_EXPAND_BATCH;   // an expand phase runs when the ready buffer has room for this many rays
-  // DIRECT: rays are traced once this many survivors are ready (or when the next event phase's rays would not fit into the store
-  // of 128: wantSlots), and the wave goes back to its photons when nothing is left to hand out and fewer than
-  // kDirectLeave rays are still under way (those few go back to the store: with rays of one or two voxel steps, a wave that
-  // left with a wavefront's worth under way -- the ring mode's rule -- would write back and take up again most of its rays)
-#ifndef I3RC_DIRECT_ENTER
-#define I3RC_DIRECT_ENTER 96   /* (radar-64 + nadir, 5e7 photons: 64 -> 59.1 ms, 80 -> 58.8, 96 -> 58.2, 112 -> 58.3; leave level 8 ... 48: within 1 %) */
-#endif
-#ifndef I3RC_DIRECT_LEAVE
-#define I3RC_DIRECT_LEAVE 24
-#endif
-  constexpr int kDirectEnter = I3RC_DIRECT_ENTER, kDirectLeave = I3RC_DIRECT_LEAVE;
+  constexpr int kDirectEnter = I3RC_DIRECT_ENTER, kDirectLeave = I3RC_DIRECT_LEAVE;   // DIRECT: the levels of ready / running rays at which a wave turns to its rays / back
   // (an event phase that would not fit -- possible when kDirectEnter is set above kDirectReady - 64 -- sends the wave to its rays first: wantSlots)
   static_assert(!DIRECT || (kDirectReady >= kDirectEnter && (kDirectReady & (kDirectReady - 1)) == 0), "the ready store holds the entry level; a power of two");
   constexpr int kLowWater = I3RC_LOW_WATER, kStepAhead = I3RC_STEP_AHEAD, kPhotonStepAhead = I3RC_PHOTON_STEP_AHEAD;
@@ -634,12 +595,12 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
   unsigned rdHead = 0u, rdTail = 0u;                  // ready rays taken / made
   constexpr int kReady = DIRECT ? kDirectReady : kReadyRays;     // slots of the wave's ready store
   lds_float *const qBase = L.queue + (threadIdx.x >> 6) * (kRecWords * P.rayQueueCap + kReadyWords * kReady);
-  lds_float *const rdBase = qBase + kRecWords * P.rayQueueCap;   // ready rays: word w of slot s at rdBase[w * kReady + s]
+  lds_float *const rdBase = qBase + kRecWords * P.rayQueueCap;   // ready rays (ReadyRay, tracer.hpp)
   const unsigned qMask = (unsigned)P.rayQueueCap - 1u;
   const unsigned qMagic = ((1u << 20) + (unsigned)P.nDir - 1u) / (unsigned)(P.nDir > 0 ? P.nDir : 1);   // t / nDir = (t * qMagic) >> 20 for t < nDir + 64 <= 319 (nDir <= 255)
   bool pendingShadow = false;
   float wI = 0.0f, inDx = 0.0f, inDy = 0.0f, inDz = 0.0f;   // of the event being pushed
-  int evInfo = 0;
+  int evInfo = 0;   // (an EventInfo word)
 
   // Thresholds: fixed when the caller asks for them (> 0), else adapted by every wave to its own photons at every
   // reservoir refill.  Event phase: the longer the photons' own traces (voxel steps per event), the more a
@@ -658,15 +619,6 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
     if (adaptEvent) {
       const float events = (float)(wc.scat + wc.photons + wc.surf), steps = (float)wc.steps;
       if (events > 0.0f && steps > 0.0f) {
-        // (round 4, the step phase a third cheaper than it was: 44 - slope * steps per event fits the measured optima -- step cloud 36 ... 40
-        // at 2.5 steps per event, Landsat-36 28 at 9.5, Landsat-119 18 ... 20 at 15 -- where 58 / sqrt(steps per event) sat below them on
-        // the long traces; radiance kernels, whose photons share the wave's time with their rays, want the flatter slope)
-#ifndef I3RC_EVTHR_SLOPE_FLUX
-#define I3RC_EVTHR_SLOPE_FLUX 2.0f
-#endif
-#ifndef I3RC_EVTHR_SLOPE_RADIANCE
-#define I3RC_EVTHR_SLOPE_RADIANCE 1.2f
-#endif
         const int t = (int)(44.0f - (INTENSITY ? I3RC_EVTHR_SLOPE_RADIANCE : I3RC_EVTHR_SLOPE_FLUX) * (steps * __builtin_amdgcn_rcpf(events)));
         evThr = __builtin_amdgcn_readfirstlane(t < 12 ? 12 : (t > 44 ? 44 : t));
       }
@@ -674,12 +626,6 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
     if (adaptLight) {
       raysSeen += raysStarted; raysStarted = 0u;
       if (raysSeen > 0u && wc.shadow > 0u) {
-#ifndef I3RC_LITHR_COEF
-#define I3RC_LITHR_COEF 70.0f
-#endif
-#ifndef I3RC_LITHR_MIN
-#define I3RC_LITHR_MIN 16
-#endif
         const int t = (int)(I3RC_LITHR_COEF * __builtin_amdgcn_rsqf((float)wc.shadow * __builtin_amdgcn_rcpf((float)raysSeen)));
         liThr = __builtin_amdgcn_readfirstlane(t < I3RC_LITHR_MIN ? I3RC_LITHR_MIN : (t > 32 ? 32 : t));
       }
@@ -719,11 +665,10 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
   // look-up), the ray's own Philox block (counter: photon, block of its event, direction + 1), free path, roulette stage and
   // target.  false: the ray is known to contribute nothing and is not traced (below).  Called by the EXPAND phase of ray mode
   // (the event from the wave's ring) and, in DIRECT kernels, by the event phase itself (the event from registers).
-  // The ray's info word: component | direction << 8 | stage << 16 (0: plain local estimate, 1: small contribution, 2 / 3: the two
-  // legs of a large one) | roulette won << 18 | batch << 19 (fused launches: the batch of the ray's photon, relative to the launch's first).
+  // (the event's and the ray's info words: EventInfo, RayInfo, tracer.hpp)
   auto make_ray = [&](const auto &Px, const auto &Ax, int info, float inX, float inY, float inZ, uint32_t photonLo, uint32_t photonHi,
-                      uint32_t eventBlock, uint32_t batch, int dIdx, float &word6, float &normOut, float &tauFreeOut, float &targetOut) -> bool {
-    const int comp = info & 0xff;
+                      uint32_t eventBlock, uint32_t batch, int dIdx, float &rayWord, float &normOut, float &tauFreeOut, float &targetOut) -> bool {
+    const int comp = EventInfo::component(info);
     const float uz = L.dirCos[3 * dIdx + 2];
     float norm;
     if (comp < 1) norm = 1.0f / kPi;
@@ -736,9 +681,9 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
 #else
       const float ang = acosf(proj);
 #endif
-      const int pfi = (int)((unsigned)info >> 16);   // (table entries up to 65535: the record's upper half is unsigned)
+      const int pfi = EventInfo::table_entry(info);
       const CompTables ct = (GENERAL || MULTI) ? load_tables(Px.comp[comp - 1]) : load_tables(Px.comp0);
-      const float *tab = ((info & 0x100) ? ct.fwdOrig : ct.fwd) + (size_t)(pfi - 1) * ct.nFwd;
+      const float *tab = (EventInfo::hybrid(info) ? ct.fwdOrig : ct.fwd) + (size_t)(pfi - 1) * ct.nFwd;
       norm = fast_div(lookup_phase_fast(tab, ct.nFwd, ang), (4.0f * kPi) * fabsf(uz));
     }
     int stg = 0;
@@ -749,12 +694,12 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
       rng.count_draws(2u);
       tauFree = -fast_log(fmaxf(kTiny, u32_to_unit_float(q4.v[0])));
       // small contribution: it counts -- with the weight of the roulette's bound -- with probability pi normPF / zetaMin
-      // (:1551-1559); the deviate is compared here, the outcome travels as bit 18 of the ray's info word
+      // (:1551-1559); the deviate is compared here, the outcome travels in the ray's info word (RayInfo::won)
       const float r2 = u32_to_unit_float(q4.v[1]);
       if (kPi * norm <= Px.zetaMin) { stg = 1; won = r2 * Px.zetaMin <= kPi * norm; target = tauFree; }
       else { stg = 2; target = -fast_log(fast_div(Px.zetaMin, fmaxf(kTiny, kPi * norm))); }   // tauMax
     }
-    word6 = __int_as_float(comp | (dIdx << 8) | (stg << 16) | (won ? 1 << 18 : 0) | (int)(batch << 19));
+    rayWord = __int_as_float(RayInfo::pack(comp, dIdx, stg, won, batch));   // (as the ready ray's slot holds it)
     normOut = norm; tauFreeOut = tauFree; targetOut = target;
     // A small contribution that has lost its roulette (:1554: the deviate is independent of the path) is 0 whatever
     // the trace would find: such a ray is not traced at all -- the same estimator, evaluated lazily.  (The
@@ -796,7 +741,7 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
         // ready buffer), so that the photon loop's register allocation knows nothing of them and the other way round
         Ray sr;                                             // (every field is set when a lane takes a ray, before any use: no initial
         int rst = R_EMPTY, sInfo;                           //  values, which would cost a register copy each at every pass of the photon loop)
-        float sW, sNorm, sTauFree;                          // state; component | direction << 8 | stage << 16 (bit 24: see EXPAND); weight, phase-function factor, free path
+        float sW, sNorm, sTauFree;                          // state; info word; weight, phase-function factor, free path
         // (One back edge only: EXPAND runs in a loop of its own and SERVICE goes on into the step phase.  With three ways
         // back to the loop's head -- after an expand, after a service, after the steps -- the compiler kept the rays' 27
         // registers in one set at the head and in another at the latch and copied them to and fro, some forty vector
@@ -815,29 +760,23 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
             const auto &Px = kx->P;
             const auto &Ax = kx->A;
             bool keep = false;
-            float evWord6 = 0.0f, evNorm = 0.0f, evTauFree = 0.0f, evTarget = 0.0f;
-            const lds_float *evRec = qBase;
+            float evRayWord = 0.0f, evNorm = 0.0f, evTauFree = 0.0f, evTarget = 0.0f;
+            lds_float *evRec = qBase;
             if (lane < n) {                                                  // next radiance direction (:1473-1510)
               const unsigned t = qHeadSub + (unsigned)lane;
               const unsigned eOff = (t * qMagic) >> 20;
               const int dIdx = (int)(t - eOff * (unsigned)Px.nDir);
-              const lds_float *rec = qBase + ((qHeadEv + eOff) & qMask);
-              const int cap = Px.rayQueueCap;
-              // (fused launches: photon numbers are below 2^32 and the record's twelfth word carries the photon's batch instead)
-              const uint32_t word12 = __float_as_uint(rec[12 * cap]);
-              keep = make_ray(Px, Ax, __float_as_int(rec[10 * cap]), rec[7 * cap], rec[8 * cap], rec[9 * cap], __float_as_uint(rec[11 * cap]),
-                              BATCHED ? 0u : word12, __float_as_uint(rec[13 * cap]), BATCHED ? word12 : 0u, dIdx, evWord6, evNorm, evTauFree, evTarget);
-              evRec = rec;
+              const EventRecord<BATCHED> ev{qBase + ((qHeadEv + eOff) & qMask), Px.rayQueueCap};
+              const uint32_t photonHi = ev.photon_hi(), batch = ev.batch();   // (one word of the record: EventRecord)
+              keep = make_ray(Px, Ax, ev.info(), ev.in_dx(), ev.in_dy(), ev.in_dz(), ev.photon_lo(), photonHi, ev.philox_block(), batch, dIdx,
+                              evRayWord, evNorm, evTauFree, evTarget);
+              evRec = ev.rec;
             }
             const unsigned long long keepMask = __ballot(keep);
             if (keep) {
-              const int cap = Px.rayQueueCap;
-              lds_float *out = rdBase + ((rdTail + (unsigned)lanes_below(keepMask)) & (unsigned)(kReady - 1));
-              out[0] = evRec[0]; out[kReady] = evRec[cap]; out[2 * kReady] = evRec[2 * cap];
-              out[3 * kReady] = evRec[3 * cap]; out[4 * kReady] = evRec[4 * cap]; out[5 * kReady] = evRec[5 * cap];
-              out[6 * kReady] = evWord6;
-              out[7 * kReady] = evRec[6 * cap];
-              out[8 * kReady] = evNorm; out[9 * kReady] = evTauFree; out[10 * kReady] = evTarget; out[11 * kReady] = 0.0f;
+              const EventRecord<BATCHED> ev{evRec, Px.rayQueueCap};
+              ReadyRay::store_from(rdBase + ((rdTail + (unsigned)lanes_below(keepMask)) & (unsigned)(kReady - 1)), kReady, ev,
+                                   __float_as_int(evRayWord), evNorm, evTauFree, evTarget);
             }
             {   // ring bookkeeping (wave-uniform)
               const unsigned t = qHeadSub + (unsigned)n;
@@ -868,16 +807,16 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
             bool secondLeg = false;
             if (rst == R_ENDED) {                                           // the ray that just ended (:1517-1596)
               double *rayBlk = nullptr;                                     // (fused launches: the tally block of the ray's batch)
-              if constexpr (BATCHED) rayBlk = lane_block((uint32_t)sInfo >> 19);
+              if constexpr (BATCHED) rayBlk = lane_block(RayInfo::batch(sInfo));
               const Tally<ColdProblem, BATCHED> tally{Px, L, rayBlk};
               const float tauB = sr.acc;
               const bool outTop = sr.iz >= Px.nz + 1;
-              const int comp = sInfo & 0xff, dIdx = (sInfo >> 8) & 0xff, stage = (sInfo >> 16) & 3;
+              const int comp = RayInfo::component(sInfo), dIdx = RayInfo::direction(sInfo), stage = RayInfo::stage(sInfo);
               const float direct = tauB >= 0.0f ? (sW * sNorm) * fast_exp(-tauB) : 0.0f;   // plain local estimate
               const float capped = outTop ? sW * Px.zetaMin * (1.0f / kPi) : 0.0f;          // roulette survivor
               float con = 0.0f;
               if (stage == 0) con = direct;
-              else if (stage == 1) con = (sInfo & (1 << 18)) ? capped : 0.0f;
+              else if (stage == 1) con = RayInfo::won(sInfo) ? capped : 0.0f;
               else if (stage == 2) {
                 if (outTop) con = direct;
                 else if (tauB >= 0.0f && sr.iz >= 1) {                      // second leg, up to the free path (:1576-1587)
@@ -885,7 +824,7 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
                   // iz < 1, a failed trace tauB = -2 -- and its last advance is still to be made: trace_step_lazy.  Every other ray
                   // that ends at its target contributes nothing, wherever it stands: stages 1 and 3 count only through the top.)
                   finish_arrival(sr);
-                  sr.acc = 0.0f; sr.target = sTauFree; sInfo |= 1 << 16; rst = R_TRACE; secondLeg = true;   // (stage 2 -> 3)
+                  sr.acc = 0.0f; sr.target = sTauFree; sInfo = RayInfo::to_second_leg(sInfo); rst = R_TRACE; secondLeg = true;
                 }
                 // (a first leg that left through the BOTTOM -- a downward radiance direction -- gets no second leg: the
                 // reference starts one from outside the grid, reads zPosition(0) / totalExt(:, :, 0) out of bounds and
@@ -908,18 +847,15 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
             const int take = leaving ? 0 : (nFree < ready ? nFree : ready);   // (a wave about to leave ends its rays but takes no new ones)
             const int rank = lanes_below(freeMask);
             if (rst == R_EMPTY && rank < take) {
-              const lds_float *in = rdBase + ((rdHead + (unsigned)rank) & (unsigned)(kReady - 1));
-              sr.x = in[0]; sr.y = in[kReady]; sr.z = in[2 * kReady];
-              sr.ix = __float_as_int(in[3 * kReady]); sr.iy = __float_as_int(in[4 * kReady]); sr.iz = __float_as_int(in[5 * kReady]);
-              sInfo = __float_as_int(in[6 * kReady]);
-              sW = in[7 * kReady]; sNorm = in[8 * kReady]; sTauFree = in[9 * kReady];
-              sr.target = in[10 * kReady]; sr.acc = in[11 * kReady];
+              const ReadyRay::Words in = ReadyRay::load(rdBase + ((rdHead + (unsigned)rank) & (unsigned)(kReady - 1)), kReady);
+              sr.x = in.x; sr.y = in.y; sr.z = in.z; sr.ix = in.ix; sr.iy = in.iy; sr.iz = in.iz;
+              sInfo = in.info; sW = in.weight; sNorm = in.norm; sTauFree = in.freePath; sr.target = in.target; sr.acc = in.opticalPath;
 #ifdef I3RC_NO_DIRTAB   /* (measurement knob: the direction's derived values worked out at every ray start, as before round 4) */
-              const int dIdx = (sInfo >> 8) & 0xff;
+              const int dIdx = RayInfo::direction(sInfo);
               sr.dx = L.dirCos[3 * dIdx]; sr.dy = L.dirCos[3 * dIdx + 1]; sr.dz = L.dirCos[3 * dIdx + 2];
               sr.set_direction(L);
 #else
-              sr.load_direction(L.dirTab + 16 * ((sInfo >> 8) & 0xff));
+              sr.load_direction(L.dirTab + 16 * RayInfo::direction(sInfo));
 #endif
               rst = R_TRACE;
             }
@@ -937,12 +873,8 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
           const int readyNow = (int)(rdTail - rdHead);
           if ((leaving && (DIRECT || ready + nBack < kLowWater)) || (nBack == 0 && readyNow == 0 && ringRays == 0)) {
             if (rst == R_TRACE) {
-              lds_float *out = rdBase + ((rdTail + (unsigned)lanes_below(backMask)) & (unsigned)(kReady - 1));
-              out[0] = sr.x; out[kReady] = sr.y; out[2 * kReady] = sr.z;
-              out[3 * kReady] = __int_as_float(sr.ix); out[4 * kReady] = __int_as_float(sr.iy); out[5 * kReady] = __int_as_float(sr.iz);
-              out[6 * kReady] = __int_as_float(sInfo);
-              out[7 * kReady] = sW; out[8 * kReady] = sNorm; out[9 * kReady] = sTauFree;
-              out[10 * kReady] = sr.target; out[11 * kReady] = sr.acc;
+              ReadyRay::store(rdBase + ((rdTail + (unsigned)lanes_below(backMask)) & (unsigned)(kReady - 1)), kReady, sr.x, sr.y, sr.z, sr.ix, sr.iy, sr.iz,
+                              sInfo, sW, sNorm, sTauFree, sr.target, sr.acc);
             }
             rdTail += (unsigned)nBack;
             wc.calls -= (unsigned)nBack;      // (they are counted again when they are taken up: one tracer call each, whatever the schedule)
@@ -961,7 +893,7 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
               // (an arrival: see the service phase.  The ray's own stage says whether it has a target: the wave-uniform P.useRRI says the
               // same, and as a run-time flag in this loop it came out as a lane mask made under another loop's exec mask -- GridPlace's trap,
               // caught by tests/test_build_isa.py)
-              if (trace_step_lazy<GRID, false, GENERAL, !DIRECT>(P, L, sr, ((sInfo >> 16) & 3) != 0) != STEP_CONTINUE) rst = R_ENDED;   // (ring kernels: the short form, see trace_step_lazy)
+              if (trace_step_lazy<GRID, false, GENERAL, !DIRECT>(P, L, sr, RayInfo::stage(sInfo) != 0) != STEP_CONTINUE) rst = R_ENDED;   // (ring kernels: the short form, see trace_step_lazy)
             }
             PROF_END(PH_RAYSTEP, nTracing);
           };
@@ -1015,7 +947,7 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
       const auto &Ae = ke->A;
       if constexpr (LANE_COUNTS) {   // a 16-bit count about to overflow (one event adds at most one to each): hand over now
         // (steps: a hand-over sums the lanes' counts across the wave in 32 bits -- 64 lanes of less than 2^25 each)
-        const bool full = ((accA | accB) & 0x80008000u) != 0u || accSteps >= (1u << 25);
+        const bool full = LanePairs::about_to_overflow(accA, accB) || accSteps >= (1u << 25);
         if (__ballot(full) != 0ull) flush_lanes(full);
       }
       double *laneBlk = nullptr;
@@ -1040,7 +972,7 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
       wc.top += count_lanes(atTop);
       wc.surf += count_lanes(atSurface);
       if constexpr (BATCHED) {
-        if constexpr (LANE_COUNTS) accB += (atSurface ? 1u : 0u) + (atTop ? 0x10000u : 0u);
+        if constexpr (LANE_COUNTS) accB.add(atSurface, atTop);
         if (dropped) {
           double *const c = counter_block(rng.batch);
           unsafeAtomicAdd(c + I3RC_CNT_DROPPED, 1.0);
@@ -1093,7 +1025,7 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
           }
           // a lane whose next photon belongs to another batch hands over what it has counted for the batch it leaves
           if constexpr (LANE_COUNTS) {
-            const bool leaves = isNew && mine >= 0 && mineBatch != rng.batch && (accSteps | accA | accB | rng.used) != 0u;
+            const bool leaves = isNew && mine >= 0 && mineBatch != rng.batch && (accSteps | accA.word | accB.word | rng.used) != 0u;
             if (__ballot(leaves) != 0ull) flush_lanes(leaves);
           }
           if (isNew) {
@@ -1198,7 +1130,7 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
                 const float sinTheta = exact_sqrt(1.0f - mu * mu);
                 r.dx = sinTheta * __builtin_amdgcn_cosf(turn); r.dy = sinTheta * __builtin_amdgcn_sinf(turn); r.dz = mu;
               }
-              if (defer) { pendingShadow = true; wI = w; evInfo = 0; }    // component 0: the surface (:567-580)
+              if (defer) { pendingShadow = true; wI = w; evInfo = EventInfo::kSurface; }
               else if (INTENSITY)
                 intensity_contribution<GRID>(Pe, L, rng, nested, w, r.x, r.y, r.z, r.ix, r.iy, r.iz, r.dx, r.dy, r.dz, 0, order);
               st = ST_TRACE;
@@ -1239,9 +1171,6 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
               const bool needCell = GENERAL || MULTI || !(Pe.uniformSsa >= 0.0f) || Pe.uniformSsa < 1.0f || Pe.uniformPf < 1;
               if (needCell) cell = cell_index(Pe, r.ix, r.iy, r.iz);
               int comp = 1;                                               // :637-638
-#ifndef I3RC_CELL_RECORD_READS
-#define I3RC_CELL_RECORD_READS 1
-#endif
               // TWO components (cloud + gas, cloud + aerosol: the usual production domain): what the scattering needs of its cell comes as
               // ONE 16-byte record (DevProblem::cellRec) -- one cache line, one trip to L2 -- and the component's pair is picked when the
               // deviate has been compared, instead of one read to choose the component and then two more, from two more arrays, that wait
@@ -1318,7 +1247,7 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
               if (defer) {                                                // :654-668: pushed after this event, traced in ray mode
                 pendingShadow = true; wI = w;
                 inDx = r.dx; inDy = r.dy; inDz = r.dz;                     // incoming direction
-                evInfo = comp | ((Pe.useHybrid && order <= Pe.numOrdersOrig) ? 0x100 : 0) | (int)((unsigned)pfi << 16);
+                evInfo = EventInfo::pack(comp, Pe.useHybrid && order <= Pe.numOrdersOrig, pfi);
               } else if (INTENSITY)
                 intensity_contribution<GRID>(Pe, L, rng, nested, w, r.x, r.y, r.z, r.ix, r.iy, r.iz, r.dx, r.dy, r.dz, comp, order);
               if (Pe.useRR && w < 0.5f) {                                  // :673-680
@@ -1361,17 +1290,13 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
       if constexpr (DIRECT) {   // one radiance direction: the event becomes a ready ray here and now (make_ray), survivors only go to LDS
         if (defer) {
           bool keep = false;
-          float word6 = 0.0f, norm = 0.0f, tauFree = 0.0f, target = 0.0f;
+          float rayWord = 0.0f, norm = 0.0f, tauFree = 0.0f, target = 0.0f;
           if (pendingShadow)
-            keep = make_ray(Pe, Ae, evInfo, inDx, inDy, inDz, rng.photon_lo(), rng.photon_hi(), rng.event_block(), rng.lane_batch(), 0, word6, norm, tauFree, target);
+            keep = make_ray(Pe, Ae, evInfo, inDx, inDy, inDz, rng.photon_lo(), rng.photon_hi(), rng.event_block(), rng.lane_batch(), 0, rayWord, norm, tauFree, target);
           const unsigned long long madeMask = __ballot(pendingShadow), keepMask = __ballot(keep);
           if (keep) {
-            lds_float *out = rdBase + ((rdTail + (unsigned)lanes_below(keepMask)) & (unsigned)(kReady - 1));
-            out[0] = r.x; out[kReady] = r.y; out[2 * kReady] = r.z;
-            out[3 * kReady] = __int_as_float(r.ix); out[4 * kReady] = __int_as_float(r.iy); out[5 * kReady] = __int_as_float(r.iz);
-            out[6 * kReady] = word6;
-            out[7 * kReady] = wI;
-            out[8 * kReady] = norm; out[9 * kReady] = tauFree; out[10 * kReady] = target; out[11 * kReady] = 0.0f;
+            ReadyRay::store(rdBase + ((rdTail + (unsigned)lanes_below(keepMask)) & (unsigned)(kReady - 1)), kReady, r.x, r.y, r.z, r.ix, r.iy, r.iz,
+                            __float_as_int(rayWord), wI, norm, tauFree, target, 0.0f);
           }
           pendingShadow = false;
           const unsigned kept = (unsigned)__popcll(keepMask);
@@ -1382,20 +1307,23 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, INTENSITY ? (GENERAL ? 3 : (
       if (defer) {   // push the events of this phase into the wave's ring: one record serves all D rays of an event
         const unsigned long long pushMask = __ballot(pendingShadow);
         if (pendingShadow) {
-          lds_float *rec = qBase + ((qTail + (unsigned)lanes_below(pushMask)) & qMask);
-          const int cap = Pe.rayQueueCap;
-          rec[0] = r.x; rec[cap] = r.y; rec[2 * cap] = r.z;
-          rec[3 * cap] = __int_as_float(r.ix); rec[4 * cap] = __int_as_float(r.iy); rec[5 * cap] = __int_as_float(r.iz);
-          rec[6 * cap] = wI;
-          rec[7 * cap] = inDx; rec[8 * cap] = inDy; rec[9 * cap] = inDz;
-          rec[10 * cap] = __int_as_float(evInfo);
-          rec[11 * cap] = __uint_as_float(rng.photon_lo()); rec[12 * cap] = __uint_as_float(BATCHED ? rng.lane_batch() : rng.photon_hi());
-          rec[13 * cap] = __uint_as_float(rng.event_block());
+          const EventRecord<BATCHED> ev{qBase + ((qTail + (unsigned)lanes_below(pushMask)) & qMask), Pe.rayQueueCap};
+          using Ev = EventRecord<BATCHED>;
+          lds_float *const rec = ev.rec;
+          const int cap = ev.cap;
+          rec[Ev::kX * cap] = r.x; rec[Ev::kY * cap] = r.y; rec[Ev::kZ * cap] = r.z;
+          rec[Ev::kIx * cap] = __int_as_float(r.ix); rec[Ev::kIy * cap] = __int_as_float(r.iy); rec[Ev::kIz * cap] = __int_as_float(r.iz);
+          rec[Ev::kWeight * cap] = wI;
+          rec[Ev::kInDx * cap] = inDx; rec[Ev::kInDy * cap] = inDy; rec[Ev::kInDz * cap] = inDz;
+          rec[Ev::kInfo * cap] = __int_as_float(evInfo);
+          rec[Ev::kPhotonLo * cap] = __uint_as_float(rng.photon_lo());
+          rec[Ev::kPhotonHiOrBatch * cap] = __uint_as_float(Ev::kCarriesBatch ? rng.lane_batch() : rng.photon_hi());
+          rec[Ev::kPhiloxBlock * cap] = __uint_as_float(rng.event_block());
           pendingShadow = false;
         }
         qTail += (unsigned)__popcll(pushMask);
       }
-      if constexpr (LANE_COUNTS) accA += (didScatter ? 1u : 0u) + (didRoulette ? 0x10000u : 0u);
+      if constexpr (LANE_COUNTS) accA.add(didScatter, didRoulette);
       wc.scat += count_lanes(didScatter);
       wc.roul += count_lanes(didRoulette);
       if constexpr (!BATCHED) wc.calls += count_lanes(startedTrace);   // (BATCHED: a batch's photon traces = its scatterings + surface arrivals + exits + drops)

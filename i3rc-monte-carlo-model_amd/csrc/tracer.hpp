@@ -152,10 +152,101 @@ struct Lds {
   lds_float *queue;           // [waves][kRecWords][rayQueueCap]: every wave's ring of local-estimate events (see kernels.hpp)
 };
 __device__ __forceinline__ void lds_add(lds_tally *p, float v) { (void)__hip_atomic_fetch_add(p, (tally_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }   // ds_add_f64 (ds_add_f32 with I3RC_LDS_F32)
-// One record of a wave's ray queue: what the D local-estimate (shadow) rays of one scattering / reflection event need.
-constexpr int kRecWords = 14;   // x y z | ix iy iz | weight | incoming direction (3) | info | photon id (2) | Philox block
-// ... and one ready-made shadow ray of the wave's ready buffer (kReadyRays of them, one expand phase's worth)
-constexpr int kReadyWords = 12;  // x y z | ix iy iz | component, direction, stage | weight | phase-function factor | free path | target | optical path so far
+// ---- The packed words and LDS records of the local-estimate (shadow) rays: each layout is defined HERE and used by name elsewhere.
+// The info word of an EVENT (a scattering or a reflection that wants its radiance rays): component (0: the surface) | hybrid << 8 (the
+// forward table of the original phase function, :1473-1510) | table entry << 16 (up to 65535: the word's upper half is unsigned).
+// (The words themselves stay plain ints in the kernel's registers: these are their layouts.)
+struct EventInfo {
+  static constexpr int kComponentBits = 8, kHybridShift = 8, kEntryShift = 16;
+  static __device__ __forceinline__ int pack(int component, bool hybrid, int tableEntry) {
+    return component | (hybrid ? 1 << kHybridShift : 0) | (int)((unsigned)tableEntry << kEntryShift);
+  }
+  static constexpr int kSurface = 0;   // component 0, no table (:567-580)
+  static __device__ __forceinline__ int component(int info) { return info & ((1 << kComponentBits) - 1); }
+  static __device__ __forceinline__ bool hybrid(int info) { return (info & (1 << kHybridShift)) != 0; }
+  static __device__ __forceinline__ int table_entry(int info) { return (int)((unsigned)info >> kEntryShift); }
+};
+// The info word of a RAY: component | direction << 8 | stage << 16 (0: plain local estimate, 1: small contribution, 2 / 3: the two
+// legs of a large one) | roulette won << 18 | batch << 19 (fused launches: the batch of the ray's photon, relative to the launch's
+// first -- kRayBatchBits of them, which bounds a fused group of a radiance run: fused_group_size, i3rc_hip.hip).
+constexpr int kRayBatchBits = 13;
+struct RayInfo {
+  static constexpr int kComponentBits = 8, kDirectionBits = 8, kStageBits = 2;
+  static constexpr int kDirectionShift = kComponentBits, kStageShift = kDirectionShift + kDirectionBits, kWonShift = kStageShift + kStageBits,
+                       kBatchShift = kWonShift + 1;
+  static_assert(kBatchShift + kRayBatchBits == 32, "the ray's info word is 32 bits");
+  static_assert(I3RC_MAX_COMPONENTS < (1 << kComponentBits) && I3RC_MAX_DIRECTIONS <= (1 << kDirectionBits),
+                "components 0 (the surface) ... ncomp and directions 0 ... nDir - 1 fit their fields");
+  static __device__ __forceinline__ int pack(int component, int direction, int stage, bool won, uint32_t batch) {
+    return component | (direction << kDirectionShift) | (stage << kStageShift) | (won ? 1 << kWonShift : 0) | (int)(batch << kBatchShift);
+  }
+  static __device__ __forceinline__ int component(int info) { return info & ((1 << kComponentBits) - 1); }
+  static __device__ __forceinline__ int direction(int info) { return (info >> kDirectionShift) & ((1 << kDirectionBits) - 1); }
+  static __device__ __forceinline__ int stage(int info) { return (info >> kStageShift) & ((1 << kStageBits) - 1); }
+  static __device__ __forceinline__ bool won(int info) { return (info & (1 << kWonShift)) != 0; }
+  static __device__ __forceinline__ uint32_t batch(int info) { return (uint32_t)info >> kBatchShift; }
+  static __device__ __forceinline__ int to_second_leg(int info) { return info | 1 << kStageShift; }   // stage 2 -> 3
+};
+// One record of a wave's ray queue (the ring): what the D rays of one event need.  Word w of the record at `rec` is rec[w * cap],
+// cap the ring's capacity in records.  Photon numbers of a fused launch are below 2^32: there the word of their upper half carries
+// the photon's batch instead.
+constexpr int kRecWords = 14;
+template <bool BATCHED>
+struct EventRecord {
+  enum Word { kX, kY, kZ, kIx, kIy, kIz, kWeight, kInDx, kInDy, kInDz, kInfo, kPhotonLo, kPhotonHiOrBatch, kPhiloxBlock, kWords };
+  static_assert(kWords == kRecWords, "EventRecord names every word of a record");
+  static constexpr bool kCarriesBatch = BATCHED;
+  lds_float *rec;
+  int cap;
+  __device__ __forceinline__ lds_float &at(int w) const { return rec[w * cap]; }
+  // The one writer is the event phase of photon_kernel, which stores the words by these names on the raw pointer: every push()
+  // tried here -- values as arguments, the stream by reference or by value, stores through at() -- made the compiler order some
+  // ring kernel's instructions differently (the same program, no longer the same assembly).  The readers: what make_ray needs of
+  // an event below; the ray's start -- position, cell, weight -- goes from the record to a ready ray's slot in ReadyRay::store_from.
+  __device__ __forceinline__ float in_dx() const { return at(kInDx); }
+  __device__ __forceinline__ float in_dy() const { return at(kInDy); }
+  __device__ __forceinline__ float in_dz() const { return at(kInDz); }
+  __device__ __forceinline__ int info() const { return __float_as_int(at(kInfo)); }   // (an EventInfo word)
+  __device__ __forceinline__ uint32_t photon_lo() const { return __float_as_uint(at(kPhotonLo)); }
+  __device__ __forceinline__ uint32_t photon_hi() const { return kCarriesBatch ? 0u : __float_as_uint(at(kPhotonHiOrBatch)); }
+  __device__ __forceinline__ uint32_t batch() const { return kCarriesBatch ? __float_as_uint(at(kPhotonHiOrBatch)) : 0u; }
+  __device__ __forceinline__ uint32_t philox_block() const { return __float_as_uint(at(kPhiloxBlock)); }
+};
+// ... and one ready-made ray of the wave's ready store (kReadyRays slots; the one-direction kernels: kDirectReady).  Word w of the
+// ray in slot s is store[w * slots + s]; `slot` below is store + s.
+constexpr int kReadyWords = 12;
+struct ReadyRay {
+  enum Word { kX, kY, kZ, kIx, kIy, kIz, kInfo, kWeight, kNorm /* phase-function factor */, kFreePath, kTarget, kOpticalPath /* so far */, kWords };
+  static_assert(kWords == kReadyWords, "ReadyRay names every word of a slot");
+  static __device__ __forceinline__ void store(lds_float *slot, int slots, float x, float y, float z, int ix, int iy, int iz, int info,
+                                               float weight, float norm, float freePath, float target, float opticalPath) {
+    slot[kX * slots] = x; slot[kY * slots] = y; slot[kZ * slots] = z;
+    slot[kIx * slots] = __int_as_float(ix); slot[kIy * slots] = __int_as_float(iy); slot[kIz * slots] = __int_as_float(iz);
+    slot[kInfo * slots] = __int_as_float(info);
+    slot[kWeight * slots] = weight; slot[kNorm * slots] = norm; slot[kFreePath * slots] = freePath;
+    slot[kTarget * slots] = target; slot[kOpticalPath * slots] = opticalPath;
+  }
+  // ... of a ray that starts where its event happened: position, cell and weight word by word from the event's record (a read, a write)
+  template <bool BATCHED>
+  static __device__ __forceinline__ void store_from(lds_float *slot, int slots, const EventRecord<BATCHED> &ev, int info, float norm, float freePath, float target) {
+    slot[kX * slots] = ev.at(ev.kX); slot[kY * slots] = ev.at(ev.kY); slot[kZ * slots] = ev.at(ev.kZ);
+    slot[kIx * slots] = ev.at(ev.kIx); slot[kIy * slots] = ev.at(ev.kIy); slot[kIz * slots] = ev.at(ev.kIz);
+    slot[kInfo * slots] = __int_as_float(info);
+    slot[kWeight * slots] = ev.at(ev.kWeight);
+    slot[kNorm * slots] = norm; slot[kFreePath * slots] = freePath; slot[kTarget * slots] = target; slot[kOpticalPath * slots] = 0.0f;
+  }
+  // (by value: with twelve references to fill, the radiance kernels came out with other register names and another order of moves)
+  struct Words { float x, y, z; int ix, iy, iz, info; float weight, norm, freePath, target, opticalPath; };
+  static __device__ __forceinline__ Words load(const lds_float *slot, int slots) {
+    Words w;
+    w.x = slot[kX * slots]; w.y = slot[kY * slots]; w.z = slot[kZ * slots];
+    w.ix = __float_as_int(slot[kIx * slots]); w.iy = __float_as_int(slot[kIy * slots]); w.iz = __float_as_int(slot[kIz * slots]);
+    w.info = __float_as_int(slot[kInfo * slots]);
+    w.weight = slot[kWeight * slots]; w.norm = slot[kNorm * slots]; w.freePath = slot[kFreePath * slots];
+    w.target = slot[kTarget * slots]; w.opticalPath = slot[kOpticalPath * slots];
+    return w;
+  }
+};
 constexpr int kReadyRays = 64;
 #ifndef I3RC_DIRECT_READY
 #define I3RC_DIRECT_READY 128
