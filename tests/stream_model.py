@@ -1,0 +1,630 @@
+"""A float64 model of the PRODUCTION photon streams in a horizontally uniform medium, written from the convention as
+csrc/philox.hpp (PhiloxStreamT), csrc/kernels.hpp (photon_kernel: parts A to C of the event phase, make_ray) and csrc/tracer.hpp
+(scattering_cosine<false>, next_direct, lookup_phase_fast) state it.  Plain numpy; of the product it imports nothing, and of the
+tests only tests/philox_ref.py (the scalar Philox that `philox` below is held against).
+
+What the model follows (the line it restates in brackets):
+  * key (seed0, seed1), counter (photon_lo, photon_hi, block, 0); block 0 of a photon gives start x, start y and the first optical
+    depth, block k its k-th event; next() -- the component choice -- refills from the SAME block counter, four deviates a block
+    [PhiloxStreamT::make_block, begin_event, next];
+  * deviate = float32(float64(u) / (2^32 - 1)) [u32_to_unit_float];
+  * roles: first() scattering angle | start x | cosine of a reflection; second() azimuth | start y; path() optical depth; spare()
+    roulette [philox.hpp, the comment above PhiloxStreamT];
+  * the scattering cosine in float32, operation by operation, with quirk Q1 (`left` is not rescaled by n) [scattering_cosine<false>];
+    1 - cos^2 in float32 as well (near-forward scattering is badly conditioned there: the model must not be better than the kernel);
+  * the new direction: next_direct's formula in float64, azimuth 2 pi second() [next_direct, disc_point];
+  * surface: mu = sqrt(first()), azimuth second(), weight times albedo; a black surface ends a photon of a flux kernel without a
+    block being drawn, a radiance kernel draws the block and its two deviates first [part A `atBlack`, part C];
+  * components: 1 + number of the cell's first ncomp - 1 cumulative extinction fractions at or below the deviate [part C, MULTI];
+  * absorption w (1 - omega) into the cell, then w omega; roulette below 0.5: spare() >= w ends the photon, else w = 1 [part C];
+  * radiance, plain local estimate: w P(theta) / (4 pi |mu_d|) exp(-tau) per event and direction, the surface's w / pi exp(-tau), into
+    the column in which the RAY leaves the domain [service phase: `(sr.iy - 1) * nx + (sr.ix - 1)`]; hybrid tables for orders up
+    to numOrdersOrig; the contribution limit [make_ray, service phase];
+  * counters, and the deviates consumed one by one (I3RC_CNT_RNG_DRAWS).
+The optical path is analytic: with C(z) the extinction integrated from the bottom, a path of optical depth tau along direction
+cosine dz ends where C changes by tau |dz|.  The tracer itself is pinned bit for bit elsewhere (tests/test_gpu_parity.py).
+
+Out of scope (the replay pin and the oracle tests cover them): max cross-section, the local estimate's own roulette (Iwabuchi) --
+and with it the local-estimate ray's Philox block, which is drawn for nothing else --, gridded surfaces, explicit photon sources,
+horizontally varying fields.
+
+MARGINS AND BOUNDS.  Every discrete decision records its margin and the model's own bound on the float32 error of the compared
+quantity; a photon is FRAGILE when some margin is below 4 bounds.  The decisions: top / bottom / which layer (one comparison of
+optical depths), the component compare (both sides are float32 values the kernel holds too: bound 0), the roulette compares
+(w < 0.5, spare >= w), the column of an event, an exit or a ray's exit, the sign of the direction's z-cosine in next_direct (its
+frame changes hands there) and the contribution limit.  The table intervals are no such decisions here: the inverse table's k comes
+from a float32 product the model forms bit for bit, and the forward table's interpolation is continuous across k -- a neighbouring
+interval is within what P at theta +- e_theta already allows.  The bound is first order and summed along
+the photon's events from what the code states: hardware sin / cos 1e-7 absolute, fast_log 2 ulp, v_rcp / v_sqrt / v_exp 1 ulp, one
+rounding (2^-24 relative) per float32 operation otherwise, one ulp for the scattering cosine wherever refined_rcp(n) one ulp off the
+correctly rounded 1 / n would give another one (evaluated per event):
+  height          kept as e_C, the error of C(z): e_C + |dz| (2 ulp tau + 3 eps steps tau_path) + (side faces + 1) eps (|z|max + 2 dz) ext_max
+                  + tau_path e_dir, which is what the comparison with the layers' faces, the top and the bottom sees (a coordinate is
+                  exact on a face it has just reached: z is rounded only where a side face is crossed); + 4 eps |z|max ext at the event
+  x, y            e_xy + s e_dir + |d| e_s + steps eps (|x|max + 2 dx),  e_s = (e_C' / ext' + e_C / ext) / |dz| + s e_dir / |dz|
+  direction       gain e_dir + [ulp / sin(theta) where the cosine is not certain to the bit] + 1e-7 sqrt2 sin(theta) + 3 ulp sin(theta) + 10 eps,  gain = the rotation's own
+                  Lipschitz constant at that event: the largest singular value of its finite-difference Jacobian on the tangent plane
+  weight          one eps per factor
+  radiance        the weight's, P at theta +- e_theta (evaluated, not linearised), exp at tau +- e_tau, 1 ulp each for v_rcp / v_exp
+(steps: voxel faces crossed + 1).  No constant in it is fitted to what a kernel gives.
+
+Measured with `python -m tests.stream_model` (fragile photons / photons, per shared case; the cap tests/test_stream_model_cpu.py
+asserts is 0.5 %): see FRAGILE_SHARES at the end of this module."""
+import ctypes
+import ctypes.util
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from tests.philox_ref import M0, M1, W0, W1   # (the multipliers and Weyl constants: one statement of them)
+
+f32, f64 = np.float32, np.float64
+EPS, ULP, SINCOS = 2.0 ** -24, 2.0 ** -23, 1e-7
+TINY = float(np.finfo(np.float32).tiny)
+PI32 = f32(3.14159265358979312)
+SAFETY = 4.0
+_M0, _M1, _W0, _W1, _MASK = (np.uint64(v) for v in (M0, M1, W0, W1, 0xFFFFFFFF))
+_S32 = np.uint64(32)
+_libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+for _n in ("cosf", "sinf", "sqrtf"):
+    getattr(_libm, _n).argtypes, getattr(_libm, _n).restype = [ctypes.c_float], ctypes.c_float
+
+
+def philox(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on arrays (uint64 holding 32-bit words); scalars broadcast."""
+    c0, c1, c2, c3, k0, k1 = (np.asarray(v, np.uint64) & _MASK for v in np.broadcast_arrays(c0, c1, c2, c3, k0, k1))
+    for _ in range(10):
+        p0, p1 = _M0 * c0, _M1 * c2
+        c0, c1, c2, c3 = ((p1 >> _S32) ^ c1 ^ k0) & _MASK, p1 & _MASK, ((p0 >> _S32) ^ c3 ^ k1) & _MASK, p0 & _MASK
+        k0, k1 = (k0 + _W0) & _MASK, (k1 + _W1) & _MASK
+    return c0, c1, c2, c3
+
+
+def unit(u):
+    """deviate of a 32-bit word, as a float64 holding the float32 value"""
+    return (np.asarray(u, np.uint64).astype(f64) / 4294967295.0).astype(f32).astype(f64)
+
+
+def direction(mu, phi_deg):
+    """makeDirectionCosines as the host evaluates it (float32, libm)"""
+    mu = f32(mu)
+    phi = f32(f32(f32(phi_deg) * f32(np.arccos(f32(-1.0)))) / f32(180.0))
+    st = f32(_libm.sqrtf(f32(f32(1.0) - f32(mu * mu))))
+    return np.array([f32(st * f32(_libm.cosf(phi))), f32(st * f32(_libm.sinf(phi))), mu], f32)
+
+
+@dataclass
+class Problem:
+    xe: np.ndarray
+    ye: np.ndarray
+    ze: np.ndarray
+    ext: np.ndarray                 # [ncomp, nz] float32
+    ssa: np.ndarray                 # [ncomp, nz]
+    pfi: np.ndarray                 # [ncomp, nz] table entry, 1-based (0 where there is no extinction)
+    inv: list                       # per component [nEntries, nInv] scattering angles, as handed to the device
+    mu0: float = 1.0
+    azimuth: float = 0.0
+    albedo: float = 0.0
+    roulette: bool = True
+    dirs: np.ndarray = None         # [nDir, 3] float32 direction cosines, as handed to the device
+    fwd: list = None                # per component [nEntries, nFwd]: the table in use (the hybrid one where that is on)
+    fwd_orig: list = None           # ... and the original phase functions (orders <= orders_orig with hybrid on)
+    hybrid: bool = False
+    orders_orig: int = 0
+    max_contrib: float = None       # the contribution limit; None: off
+
+    def __post_init__(self):
+        self.xe, self.ye, self.ze = (np.asarray(a, f32) for a in (self.xe, self.ye, self.ze))
+        self.ext, self.ssa = np.atleast_2d(np.asarray(self.ext, f32)), np.atleast_2d(np.asarray(self.ssa, f32))
+        self.pfi = np.atleast_2d(np.asarray(self.pfi, np.int64))
+        self.inv = [np.atleast_2d(np.asarray(t, f32)) for t in self.inv]
+        if self.dirs is not None:
+            self.dirs = np.asarray(self.dirs, f32).reshape(-1, 3)
+            self.fwd = [np.atleast_2d(np.asarray(t, f32)) for t in self.fwd]
+            self.fwd_orig = self.fwd if self.fwd_orig is None else [np.atleast_2d(np.asarray(t, f32)) for t in self.fwd_orig]
+
+    @property
+    def ndir(self):
+        return 0 if self.dirs is None else len(self.dirs)
+
+
+@dataclass
+class Result:
+    n: int
+    tallies: dict
+    bounds: dict
+    counters: dict
+    per_photon: dict                # fate (0 top, 1 surface, 2 roulette / absorbed), order, weight, fragile, counts, deposits
+    caps: dict = field(default_factory=dict)
+
+    @property
+    def fragile_share(self):
+        return float(self.per_photon["fragile"].mean())
+
+
+VARIANTS = ("swap first second", "azimuth from first", "table interval k + 1")
+
+
+def run(P, seed, first_photon, n, variant=None, drop_high_word=False):
+    """n photons first_photon .. first_photon + n - 1 of the key `seed`"""
+    assert variant is None or variant in VARIANTS, variant
+    nx, ny, nz, ncomp = len(P.xe) - 1, len(P.ye) - 1, len(P.ze) - 1, P.ext.shape[0]
+    xe, ye, ze = P.xe.astype(f64), P.ye.astype(f64), P.ze.astype(f64)
+    x0, y0, Lx, Ly = xe[0], ye[0], xe[-1] - xe[0], ye[-1] - ye[0]
+    # the host's sums (float32, component after component) and cumulative fractions
+    cum32 = np.cumsum(P.ext, axis=0, dtype=f32).astype(f32)
+    tot32 = cum32[-1]
+    frac = np.where(tot32 > TINY, cum32 / np.where(tot32 > TINY, tot32, f32(1)), cum32).astype(f32).astype(f64)
+    ext = tot32.astype(f64)
+    cumz = np.concatenate([[0.0], np.cumsum(ext * np.diff(ze))])
+    extmax = float(ext.max())
+    zs, xs = float(np.abs(ze).max()), float(max(np.abs(xe).max(), np.abs(ye).max()))
+    dzmax, dxmax = float(np.diff(ze).max()), float(max(np.diff(xe).max(), np.diff(ye).max()))
+    cosT = [np.cos(t.astype(f64)).astype(f32) for t in P.inv]
+    nd = P.ndir
+    black = not (f32(P.albedo) > TINY) and nd == 0
+    alb = float(f32(P.albedo))
+    k0, k1 = np.uint64(seed[0] & 0xFFFFFFFF), np.uint64(seed[1] & 0xFFFFFFFF)
+    pid = np.uint64(first_photon) + np.arange(n, dtype=np.uint64)
+    lo, hi = pid & _MASK, (np.zeros(n, np.uint64) if drop_high_word else pid >> _S32)
+
+    T = dict(fluxUp=np.zeros((ny, nx)), fluxDown=np.zeros((ny, nx)), volumeAbsorption=np.zeros((nz, ny, nx)),
+             intensity=np.zeros((ncomp + 1, max(nd, 1), ny, nx)), intensityExcess=np.zeros((ncomp + 1, max(nd, 1))))
+    Bd = {k: np.zeros_like(v) for k, v in T.items()}
+    cnt = {k: np.zeros(n, np.int64) for k in ("scatterings", "surfaceHits", "exitsTop", "roulette", "rngDraws")}
+    dep = {k: np.zeros(n) for k in ("fluxUp", "fluxDown", "volumeAbsorption", "intensity")}
+    fragile, why = np.zeros(n, bool), {}
+    fate, order, wfin = np.full(n, -1), np.zeros(n, np.int64), np.zeros(n)
+
+    def decide(idx, margin, bound, kind):
+        bad = margin < SAFETY * bound
+        if bad.any():
+            fragile[idx[bad]] = True
+            why[kind] = why.get(kind, 0) + int(bad.sum())
+
+    def roles(idx, blk):
+        e = philox(lo[idx], hi[idx], blk, 0, k0, k1)
+        u = [unit(w) for w in e]
+        if variant == "swap first second":
+            u[0], u[1] = u[1], u[0]
+        return u
+
+    def column(idx, xu, yu, ex_, who):
+        """periodic wrap, column and the faces crossed on the way from the photon's current column"""
+        kx, ky = np.floor((xu - x0) / Lx), np.floor((yu - y0) / Ly)
+        xw, yw = xu - kx * Lx, yu - ky * Ly
+        ci = np.clip(np.searchsorted(xe, xw, side="right") - 1, 0, nx - 1)
+        cj = np.clip(np.searchsorted(ye, yw, side="right") - 1, 0, ny - 1)
+        m = np.minimum(np.minimum(xw - xe[ci], xe[ci + 1] - xw), np.minimum(yw - ye[cj], ye[cj + 1] - yw))
+        if who:
+            decide(idx, m, ex_, who)
+        crossed = np.abs(kx * nx + ci - cix[idx]) + np.abs(ky * ny + cj - ciy[idx])
+        return xw, yw, ci, cj, crossed
+
+    def rotate(s, cosS, sinT, turn):
+        ang = 2.0 * np.pi * turn
+        ax, ay = sinT * np.cos(ang), sinT * np.sin(ang)
+        b = s[0] * ax - s[1] * ay
+        dd = cosS - b / (1.0 + np.abs(s[2]))
+        return np.array([s[0] * dd + ax, s[1] * dd - ay, s[2] * cosS - np.copysign(np.abs(b), s[2] * b)])
+
+    def radiance(idx, comp, px, py, pz, din, wgt, e_c, e_h, e_dir, e_w, ordr):
+        """the local estimate of the events `idx` (comp 0: the surface), every direction"""
+        for d in range(nd):
+            u = P.dirs[d].astype(f64)
+            up = u[2] > 0
+            zb = ze[-1] if up else ze[0]
+            s = (zb - pz) / u[2]
+            Cz = np.interp(pz, ze, cumz)
+            tauB = np.abs((cumz[-1] if up else 0.0) - Cz) / abs(u[2])
+            lay = np.clip(np.searchsorted(ze, pz, side="right") - 1, 0, nz - 1)
+            ds = e_c / np.where(ext[lay] > 0, ext[lay], 1.0) / abs(u[2])
+            exy = e_h + max(abs(u[0]), abs(u[1])) * ds
+            crossed = column(idx, px + u[0] * s, py + u[1] * s, None, None)[4]
+            steps = (nz - lay if up else lay + 1) + crossed + 1
+            _, _, ci, cj, _ = column(idx, px + u[0] * s, py + u[1] * s, exy + steps * EPS * (xs + 2 * dxmax), "ray column")
+            e_tau = (e_c + extmax * (crossed + 1) * EPS * (zs + 2 * dzmax)) / abs(u[2]) + 3 * EPS * steps * tauB
+            if comp is None:
+                norm, e_norm = np.full(len(idx), 1.0 / np.pi), np.zeros(len(idx))
+                cidx = np.zeros(len(idx), np.int64)
+            else:
+                cidx = comp
+                proj = np.clip(din[0] * u[0] + din[1] * u[1] + din[2] * u[2], -1.0, 1.0)
+                e_proj = e_dir + 4 * EPS
+                theta = np.arccos(proj)
+                e_th = np.minimum(e_proj / np.sqrt(np.maximum(1.0 - proj * proj, 1e-300)), np.sqrt(2 * e_proj)) + 4 * EPS * np.pi
+                norm, e_norm = np.zeros(len(idx)), np.zeros(len(idx))
+                for c in range(1, ncomp + 1):
+                    for orig in (False, True):
+                        sel = (comp == c) & ((P.hybrid & (ordr <= P.orders_orig)) == orig)
+                        if not sel.any():
+                            continue
+                        tab = (P.fwd_orig if orig else P.fwd)[c - 1].astype(f64)
+                        rows = tab[pfi_ev[sel] - 1]
+                        th = theta[sel]
+                        val, pos = _rowwise(rows, th)
+                        vlo, _ = _rowwise(rows, np.clip(th - e_th[sel], 0.0, np.pi))
+                        vhi, _ = _rowwise(rows, np.clip(th + e_th[sel], 0.0, np.pi))
+                        norm[sel] = val / (4.0 * np.pi * abs(u[2]))
+                        e_norm[sel] = (np.maximum(np.abs(vlo - val), np.abs(vhi - val)) + 4 * EPS * np.abs(val)) / (4.0 * np.pi * abs(u[2]))
+            att = np.exp(-tauB)
+            con = wgt * norm * att
+            e_con = con * (e_w + 4 * EPS + 3 * ULP + 2 * EPS * tauB + np.expm1(e_tau)) + wgt * e_norm * att
+            if P.max_contrib is not None:
+                mc = float(f32(P.max_contrib))
+                decide(idx, np.abs(con - mc), e_con, "contribution limit")
+                over = con > mc
+                np.add.at(T["intensityExcess"], (cidx[over], d), con[over] - mc)
+                np.add.at(Bd["intensityExcess"], (cidx[over], d), e_con[over])
+                e_con = np.where(over, 0.0, e_con)
+                con = np.where(over, mc, con)
+            np.add.at(T["intensity"], (cidx, d, cj, ci), con)
+            np.add.at(Bd["intensity"], (cidx, d, cj, ci), e_con)
+            np.add.at(dep["intensity"], idx, con)
+
+    # ---- block 0: start position, first optical depth -------------------------------------------------------------------------
+    all_ = np.arange(n)
+    u = roles(all_, 0)
+    x, y = x0 + u[0] * Lx, y0 + u[1] * Ly
+    zstart = float(f32(P.ze[0] + f32(f32(f32(1.0) - f32(ULP)) * f32(P.ze[-1] - P.ze[0]))))
+    assert zstart < ze[-1], "photons must start inside the domain (a thin elevated domain rounds the start to its top)"
+    z = np.full(n, zstart)
+    sun = direction(-abs(P.mu0), P.azimuth).astype(f64)
+    dvec = np.repeat(sun[:, None], n, axis=1)
+    w = np.ones(n)
+    tau = -np.log(np.maximum(TINY, u[2]))
+    blk = np.ones(n, np.int64)
+    have = np.zeros(n, np.int64)
+    cur = np.zeros((4, n))
+    cnt["rngDraws"] += 3
+    e_c, e_h, e_dir, e_w = np.zeros(n), np.full(n, 2 * EPS * xs), np.zeros(n), np.zeros(n)
+    cix = np.clip(np.searchsorted(xe, x, side="right") - 1, 0, nx - 1).astype(f64)
+    ciy = np.clip(np.searchsorted(ye, y, side="right") - 1, 0, ny - 1).astype(f64)
+    lay = np.full(n, min(int(np.searchsorted(ze, zstart, side="right") - 1), nz - 1))
+    alive = np.ones(n, bool)
+    pfi_ev = None
+    surface_z = float(f32(P.ze[0] + (np.spacing(np.abs(P.ze[0])) if P.ze[0] != 0 else f32(TINY))))   # z0 + spacing(z0)
+
+    while alive.any():
+        idx = np.nonzero(alive)[0]
+        dz = dvec[2, idx]
+        assert np.all(dz != 0.0)
+        adz = np.abs(dz)
+        up = dz > 0
+        Cz = np.interp(z[idx], ze, cumz)
+        Ct = Cz + np.where(up, 1.0, -1.0) * tau[idx] * adz
+        top, bottom = up & (Ct >= cumz[-1]), ~up & (Ct <= 0.0)
+        ev = ~(top | bottom)
+        lnew = np.where(up, np.searchsorted(cumz, Ct, side="right") - 1, np.searchsorted(cumz, Ct, side="left") - 1)
+        lnew = np.clip(lnew, 0, nz - 1)
+        znew = np.where(top, ze[-1], np.where(bottom, ze[0], ze[lnew] + (np.minimum(np.maximum(Ct, cumz[lnew]), cumz[lnew + 1]) - cumz[lnew]) / np.where(ext[lnew] > 0, ext[lnew], 1.0)))
+        s = (znew - z[idx]) / dz
+        tau_tr = np.abs(np.interp(znew, ze, cumz) - Cz) / adz
+        xu, yu = x[idx] + dvec[0, idx] * s, y[idx] + dvec[1, idx] * s
+        # (the column first with the error of the step before: the faces crossed enter the bound)
+        kx, ky = np.floor((xu - x0) / Lx), np.floor((yu - y0) / Ly)
+        ci0 = np.clip(np.searchsorted(xe, xu - kx * Lx, side="right") - 1, 0, nx - 1)
+        cj0 = np.clip(np.searchsorted(ye, yu - ky * Ly, side="right") - 1, 0, ny - 1)
+        nxy = np.abs(kx * nx + ci0 - cix[idx]) + np.abs(ky * ny + cj0 - ciy[idx])
+        steps = np.abs(lnew - lay[idx]) + nxy + 1
+        # (in the vertical optical-depth coordinate C: the start's error, the target's, the steps' roundings, the direction's)
+        e_ct = e_c[idx] + adz * (2 * ULP * tau[idx] + 3 * EPS * steps * tau_tr) + extmax * (nxy + 1) * EPS * (zs + 2 * dzmax) + tau_tr * e_dir[idx]
+        m_face = np.where(ev, np.minimum(Ct - cumz[lnew], cumz[lnew + 1] - Ct), np.where(top, Ct - cumz[-1], -Ct))
+        decide(idx, m_face, e_ct, "top / bottom / layer")
+        ext_new, ext_old = np.where(ext[lnew] > 0, ext[lnew], 1.0), np.where(ext[lay[idx]] > 0, ext[lay[idx]], 1.0)
+        e_cn = np.where(ev, e_ct + 4 * EPS * zs * ext_new, 0.0)
+        e_s = (e_cn / ext_new + e_c[idx] / ext_old) / adz + np.abs(s) * e_dir[idx] / adz
+        e_xy = e_h[idx] + np.abs(s) * e_dir[idx] + np.maximum(np.abs(dvec[0, idx]), np.abs(dvec[1, idx])) * e_s + steps * EPS * (xs + 2 * dxmax)
+        xw, yw, ci, cj, _ = column(idx, xu, yu, e_xy, "column")
+        x[idx], y[idx], z[idx] = xw, yw, znew
+        cix[idx], ciy[idx], lay[idx] = ci, cj, lnew
+        e_c[idx], e_h[idx] = e_cn, e_xy
+
+        # ---- exits through the top ------------------------------------------------------------------------------------------
+        t = idx[top]
+        np.add.at(T["fluxUp"], (cj[top], ci[top]), w[t])
+        np.add.at(Bd["fluxUp"], (cj[top], ci[top]), w[t] * e_w[t])
+        dep["fluxUp"][t] += w[t]
+        cnt["exitsTop"][t] += 1
+        fate[t], wfin[t], alive[t] = 0, w[t], False
+
+        # ---- the surface ----------------------------------------------------------------------------------------------------
+        b = idx[bottom]
+        if len(b):
+            np.add.at(T["fluxDown"], (cj[bottom], ci[bottom]), w[b])
+            np.add.at(Bd["fluxDown"], (cj[bottom], ci[bottom]), w[b] * e_w[b])
+            dep["fluxDown"][b] += w[b]
+            cnt["surfaceHits"][b] += 1
+            fate[b], wfin[b] = 1, w[b]
+            if black:
+                alive[b] = False
+            else:
+                u = roles(b, blk[b])
+                blk[b] += 1
+                cnt["rngDraws"][b] += 2
+                order[b] += 1
+                assert np.all(u[0] > 0.0), "a reflection's deviate of exactly 0 (the retry) is not modelled"
+                mu = np.sqrt(u[0].astype(f32)).astype(f32)                      # exact_sqrt
+                sinT = np.sqrt((f32(1.0) - (mu * mu).astype(f32)).astype(f32)).astype(f32).astype(f64)
+                turn = u[0] if variant == "azimuth from first" else u[1]
+                w[b] = w[b] * alb
+                e_w[b] += EPS
+                dead = w[b] <= TINY
+                alive[b[dead]] = False
+                g = b[~dead]
+                sg, tg = sinT[~dead], turn[~dead]
+                dvec[:, g] = np.array([sg * np.cos(2 * np.pi * tg), sg * np.sin(2 * np.pi * tg), mu[~dead].astype(f64)])
+                e_dir[g] = SINCOS * np.sqrt(2.0) * sg + 2 * EPS
+                z[g] = surface_z
+                lay[g] = 0
+                if nd:
+                    radiance(g, None, x[g], y[g], z[g], None, w[g], e_c[g], e_h[g], e_dir[g], e_w[g], order[g])
+                tau[g] = -np.log(np.maximum(TINY, u[2][~dead]))
+                cnt["rngDraws"][g] += 1
+
+        # ---- scatterings ----------------------------------------------------------------------------------------------------
+        e = idx[ev]
+        if len(e):
+            le, cie, cje = lnew[ev], ci[ev], cj[ev]
+            u = roles(e, blk[e])
+            blk[e] += 1
+            order[e] += 1
+            cnt["scatterings"][e] += 1
+            comp = np.ones(len(e), np.int64)
+            if ncomp > 1:
+                need = have[e] == 0
+                if need.any():
+                    r = e[need]
+                    words = philox(lo[r], hi[r], blk[r], 0, k0, k1)
+                    cur[:, r] = np.array([unit(v) for v in words])
+                    blk[r] += 1
+                    have[r] = 4
+                rc = cur[4 - have[e], e]
+                have[e] -= 1
+                cnt["rngDraws"][e] += 1
+                for k in range(ncomp - 1):
+                    comp += rc >= frac[k, le]
+                    decide(e, np.abs(rc - frac[k, le]) + np.where(rc == frac[k, le], 1.0, 0.0), np.zeros(len(e)), "component")
+            om = P.ssa[comp - 1, le].astype(f64)
+            pfi_ev = np.maximum(P.pfi[comp - 1, le], 1)
+            absorbing = om < 1.0
+            inc = np.where(absorbing, w[e] * (1.0 - om), 0.0)
+            np.add.at(T["volumeAbsorption"], (le, cje, cie), inc)
+            np.add.at(Bd["volumeAbsorption"], (le, cje, cie), inc * (e_w[e] + 2 * EPS))
+            dep["volumeAbsorption"][e] += inc
+            w[e] = np.where(absorbing, w[e] * om, w[e])
+            e_w[e] += np.where(absorbing, EPS, 0.0)
+            if nd:
+                radiance(e, comp, x[e], y[e], z[e], dvec[:, e], w[e], e_c[e], e_h[e], e_dir[e], e_w[e], order[e])
+            if P.roulette:
+                decide(e, np.abs(w[e] - 0.5), w[e] * e_w[e], "roulette")
+                play = w[e] < 0.5
+                cnt["roulette"][e[play]] += 1
+                cnt["rngDraws"][e[play]] += 1
+                decide(e[play], np.abs(u[3][play] - w[e][play]), (w[e] * e_w[e])[play], "roulette")
+                lost = play & (u[3] >= w[e])
+                w[e] = np.where(play, np.where(lost, 0.0, 1.0), w[e])
+                e_w[e] = np.where(play, 0.0, e_w[e])
+            dead = w[e] <= TINY
+            fate[e[dead]], wfin[e[dead]] = 2, 0.0
+            alive[e[dead]] = False
+            g, keep = e[~dead], ~dead
+            if len(g):
+                # scattering_cosine<false>, float32 operation by operation
+                # (refined_rcp(n) is v_rcp with one Newton step: the correctly rounded 1 / n or a neighbour.  The cosine is formed with
+                # all three; where they do not agree to the bit the kernel's may be either, one ulp apart)
+                r32 = u[0][keep].astype(f32)
+                cosS, unsure = np.zeros(len(g), f32), np.zeros(len(g), bool)
+                for c in range(1, ncomp + 1):
+                    sel = comp[keep] == c
+                    if not sel.any():
+                        continue
+                    tab = cosT[c - 1]
+                    nI = tab.shape[1]
+                    row = pfi_ev[keep][sel] - 1
+                    rr = r32[sel]
+                    k = (rr * f32(nI)).astype(f32).astype(np.int64) + 1
+                    inside = k < nI
+                    kk = np.minimum(k, nI - 1)
+                    shift = 1 if variant == "table interval k + 1" else 0
+                    a, bb = tab[row, np.minimum(kk - 1 + shift, nI - 1)], tab[row, np.minimum(kk + shift, nI - 1)]
+                    rcp = f32(f32(1.0) / f32(nI))
+                    vals = []
+                    for rn in (rcp, np.nextafter(rcp, f32(0)), np.nextafter(rcp, f32(1))):
+                        left = (rr - ((kk - 1).astype(f32) * rn).astype(f32)).astype(f32)
+                        val = (((f32(1.0) - left).astype(f32) * a).astype(f32) + (left * bb).astype(f32)).astype(f32)
+                        vals.append(np.where(inside, val, tab[row, nI - 1]))
+                    cosS[sel] = vals[0]
+                    unsure[sel] = (vals[1] != vals[0]) | (vals[2] != vals[0])
+                ysq = (f32(1.0) - (cosS * cosS).astype(f32)).astype(f32).astype(f64)
+                sinT = np.sqrt(np.maximum(ysq, 0.0))
+                cS = cosS.astype(f64)
+                turn = (u[0] if variant == "azimuth from first" else u[1])[keep]
+                sold = dvec[:, g]
+                decide(g, np.abs(sold[2]), e_dir[g], "frame")
+                snew = rotate(sold, cS, sinT, turn)
+                # the rotation's own gain at this event: finite differences along two tangents of the old direction
+                h = 1e-8
+                ref = np.where(np.abs(sold[0]) < 0.6, 1.0, 0.0)
+                axis = np.array([ref, 1.0 - ref, np.zeros(len(g))])
+                t1 = np.cross(sold.T, axis.T).T
+                t1 /= np.linalg.norm(t1, axis=0)
+                t2 = np.cross(sold.T, t1.T).T
+                ja, jb = (rotate(sold + h * t1, cS, sinT, turn) - snew) / h, (rotate(sold + h * t2, cS, sinT, turn) - snew) / h
+                aa, bb_, ab = (ja * ja).sum(0), (jb * jb).sum(0), (ja * jb).sum(0)
+                gain = np.sqrt(0.5 * (aa + bb_ + np.sqrt((aa - bb_) ** 2 + 4 * ab * ab)))   # largest singular value of (ja jb)
+                e_cos = np.where(unsure, np.minimum(ULP / np.maximum(sinT, 1e-300), np.sqrt(2 * ULP)), 0.0)
+                e_dir[g] = gain * e_dir[g] + e_cos + (SINCOS * np.sqrt(2.0) + 3 * ULP) * sinT + 10 * EPS
+                dvec[:, g] = snew
+                tau[g] = -np.log(np.maximum(TINY, u[2][keep]))
+                cnt["rngDraws"][g] += 3
+
+    T["fluxAbsorbed"] = T["volumeAbsorption"].sum(0)
+    Bd["fluxAbsorbed"] = Bd["volumeAbsorption"].sum(0)
+    dep["fluxAbsorbed"] = dep["volumeAbsorption"]
+    if nd == 0:
+        for k in ("intensity", "intensityExcess"):
+            T.pop(k), Bd.pop(k)
+    counters = {k: int(v.sum()) for k, v in cnt.items()}
+    counters.update(photons=n, dropped=0)
+    # what a fragile photon may carry into an entry other than the model's: its weight never exceeds 1, so 1 per tally it can make
+    # plus what the model itself has it deposit; a radiance contribution is at most max P / (4 pi min |mu_d|) (or the limit, or 1 / pi)
+    caps = {k: 1.0 + dep[k] for k in ("fluxUp", "fluxDown", "fluxAbsorbed", "volumeAbsorption")}
+    if nd:
+        cmax = max(max(float(t.max()) for t in P.fwd + P.fwd_orig) / (4 * np.pi * float(np.abs(P.dirs[:, 2]).min())), 1 / np.pi)
+        if P.max_contrib is not None:
+            cmax = min(cmax, float(P.max_contrib))
+        caps["intensity"] = dep["intensity"] + (order + 1) * cmax
+        caps["intensityExcess"] = caps["intensity"]
+    per = dict(fate=fate, order=order, weight=wfin, fragile=fragile, why=why, **{"n_" + k: v for k, v in cnt.items()})
+    return Result(n, T, Bd, counters, per, caps)
+
+
+def _rowwise(rows, theta):
+    """lookup_phase_fast with one table row per angle"""
+    nf = rows.shape[1]
+    rcp = float(f32(f32(nf - 1) * f32(f32(1.0) / PI32)))
+    pos = theta * rcp
+    k = pos.astype(np.int64) + 1
+    inside = k < nf
+    kk = np.minimum(k, nf - 1)
+    fr = pos - (kk - 1)
+    i = np.arange(len(theta))
+    return np.where(inside, (1.0 - fr) * rows[i, kk - 1] + fr * rows[i, kk], rows[i, nf - 1]), pos
+
+
+def clean_range(model):
+    """(first, count) of the longest run of consecutive photons of a run none of which is fragile: launched on its own, that range
+    must give the model's counters exactly and its tallies within the float32 bound alone"""
+    edges = np.concatenate([[-1], np.nonzero(model.per_photon["fragile"])[0], [model.n]])
+    k = int(np.argmax(np.diff(edges)))
+    return int(edges[k] + 1), int(edges[k + 1] - edges[k] - 1)
+
+
+COUNTERS_EXACT = ("photons", "dropped")
+COUNTERS_FRAGILE = ("scatterings", "surfaceHits", "exitsTop", "roulette", "rngDraws")
+
+
+def compare_counters(models, counters, names=COUNTERS_EXACT + COUNTERS_FRAGILE):
+    """counters (of one run, or summed over several) against the models' sums; the fragile photons' own counts are the allowance"""
+    miss = []
+    for k in names:
+        want = sum(m.counters[k] for m in models)
+        allow = 0 if k in COUNTERS_EXACT else sum(int(m.per_photon["n_" + k][m.per_photon["fragile"]].sum()) for m in models)
+        if abs(int(counters[k]) - want) > allow:
+            miss.append((k, int(counters[k]), want, allow))
+    return miss
+
+
+def compare(model, tallies, counters, counter_names=COUNTERS_EXACT + COUNTERS_FRAGILE):
+    """Hold another run's raw tallies (sums over photons, shaped as the model's) and counters against the model's.  Returns
+    (list of misses, {field: largest difference / its tolerance}); the caller asserts that the list is empty."""
+    frag = model.per_photon["fragile"]
+    miss, worst = compare_counters([model], counters, counter_names), {}
+    for k, want in model.tallies.items():
+        got = np.asarray(tallies[k], f64).reshape(want.shape)
+        slack = float(model.caps[k][frag].sum())
+        tol = model.bounds[k] + slack
+        diff = np.abs(got - want)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = np.where(diff > 0, diff / np.where(tol > 0, tol, TINY), 0.0)
+        worst[k] = float(ratio.max())
+        if worst[k] > 1.0:
+            at = np.unravel_index(int(ratio.argmax()), ratio.shape)
+            miss.append((k, at, float(got[at]), float(want[at]), float(tol[at])))
+    return miss, worst
+
+
+# ---- the shared cases ---------------------------------------------------------------------------------------------------------------
+# name -> dict(domain=..., tables=[per component (g of each table entry)], params) ; domains are 4 x 3 columns over layers with gaps
+def _layers(nz, z0, regular=True, seed=1):
+    if regular:
+        return (f32(z0) + f32(3.5) * np.arange(nz + 1, dtype=f32)).astype(f32)
+    rng = np.random.default_rng(seed)
+    return (f32(z0) + np.concatenate([[0.0], np.cumsum(rng.uniform(2, 5, nz))])).astype(f32)
+
+
+_XE, _YE = f32(120.0) * np.arange(5, dtype=f32), f32(150.0) * np.arange(4, dtype=f32)
+_XI, _YI = np.array([0, 70, 190, 300, 480], f32), np.array([0, 130, 210, 450], f32)
+
+
+def _case(ext, ssa, pfi, gs, ze, xe=_XE, ye=_YE, n=20_000, **kw):
+    return dict(xe=xe, ye=ye, ze=ze, ext=np.atleast_2d(np.asarray(ext, f32)), ssa=np.atleast_2d(np.asarray(ssa, f32)),
+                pfi=np.atleast_2d(np.asarray(pfi, np.int64)), gs=gs, n=n, params=kw)
+
+
+def _cases():
+    C = {}
+    e8 = np.array([0.04, 0.0, 0.06, 0.02, 0.0, 0.0, 0.05, 0.03], f32)      # optical depth 0.7 in 8 layers of 3.5 m, three of them empty:
+    # free paths are short beside the columns (120 m and more), so few photons come within their own error of a column's side
+    on = (e8 > 0)
+    C["a common"] = _case(e8, on * f32(1.0), on * 1, [(0.85,)], _layers(8, 6.0), albedo=0.3)
+    C["a absorbing"] = _case(e8, on * f32(0.9), on * 1, [(0.85,)], _layers(8, 6.0), albedo=0.3)
+    ssa_b = np.where(on, np.array([0.99, 0, 0.8, 0.95, 0, 0, 0.6, 1.0], f32), 0)
+    C["b records"] = _case(e8, ssa_b, on * np.array([1, 0, 2, 1, 0, 0, 2, 2]), [(0.85, 0.6)], _layers(8, 6.0), albedo=0.3)
+    gas = np.linspace(0.03, 0.02, 8, dtype=f32)
+    C["c two"] = _case([e8, gas], [on * f32(0.98), np.full(8, f32(0.6))], [on * np.array([1, 0, 2, 1, 0, 0, 2, 1]), np.ones(8)],
+                       [(0.85, 0.6), (0.0,)], _layers(8, 0.0, False), albedo=0.3)
+    aer = np.array([0.02, 0.02, 0.01, 0, 0, 0, 0, 0], f32)
+    C["d three"] = _case([e8, aer, gas], [on * f32(0.98), (aer > 0) * f32(0.92), np.full(8, f32(0.6))],
+                         [on * 1, (aer > 0) * 1, np.ones(8)], [(0.85,), (0.7,), (0.0,)], _layers(8, 0.0, False), albedo=0.3)
+    C["e irregular"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), xe=_XI, ye=_YI, albedo=0.3)
+    C["f no roulette"] = _case(e8, on * f32(0.4), on * 1, [(0.6,)], _layers(8, 6.0), albedo=0.3, roulette=False)
+    C["f roulette"] = _case(e8, on * f32(0.4), on * 1, [(0.6,)], _layers(8, 6.0), albedo=0.3, roulette=True)
+    C["g black"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), albedo=0.0)
+    C["g white"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), albedo=1.0)
+    C["h one up"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), albedo=0.3, mus=[0.8], phis=[30.0], n=10_000)
+    C["h one down"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), albedo=0.3, mus=[-0.6], phis=[200.0], n=10_000)
+    C["h three"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), albedo=0.3, mus=[1.0, 0.7, -0.8], phis=[0.0, 120.0, 250.0], n=10_000)
+    C["h three two components"] = _case([e8, gas], [on * f32(0.98), np.full(8, f32(0.6))], [on * np.array([1, 0, 2, 1, 0, 0, 2, 1]), np.ones(8)],
+                                        [(0.85, 0.6), (0.0,)], _layers(8, 6.0), albedo=0.3, mus=[1.0, 0.8, -0.7], phis=[0.0, 120.0, 250.0], n=10_000)
+    C["h hybrid"] = _case(e8, on * f32(0.95), on * 1, [(0.95,)], _layers(8, 6.0), albedo=0.3, mus=[0.9], phis=[10.0], hybrid=1, n=10_000)
+    C["h limit"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), albedo=0.3, mus=[0.9, 0.4], phis=[10.0, 200.0], limit=0.5, n=10_000)
+    return C
+
+
+CASES = _cases()
+SUN = (0.7, 25.0)
+SEED = (23, 4)
+FRAGILE_CAP = 0.005
+
+
+def problem(case, inverse, forward=None, forward_orig=None, dirs=None):
+    """the model's problem for a shared case, with the tables (and directions) the host hands to the device"""
+    p = case["params"]
+    return Problem(case["xe"], case["ye"], case["ze"], case["ext"], case["ssa"], case["pfi"], inverse, mu0=SUN[0], azimuth=SUN[1],
+                   albedo=p["albedo"], roulette=p.get("roulette", True), dirs=dirs, fwd=forward, fwd_orig=forward_orig,
+                   hybrid=bool(p.get("hybrid")), orders_orig=int(p.get("hybrid", 0)), max_contrib=p.get("limit"))
+
+
+def case_directions(case):
+    p = case["params"]
+    return None if "mus" not in p else np.array([direction(m, ph) for m, ph in zip(p["mus"], p["phis"])], f32)
+
+
+# fragile photons / photons of every shared case at its size, seed SEED, photons from 0 (python -m tests.stream_model prints them)
+FRAGILE_SHARES = {
+    'a common': 0.0019,
+    'a absorbing': 0.0013,
+    'b records': 0.00135,
+    'c two': 0.00245,
+    'd three': 0.0028,
+    'e irregular': 0.00225,
+    'f no roulette': 0.00455,
+    'f roulette': 0.00025,
+    'g black': 0.0008,
+    'g white': 0.00435,
+    'h one up': 0.0027,
+    'h one down': 0.0029,
+    'h three': 0.0033,
+    'h three two components': 0.0047,
+    'h hybrid': 0.0032,
+    'h limit': 0.0031,
+}
+
+if __name__ == "__main__":
+    from tests.test_stream_model_cpu import model_for
+
+    for name in CASES:
+        r = model_for(name)
+        print(f"{name:26s} n {r.n:6d} fragile {r.fragile_share:.5f} {r.per_photon['why']} mean order {r.per_photon['order'].mean():.2f}")
