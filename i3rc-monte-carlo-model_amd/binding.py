@@ -28,6 +28,7 @@ SYMBOLS = [
     "i3rc_hip_launch_batch", "i3rc_hip_run_batches", "i3rc_hip_run_batches_moments", "i3rc_hip_get_moments_layout", "i3rc_hip_compute_batch", "i3rc_hip_expect_batches", "i3rc_hip_run_replay", "i3rc_hip_trace_rays", "i3rc_hip_synchronize",
     "i3rc_hip_fetch_tallies", "i3rc_hip_normalise", "i3rc_hip_last_kernel_ms", "i3rc_hip_kernel_ms_history", "i3rc_hip_set_tuning", "i3rc_hip_force_general_kernel", "i3rc_hip_select_kernel", "i3rc_hip_set_light_threshold", "i3rc_hip_set_launch_limit",
     "i3rc_hip_set_batch_fusion", "i3rc_hip_select_grid_place", "i3rc_hip_has_column_records", "i3rc_hip_column_records", "i3rc_hip_column_records_base", "i3rc_hip_lds_plan", "i3rc_hip_set_lds_tallies", "i3rc_hip_last_kernel_name", "i3rc_hip_last_plan", "i3rc_hip_timed_launch_count", "i3rc_hip_philox_blocks", "i3rc_hip_arith_check", "i3rc_hip_find_index", "i3rc_hip_surface_reflectance", "i3rc_hip_device_count", "i3rc_hip_version",
+    "i3rc_hip_set_level_fluxes", "i3rc_hip_get_level_flux_layout", "i3rc_hip_normalise_level_fluxes",
 ]
 
 
@@ -142,6 +143,10 @@ def load():
     if hasattr(L, "i3rc_hip_find_index"):
         L.i3rc_hip_find_index.argtypes = [H, C.c_int, fp, C.c_int64, fp, ip, ip]
         L.i3rc_hip_surface_reflectance.argtypes = [H, C.c_int64, fp, fp, fp]
+    if hasattr(L, "i3rc_hip_set_level_fluxes"):   # (absent from older builds loaded for A/B timing)
+        L.i3rc_hip_set_level_fluxes.argtypes = [H, C.c_int]
+        L.i3rc_hip_get_level_flux_layout.argtypes = [H, lp, lp, lp]
+        L.i3rc_hip_normalise_level_fluxes.argtypes = [H, dp, fp, fp]
     L.i3rc_hip_device_count.restype = C.c_int
     L.i3rc_hip_version.restype = C.c_char_p
     _lib = L

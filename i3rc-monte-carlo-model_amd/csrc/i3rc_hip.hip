@@ -105,6 +105,8 @@ struct i3rc_hip_integrator {
   int uniformPf = 0;         // ... and the phase-function entry every cell shares, else 0
 
   i3rc_tally_layout layout{};
+  bool levelFluxes = false;        // i3rc_hip_set_level_fluxes: plain flux launches also tally levelFluxUp / levelFluxDown ...
+  int64_t oLevelUp = -1, oLevelDown = -1;   // ... in a block behind the counters (offsets in float64 elements; -1: the feature is off)
   DevBuf ownTally;
   double *tally = nullptr;  // device pointer in use (own or bound)
   DevBuf workCounter;
@@ -215,6 +217,12 @@ static void compute_layout(i3rc_hip_integrator *h) {
   L.intensityByComponent = o; o += (int64_t)(h->ncomp + 1) * h->nDir * ncol;
   L.intensityExcess = o; o += (int64_t)(h->ncomp + 1) * h->nDir;
   L.counters = o; o += I3RC_NUM_COUNTERS;
+  // level fluxes (while switched on): behind everything else, so that no other offset moves -- where the kernels look for it too
+  h->oLevelUp = h->oLevelDown = -1;
+  if (h->levelFluxes) {
+    h->oLevelUp = level_block_offset(L.counters); o = h->oLevelUp + (int64_t)(h->nz + 1) * ncol;
+    h->oLevelDown = o; o += (int64_t)(h->nz + 1) * ncol;
+  }
   L.total = o;
 }
 
@@ -655,6 +663,29 @@ int i3rc_hip_zero_tallies(i3rc_hip_integrator *h) {
   return 0;
 }
 
+int i3rc_hip_set_level_fluxes(i3rc_hip_integrator *h, int on) {
+  if (!h) return 1;
+  drop_lookahead(h);
+  const bool want = on != 0;
+  if (want == h->levelFluxes) return 0;
+  // the tally layout changes: as for a change of nDir, a caller-bound buffer is refused before anything is touched
+  if (h->tally != (double *)h->ownTally.p)
+    return h->fail("i3rc_hip_set_level_fluxes: a caller-bound tally buffer is in use; unbind it (bind NULL) before switching level fluxes, "
+                   "then bind a buffer of the new layout's size");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // (launches in flight add to the buffer that is about to be replaced)
+  h->levelFluxes = want;
+  return realloc_tally(h);
+}
+
+int i3rc_hip_get_level_flux_layout(const i3rc_hip_integrator *h, int64_t *up, int64_t *down, int64_t *total) {
+  if (!h) return 1;
+  if (up) *up = h->oLevelUp;
+  if (down) *down = h->oLevelDown;
+  if (total) *total = h->layout.total;
+  return 0;
+}
+
 /* Tunables for experiments (not part of the reference API): event-phase ballot threshold, blocks per CU. */
 int i3rc_hip_set_tuning(i3rc_hip_integrator *h, int evThreshold, int blocksPerCU) {
   if (!h) return 1;
@@ -1069,7 +1100,8 @@ void record_plan(i3rc_hip_integrator *h, const LaunchPlan &plan, bool tableInLds
 
 template <class Rng>
 constexpr const char *rng_name() {
-  if constexpr (Rng::kReplay) return "ReplayStream";
+  if constexpr (LevelFluxes<Rng>::on) return "PhiloxLevelStream";
+  else if constexpr (Rng::kReplay) return "ReplayStream";
   else if constexpr (Rng::kBatched) return "PhiloxBatchStream";
   else return "PhiloxStream";
 }
@@ -1098,7 +1130,9 @@ template <class Rng>
 const std::vector<KernelEntry> &stream_kernels() {
   static const std::vector<KernelEntry> list = [] {
     std::vector<KernelEntry> v;
-    if constexpr (Rng::kBatched) {   // fused multi-batch launches
+    if constexpr (LevelFluxes<Rng>::on) {   // level fluxes: the general flux kernel, at every place
+      add<Rng, false, true, false, false, false>(v, AllPlaces{});
+    } else if constexpr (Rng::kBatched) {   // fused multi-batch launches
       add<Rng, false, false, false, false, false>(v, NoColbase{});   // flux, the common class
       add<Rng, false, false, false, false, true>(v, AllPlaces{});    // the widened class: flux, ...
       add<Rng, true, false, false, false, true>(v, AllPlaces{});     // ... radiance through the event ring, ...
@@ -1125,6 +1159,20 @@ const std::vector<KernelEntry> &stream_kernels() {
   return list;
 }
 
+// Level fluxes are tallied by the general flux kernel of a plain launch, traced: what a launch must be while they are switched on.
+// Called before a launch touches anything; `who` names the entry point in the error text.
+int level_fluxes_refused(i3rc_hip_integrator *h, const char *who) {
+  if (!h->levelFluxes) return 0;
+  if (h->nDir > 0) return h->fail(std::string(who) + ": level fluxes are tallied by flux launches only; radiance directions are set (nDir > 0)");
+  if (!h->params.useRayTracing) return h->fail(std::string(who) + ": level fluxes need ray tracing; max cross-section is in use (useRayTracing = 0)");
+  return 0;
+}
+int level_fluxes_refuse_batches(i3rc_hip_integrator *h, const char *who) {
+  if (!h->levelFluxes) return 0;
+  return h->fail(std::string(who) + ": level fluxes are tallied by plain launches only; fused or announced batches cannot give them "
+                                    "(switch them off, or call i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)");
+}
+
 struct KernelChoice {
   const KernelEntry *kern;   // nullptr: the stream has no instantiation for the key
   int threads;
@@ -1140,7 +1188,8 @@ KernelChoice choose_kernel(const i3rc_hip_integrator *h, const LaunchPlan &plan,
   const int place = plan.place;
   KernelKey key{plan.intensity, true, place, false, false, false};
   int threads = 256;
-  if constexpr (!Rng::kReplay) {   // (the replay build always runs the general kernel: it keeps the nested local estimate, no queue at all)
+  // (level fluxes: the general flux kernel whatever the problem's class -- the key as it stands)
+  if constexpr (!Rng::kReplay && !LevelFluxes<Rng>::on) {   // (the replay build always runs the general kernel: it keeps the nested local estimate, no queue at all)
     bool simple, wide;
     if (fused) {
       // the widened class (several components, irregular x / y, a gridded surface): its own fused kernels, flux ones too -- a driver's
@@ -1682,14 +1731,17 @@ void top_up_groups(i3rc_hip_integrator *h, uint32_t seed0, uint32_t nextIfNone, 
 // that a column's sum could leave the range where float32 still counts (2^24).  Per-photon random streams make a
 // long batch the same as several launches over consecutive photon ranges, so very long Directional batches are cut
 // into launches of at most 2^22 photons per compute unit (about 1e9 photons on an MI355X).
+int launch_levels(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt);   // (at the end of this file)
 int launch_batch_parts(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
   const int64_t perLaunch = h->launchLimit > 0 ? h->launchLimit : (int64_t)h->numCU << 22;
-  if (A.srcKind != 0) return launch<PhiloxStream>(h, plan, A, stream, timeIt);
+  // (level fluxes switched on: the same photons through photon_kernel<PhiloxLevelStream, ...>, see launch_levels)
+  const auto run = [&](const RunArgs &part) { return h->levelFluxes ? launch_levels(h, plan, part, stream, timeIt) : launch<PhiloxStream>(h, plan, part, stream, timeIt); };
+  if (A.srcKind != 0) return run(A);
   for (int64_t done = 0; done < A.nPhotons; done += perLaunch) {
     RunArgs part = A;
     part.firstPhoton = A.firstPhoton + done;
     part.nPhotons = std::min<int64_t>(perLaunch, A.nPhotons - done);
-    if (launch<PhiloxStream>(h, plan, part, stream, timeIt)) return 1;
+    if (run(part)) return 1;
   }
   return 0;
 }
@@ -1722,6 +1774,7 @@ int i3rc_hip_launch_batch(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1
   if (!h) return 1;
   if (!src) return h->fail("i3rc_hip_launch_batch: null source");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");  // illumination :78-79
+  if (level_fluxes_refused(h, "i3rc_hip_launch_batch")) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   LaunchPlan plan;
   if (make_problem(h, plan, h->stream, h->tally)) return 1;
@@ -1740,6 +1793,7 @@ int i3rc_hip_run_batches(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1,
   if (!src || !hostTallies || nBatches < 1) return h->fail("i3rc_hip_run_batches: bad arguments");
   if (src->kind != 0) return h->fail("i3rc_hip_run_batches: Directional photon streams only (explicit streams differ from batch to batch)");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
+  if (level_fluxes_refuse_batches(h, "i3rc_hip_run_batches")) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   if (fuse_loop(h, nPhotons, nBatches)) return run_batches_fused(h, seed0, seed1, nBatches, nPhotons, src, hostTallies);
   const int K = std::min(nBatches, inFlight <= 0 ? 6 : std::min(inFlight, (int)i3rc_hip_integrator::kMaxInFlight));
@@ -1784,6 +1838,7 @@ int i3rc_hip_run_batches_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_
   if (!src || !sum || !sumSquares || nBatches < 1) return h->fail("i3rc_hip_run_batches_moments: bad arguments");
   if (src->kind != 0) return h->fail("i3rc_hip_run_batches_moments: Directional photon streams only (explicit streams differ from batch to batch)");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
+  if (level_fluxes_refuse_batches(h, "i3rc_hip_run_batches_moments")) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   drop_lookahead(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1820,8 +1875,10 @@ int i3rc_hip_compute_batch(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed
   if (!src || !hostTallies) return h->fail("i3rc_hip_compute_batch: bad arguments");
   if (src->kind != 0) return h->fail("i3rc_hip_compute_batch: Directional photon streams only");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
+  if (level_fluxes_refused(h, "i3rc_hip_compute_batch")) return 1;
   HIPCHK(h, hipSetDevice(h->device));
-  const int depth = std::max(0, std::min(lookAhead, (int)i3rc_hip_integrator::kMaxInFlight - 1));
+  // (level fluxes switched on: no look-ahead -- one launch per call)
+  const int depth = h->levelFluxes ? 0 : std::max(0, std::min(lookAhead, (int)i3rc_hip_integrator::kMaxInFlight - 1));
   const size_t bytes = (size_t)h->layout.total * sizeof(double);
   if (reset_slots_if_layout_changed(h)) return 1;   // (a change of the layout has dropped the queue already: set_directions)
   auto free_slot = [&]() -> int {
@@ -1900,6 +1957,7 @@ int i3rc_hip_expect_batches(i3rc_hip_integrator *h, uint32_t seed0, uint32_t see
   if (!src || nBatches < 1) return h->fail("i3rc_hip_expect_batches: bad arguments");
   if (src->kind != 0) return h->fail("i3rc_hip_expect_batches: Directional photon streams only");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
+  if (level_fluxes_refuse_batches(h, "i3rc_hip_expect_batches")) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   drop_lookahead(h);
   if (!fuse_loop(h, nPhotons, nBatches)) return 0;   // (the caller goes on as it would have)
@@ -2189,4 +2247,32 @@ int i3rc_hip_normalise(const i3rc_hip_integrator *h, const double *t, float *flu
   return 0;
 }
 
+int i3rc_hip_normalise_level_fluxes(const i3rc_hip_integrator *h, const double *t, float *levelFluxUp, float *levelFluxDown) {
+  if (!h || !t) return 1;
+  if (!h->levelFluxes) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_level_fluxes: level fluxes are not switched on");
+  const size_t ncol = (size_t)h->nx * h->ny;
+  const double nPhot = t[h->layout.counters + I3RC_CNT_PHOTONS];
+  // photons per column, as i3rc_hip_normalise works them out for fluxUp (:353-367)
+  const double ax = (double)h->xE.back() - h->xE.front(), ay = (double)h->yE.back() - h->yE.front();
+  for (int j = 0; j < h->ny; ++j)
+    for (int i = 0; i < h->nx; ++i) {
+      const size_t k = (size_t)j * h->nx + i;
+      const double perCol = h->xyRegular ? nPhot / (double)ncol
+                                         : (((double)h->yE[j + 1] - h->yE[j]) * ((double)h->xE[i + 1] - h->xE[i])) / (ax * ay) * nPhot;
+      for (int lev = 0; lev <= h->nz; ++lev) {
+        if (levelFluxUp) levelFluxUp[(size_t)lev * ncol + k] = (float)(t[h->oLevelUp + (size_t)lev * ncol + k] / perCol);
+        if (levelFluxDown) levelFluxDown[(size_t)lev * ncol + k] = (float)(t[h->oLevelDown + (size_t)lev * ncol + k] / perCol);
+      }
+    }
+  return 0;
+}
+
 }  // extern "C"
+
+namespace {
+// The launch of photon_kernel<PhiloxLevelStream, ...> through the one path every plain launch takes (defined last, so that the level
+// kernels are instantiated behind every other kernel of the library).
+int launch_levels(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
+  return launch<PhiloxLevelStream>(h, plan, A, stream, timeIt);
+}
+}  // namespace

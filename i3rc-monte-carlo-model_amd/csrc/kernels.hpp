@@ -210,6 +210,56 @@ struct RngInit<ReplayStream> {
   template <class AR>
   static __device__ __forceinline__ void start(ReplayStream &g, const AR &A, long long i) { g.start(A.drawStart[i]); }
 };
+template <>
+struct RngInit<PhiloxLevelStream> : RngInit<PhiloxStream> {};
+
+// LEVEL FLUXES: upward and downward flux through every layer interface, per column (levelFluxUp / levelFluxDown [nz + 1][ny][nx],
+// level k = zEdges[k]).  photon_kernel<PhiloxLevelStream, false, true, GRID> -- the general flux kernel, the production stream under a
+// tag of its own -- tallies them at EVENT time from what the lane holds when its photon arrives: the weight (constant along the
+// straight segment just traced), the direction, the arrival position and the layer the segment began in (one more register).  The
+// tracer is not touched.  A segment from layer a to layer b (the tracer's own 1-based indices; nz + 1: out through the top, 0: onto
+// the surface) adds its weight to levelFluxUp[a ... b - 1] going up, to levelFluxDown[b ... a - 1] going down; a new photon is
+// counted at the face of its start layer that lies behind it, a reflected one at level 0, both in the tracer's own column.  The
+// block lies behind the counters of the packed tally buffer (level_block_offset) and is added to with float64 atomics in global
+// memory: no LDS carve-up changes.
+template <class Rng> struct LevelFluxes { static constexpr bool on = false; };
+template <> struct LevelFluxes<PhiloxLevelStream> { static constexpr bool on = true; };
+// offset of levelFluxUp in the packed tally buffer, levelFluxDown (nz + 1) * nx * ny words behind it -- the host's layout and the kernels' both
+__host__ __device__ inline long long level_block_offset(long long countersOffset) { return countersOffset + I3RC_NUM_COUNTERS; }
+
+// The crossings of one straight segment that arrived at (x, y, z) in column `colArr`, layer index `izTo`, from layer `izFrom` with
+// weight w.  The crossing point of level k is extrapolated BACK from the arrival along the direction and wrapped periodically with one
+// floor (a path may be many domain widths long); its column comes from find_xy.  That is float32 arithmetic on the segment's end, not
+// the tracer's own cell at that face: a crossing within rounding of a column's edge may be counted in the neighbouring column (the
+// level's total is exact either way).  The level the segment ENDS on -- the top for an exit, the surface for an arrival there -- takes
+// the tracer's own column, so that levelFluxUp[nz] and levelFluxDown[0] are fluxUp and fluxDown column by column.
+template <class PR>
+__device__ __forceinline__ void tally_level_crossings(const PR &P, const Lds &L, double *levelUp, float x, float y, float z, float dx, float dy, float dz,
+                                                      int izFrom, int izTo, int colArr, int ixArr, int iyArr, float w) {
+  const int nz = P.nz, ncol = P.nx * P.ny;
+  const bool up = dz > 0.0f;
+  int lo = up ? izFrom : izTo, hi = up ? izTo - 1 : izFrom - 1;
+  lo = lo < 0 ? 0 : lo; hi = hi > nz ? nz : hi;          // (never outside the block, whatever the indices)
+  double *const base = levelUp + (up ? 0 : (size_t)(nz + 1) * ncol);
+  const int endLevel = up ? nz : 0;                      // the level an exit / a surface arrival ends on
+  const bool endsOnBoundary = up ? izTo > nz : izTo < 1;
+  const float widthX = P.xMax - P.x0, widthY = P.yMax - P.y0;
+  for (int k = lo; k <= hi; ++k) {
+    int col = colArr;
+    if (!(endsOnBoundary && k == endLevel)) {
+      const float back = (z - L.zE[k]) / dz;             // (>= 0: the level lies behind the arrival)
+      float cx = x - dx * back, cy = y - dy * back;
+      cx = cx - floorf((cx - P.x0) / widthX) * widthX;
+      cy = cy - floorf((cy - P.y0) / widthY) * widthY;
+      cx = fminf(fmaxf(cx, P.x0), P.xMax); cy = fminf(fmaxf(cy, P.y0), P.yMax);   // (rounding at the walls; a NaN ends at x0: always a column of the grid)
+      int ix = ixArr, iy = iyArr;
+      find_xy<true>(P, L, cx, cy, ix, iy);
+      ix = ix < 1 ? 1 : (ix > P.nx ? P.nx : ix); iy = iy < 1 ? 1 : (iy > P.ny ? P.ny : iy);
+      col = (iy - 1) * P.nx + (ix - 1);
+    }
+    add_global(base + (size_t)k * ncol + col, w);
+  }
+}
 
 // Wave-private reservoir of photon indices: one returning atomic per `chunk` photons instead of one per respawn
 // round (the returning atomic costs microseconds; every wave would pay it in ~97 % of its event phases).  The two
@@ -433,6 +483,8 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   constexpr bool REPLAY = Rng::kReplay;        // per-photon fates are recorded by i3rc_hip_run_replay only
   constexpr bool BATCHED = Rng::kBatched;      // fused multi-batch launch: every lane knows its photon's batch (rng.batch)
   static_assert(!BATCHED || !GENERAL, "fused multi-batch launches: specialised kernels");
+  constexpr bool LEVELS = LevelFluxes<Rng>::on;   // level fluxes (PhiloxLevelStream): tallied by the general flux kernel only
+  static_assert(!LEVELS || (GENERAL && !INTENSITY && !TBL && !DIRECT && !MULTI), "level fluxes: the general flux kernel");
   static_assert(!MULTI || (!GENERAL && !TBL && !Rng::kReplay && (INTENSITY || BATCHED)), "MULTI: the widened class -- radiance kernels, and the fused flux kernels (plain flux launches of the class run the general flux kernel)");
   // Work counters of a fused launch.  Flux kernels: exact per batch, gathered per lane (below).  Radiance kernels have no
   // vector register to spare for that: their counters stay per WAVE and are handed to the batch whose photons the wave was
@@ -467,6 +519,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   float w = 0.0f;
   int order = 0;
   int st = ST_NEW;
+  int izFrom = 1;                     // LEVELS: the layer the photon's current segment began in
   // Absorption where the tally goes to global memory: what a photon's CONSECUTIVE scatterings in one cell add to it leaves as one
   // atomic -- when the next scattering lies in another cell, or the photon ends (so that a fused launch's lane never holds a sum of
   // another batch's block).  In clouds whose cells are optically thick (an LES field: 55 m cells, free paths of 10 m) a photon is
@@ -968,6 +1021,14 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       const bool atTop = isEv && r.z >= Pe.zMax;                           // :499-514
       const bool atSurface = isEv && !atTop && r.z <= surfaceZ;           // :515-531
       const bool atBlack = atSurface && blackSurface;                     // ... and :560-562
+      if constexpr (LEVELS) {
+        // the segment that has just ended crosses every level between the layer it began in and the one it arrived in (a dropped
+        // photon's segment tallies nothing).  The layers are the tracer's; an arrival that the tests above take for the top or the
+        // surface ends on that level, so that levelFluxUp[nz] / levelFluxDown[0] get what fluxUp / fluxDown get below.
+        if (isEv)
+          tally_level_crossings(Pe, L, tally.base() + level_block_offset(Pe.oCnt), r.x, r.y, atTop ? Pe.zMax : r.z, r.dx, r.dy, r.dz, izFrom,
+                                atTop ? Pe.nz + 1 : (atSurface ? 0 : r.iz), (r.iy - 1) * Pe.nx + (r.ix - 1), r.ix, r.iy, w);
+      }
       wc.dropped += count_lanes(dropped);
       wc.top += count_lanes(atTop);
       wc.surf += count_lanes(atSurface);
@@ -1101,6 +1162,11 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
             find_xy<true>(Pe, L, r.x, r.y, r.ix, r.iy);   // (the general kernels, and the several-components ones on an irregular x / y grid)
             find_z<true>(Pe, L, r.z, r.iz);
           }
+          if constexpr (LEVELS) {   // a new photon is counted at the face of its start layer that lies behind it (a source at the top: level nz, downward)
+            const bool down = !(r.dz > 0.0f);
+            const int k = min(max(down ? r.iz : r.iz - 1, 0), Pe.nz), ncolL = Pe.nx * Pe.ny;
+            add_global(tally.base() + level_block_offset(Pe.oCnt) + (size_t)((down ? Pe.nz + 1 : 0) + k) * ncolL + ((r.iy - 1) * Pe.nx + (r.ix - 1)), w);
+          }
           st = ST_TRACE;
         }
         if (st == ST_EVENT) {
@@ -1133,6 +1199,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
               if (defer) { pendingShadow = true; wI = w; evInfo = EventInfo::kSurface; }
               else if (INTENSITY)
                 intensity_contribution<GRID>(Pe, L, rng, nested, w, r.x, r.y, r.z, r.ix, r.iy, r.iz, r.dx, r.dy, r.dz, 0, order);
+              if constexpr (LEVELS) add_global(tally.base() + level_block_offset(Pe.oCnt) + c2, w);   // levelFluxUp[0]: the reflected weight, where it was reflected
               st = ST_TRACE;
             }
           } else {                                                        // :581-689
@@ -1273,6 +1340,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           // build follows the reference's deviates with libm's logf)
           const float tau = REPLAY ? -sample_log(fmaxf(kTiny, rng.path())) : -fast_log(fmaxf(kTiny, rng.path()));
           r.acc = 0.0f; r.target = tau;
+          if constexpr (LEVELS) izFrom = min(max(r.iz, 1), Pe.nz);
           if (rayTracing) { startedTrace = true; r.set_direction(L); }
           else {                                                          // :494-496 max cross-section move
             r.x = make_periodic(r.x + r.dx * tau / Pe.maxExt, Pe.x0, Pe.xMax);

@@ -164,6 +164,10 @@ struct PhiloxStreamT {
 // (types of their own, not aliases: kernel names -- rocprofv3, tools/kernel_resources.py -- keep the plain form)
 struct PhiloxStream : PhiloxStreamT<false> {};
 struct PhiloxBatchStream : PhiloxStreamT<true> {};
+// The production stream once more, as a TAG: photon_kernel<PhiloxLevelStream, ...> draws what photon_kernel<PhiloxStream, ...> draws and
+// also tallies the upward and downward flux through every layer interface (kernels.hpp, LevelFluxes).  A stream type and not a template
+// parameter of the kernel: the kernel's parameter list, and with it every other instantiation's name, stays as it is.
+struct PhiloxLevelStream : PhiloxStream {};
 
 // Test stream: deviates come from a buffer (the reference's MT19937 floats); see i3rc_hip_run_replay.
 struct ReplayStream {

@@ -176,6 +176,26 @@ module i3rcHipInterface
       type(c_ptr), value         :: fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, intensity, intensityByComponent
       integer(c_int)             :: rc
     end function
+    function i3rc_hip_set_level_fluxes(h, on) bind(C, name = "i3rc_hip_set_level_fluxes") result(rc)
+      import
+      type(c_ptr), value    :: h
+      integer(c_int), value :: on
+      integer(c_int)        :: rc
+    end function
+    function i3rc_hip_get_level_flux_layout(h, up, down, total) bind(C, name = "i3rc_hip_get_level_flux_layout") result(rc)
+      import
+      type(c_ptr), value              :: h
+      integer(c_int64_t), intent(out) :: up, down, total       ! offsets in float64 elements (-1: switched off), the buffer's length
+      integer(c_int)                  :: rc
+    end function
+    function i3rc_hip_normalise_level_fluxes(h, host, levelFluxUp, levelFluxDown) &
+             bind(C, name = "i3rc_hip_normalise_level_fluxes") result(rc)
+      import
+      type(c_ptr), value         :: h
+      real(c_double), intent(in) :: host(*)
+      type(c_ptr), value         :: levelFluxUp, levelFluxDown   ! (nx, ny, nz + 1) each
+      integer(c_int)             :: rc
+    end function
     function i3rc_hip_device_count() bind(C, name = "i3rc_hip_device_count") result(n)
       import
       integer(c_int) :: n

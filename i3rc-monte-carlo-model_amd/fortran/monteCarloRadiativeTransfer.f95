@@ -55,6 +55,10 @@ module monteCarloRadiativeTransfer
     real, dimension(:, :),       pointer :: fluxUp => null(), fluxDown => null(), fluxAbsorbed => null()
     real, dimension(:, :, :),    pointer :: volumeAbsorption => null(), intensity => null()
     real, dimension(:, :, :, :), pointer :: intensityByComponent => null()
+    ! ... and, with specifyParameters(computeLevelFluxes = .true.), the upward and downward flux through every layer interface
+    ! (nx, ny, nz + 1): level k is the interface at zPosition(k), 1 the surface, nz + 1 the top (not in the reference)
+    logical :: computeLevelFluxes = .false.
+    real, dimension(:, :, :),    pointer :: levelFluxUp => null(), levelFluxDown => null()
     double precision :: photonsProcessed = 0.d0, photonsDropped = 0.d0
     ! raw tallies of the batches of the last computeRadiativeTransferBatches (one column per batch)
     real(c_double), dimension(:, :), pointer :: batchTallies => null()
@@ -155,7 +159,7 @@ contains
                                useHybridPhaseFunsForIntenCalcs, hybridPhaseFunWidth,   &
                                numOrdersOrigPhaseFunIntenCalcs,                        &
                                limitIntensityContributions, maxIntensityContribution,  &
-                               status)
+                               status, computeLevelFluxes)
     type(integrator),                   intent(inout) :: thisIntegrator
     real,                     optional, intent(in   ) :: surfaceAlbedo
     type(surfaceDescription), optional, intent(in   ) :: surfaceBDRF
@@ -170,6 +174,8 @@ contains
     logical,                  optional, intent(in   ) :: limitIntensityContributions
     real,                     optional, intent(in   ) :: maxIntensityContribution
     type(ErrorMessage),                 intent(inout) :: status
+    ! (not in the reference, hence behind status: level fluxes, see reportResults)
+    logical,                  optional, intent(in   ) :: computeLevelFluxes
     integer :: i, nDir, nx, ny, nc
     real, dimension(:),    pointer :: xs, ys
     real, dimension(:, :), pointer :: albedoGrid
@@ -316,6 +322,17 @@ contains
     end if
     if(.not. deviceCall(thisIntegrator, i3rc_hip_set_params(thisIntegrator%device, thisIntegrator%parameters), &
                         "specifyParameters", status)) return
+    if(present(computeLevelFluxes)) then
+      if(.not. deviceCall(thisIntegrator, i3rc_hip_set_level_fluxes(thisIntegrator%device, merge(1, 0, computeLevelFluxes)), &
+                          "specifyParameters", status)) return
+      if(associated(thisIntegrator%levelFluxUp)) deallocate(thisIntegrator%levelFluxUp, thisIntegrator%levelFluxDown)
+      if(computeLevelFluxes) then
+        allocate(thisIntegrator%levelFluxUp  (size(thisIntegrator%totalExt, 1), size(thisIntegrator%totalExt, 2), size(thisIntegrator%totalExt, 3) + 1), &
+                 thisIntegrator%levelFluxDown(size(thisIntegrator%totalExt, 1), size(thisIntegrator%totalExt, 2), size(thisIntegrator%totalExt, 3) + 1))
+        thisIntegrator%levelFluxUp = 0.; thisIntegrator%levelFluxDown = 0.
+      end if
+      thisIntegrator%computeLevelFluxes = computeLevelFluxes
+    end if
     call setStateToSuccess(status)
   end subroutine specifyParameters
 
@@ -551,6 +568,11 @@ contains
                     c_loc(thisIntegrator%fluxDown(1, 1)), c_loc(thisIntegrator%fluxAbsorbed(1, 1)),                        &
                     c_loc(thisIntegrator%volumeAbsorption(1, 1, 1)), pIntensity, pByComponent), caller, status)
     if(.not. ok) return
+    if(thisIntegrator%computeLevelFluxes) then
+      ok = deviceCall(thisIntegrator, i3rc_hip_normalise_level_fluxes(thisIntegrator%device, raw,                           &
+                      c_loc(thisIntegrator%levelFluxUp(1, 1, 1)), c_loc(thisIntegrator%levelFluxDown(1, 1, 1))), caller, status)
+      if(.not. ok) return
+    end if
     thisIntegrator%photonsProcessed = raw(layout%counters + 1 + I3RC_CNT_PHOTONS)
     thisIntegrator%photonsDropped   = raw(layout%counters + 1 + I3RC_CNT_DROPPED)
     thisIntegrator%resultsValid     = .true.
@@ -863,7 +885,7 @@ contains
   ! Reporting
   ! ------------------------------------------------------------------------------------------------
   subroutine reportResults(thisIntegrator, meanFluxUp, meanFluxDown, meanFluxAbsorbed, fluxUp, fluxDown, fluxAbsorbed, &
-                           absorbedProfile, volumeAbsorption, meanIntensity, intensity, status)
+                           absorbedProfile, volumeAbsorption, meanIntensity, intensity, status, levelFluxUp, levelFluxDown)
     type(integrator),                   intent(in   ) :: thisIntegrator
     real,                     optional, intent(  out) :: meanFluxUp, meanFluxDown, meanFluxAbsorbed
     real, dimension(:, :),    optional, intent(  out) :: fluxUp, fluxDown, fluxAbsorbed
@@ -872,6 +894,8 @@ contains
     real, dimension(:),       optional, intent(  out) :: meanIntensity
     real, dimension(:, :, :), optional, intent(  out) :: intensity
     type(ErrorMessage),                 intent(inout) :: status
+    ! (not in the reference, hence behind status) (nx, ny, nz + 1): level k is the interface at zPosition(k)
+    real, dimension(:, :, :), optional, intent(  out) :: levelFluxUp, levelFluxDown
     integer :: nColumns, d
 
     if(.not. associated(thisIntegrator%fluxUp)) then
@@ -924,6 +948,24 @@ contains
         call setStateToFailure(status, "reportResults: intensity array has wrong dimensions.")
       else
         intensity = thisIntegrator%intensity
+      end if
+    end if
+    if(present(levelFluxUp)) then
+      if(.not. associated(thisIntegrator%levelFluxUp)) then
+        call setStateToFailure(status, "reportResults: level flux information not available")
+      else if(any(shape(levelFluxUp) /= shape(thisIntegrator%levelFluxUp))) then
+        call setStateToFailure(status, "reportResults: levelFluxUp array is the wrong size")
+      else
+        levelFluxUp = thisIntegrator%levelFluxUp
+      end if
+    end if
+    if(present(levelFluxDown)) then
+      if(.not. associated(thisIntegrator%levelFluxDown)) then
+        call setStateToFailure(status, "reportResults: level flux information not available")
+      else if(any(shape(levelFluxDown) /= shape(thisIntegrator%levelFluxDown))) then
+        call setStateToFailure(status, "reportResults: levelFluxDown array is the wrong size")
+      else
+        levelFluxDown = thisIntegrator%levelFluxDown
       end if
     end if
     if(.not. stateIsFailure(status)) call setStateToSuccess(status)
@@ -987,6 +1029,14 @@ contains
       copy%intensity = original%intensity
       copy%intensityByComponent = original%intensityByComponent
     end if
+    if(original%computeLevelFluxes) then
+      ! (the switch alone, on the copy's own fresh tally buffer: no second pass through the parameters)
+      if(deviceCall(copy, i3rc_hip_set_level_fluxes(copy%device, 1), "copy_Integrator", status)) then
+        allocate(copy%levelFluxUp(nx, ny, nz + 1), copy%levelFluxDown(nx, ny, nz + 1))
+        copy%levelFluxUp = original%levelFluxUp; copy%levelFluxDown = original%levelFluxDown
+        copy%computeLevelFluxes = .true.
+      end if
+    end if
   end function copy_Integrator
 
   subroutine finalize_Integrator(thisIntegrator)
@@ -1019,6 +1069,8 @@ contains
     if(associated(thisIntegrator%intensityByComponent)) deallocate(thisIntegrator%intensityByComponent)
     if(associated(thisIntegrator%batchTallies))         deallocate(thisIntegrator%batchTallies)
     if(associated(thisIntegrator%momentSums))           deallocate(thisIntegrator%momentSums, thisIntegrator%momentSquares)
+    if(associated(thisIntegrator%levelFluxUp))          deallocate(thisIntegrator%levelFluxUp, thisIntegrator%levelFluxDown)
+    thisIntegrator%computeLevelFluxes = .false.
     thisIntegrator%readyToCompute = .false.; thisIntegrator%computeIntensity = .false.
     thisIntegrator%useSurfaceBDRF = .false.
   end subroutine finalize_Integrator

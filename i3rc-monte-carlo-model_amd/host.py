@@ -174,7 +174,7 @@ class Integrator:
                    "intensityPhis", "computeIntensity", "useRayTracing", "useRussianRoulette",
                    "useRussianRouletteForIntensity", "zetaMin", "useHybridPhaseFunsForIntenCalcs",
                    "hybridPhaseFunWidth", "numOrdersOrigPhaseFunIntenCalcs", "limitIntensityContributions",
-                   "maxIntensityContribution")
+                   "maxIntensityContribution", "computeLevelFluxes")
 
     def __init__(self, atmosphere, device=0):
         self._h = C.c_void_p()
@@ -203,6 +203,7 @@ class Integrator:
         self.hybridPhaseFunWidth = 7.0
         self.intensityDirections = np.zeros((0, 3), np.float32)
         self.computeIntensity = False
+        self.computeLevelFluxes = False
         self._inv_size = [0] * self.ncomp
         self._fwd_size = [0] * self.ncomp
         self._fwd_stale = True
@@ -302,6 +303,18 @@ class Integrator:
             self.intensityDirections = np.zeros((0, 3), np.float32)
             self.computeIntensity = False
         self._check(self._lib.i3rc_hip_set_params(self._h, C.byref(p)), "specifyParameters")
+        if "computeLevelFluxes" in kw:
+            # upward and downward flux through every layer interface (i3rc_hip_set_level_fluxes): not in the reference
+            self._check(self._lib.i3rc_hip_set_level_fluxes(self._h, int(bool(kw["computeLevelFluxes"]))), "specifyParameters")
+            self.computeLevelFluxes = bool(kw["computeLevelFluxes"])
+            self._results = None             # (the tally layout has changed)
+
+    def level_flux_layout(self):
+        """(offset of levelFluxUp, offset of levelFluxDown, total) of the packed tally buffer, in float64 elements; the offsets are -1
+        while level fluxes are off (i3rc_hip_get_level_flux_layout)."""
+        up, down, total = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.i3rc_hip_get_level_flux_layout(self._h, C.byref(up), C.byref(down), C.byref(total)), "level_flux_layout")
+        return up.value, down.value, total.value
 
     # -- tabulateInversePhaseFunctions :1809-1861, tabulateForwardPhaseFunctions :1863-1923
     def _ensure_tables(self):
@@ -386,6 +399,11 @@ class Integrator:
                     "computeRadiativeTransfer")
         if nd:
             res["intensity"], res["intensityByComponent"] = inten, byc
+        if self.computeLevelFluxes:
+            res["levelFluxUp"] = np.zeros((self.nz + 1, self.ny, self.nx), np.float32)
+            res["levelFluxDown"] = np.zeros((self.nz + 1, self.ny, self.nx), np.float32)
+            self._check(self._lib.i3rc_hip_normalise_level_fluxes(self._h, raw.ctypes.data_as(B.dp), pf(res["levelFluxUp"]),
+                                                                  pf(res["levelFluxDown"])), "computeRadiativeTransfer")
         cnt = raw[lay.counters:lay.counters + B.NUM_COUNTERS]
         res["counters"] = {k: float(cnt[i]) for i, k in enumerate(B.COUNTER_NAMES)}
         res["raw"] = raw
@@ -495,10 +513,14 @@ class Integrator:
         return ms
 
     # -- reportResults :711-826
-    def reportResults(self):
+    def reportResults(self, levelFluxUp=False, levelFluxDown=False):
+        """levelFluxUp / levelFluxDown = True ask for the level fluxes, (nz + 1, ny, nx) each, level k at zPosition[k] (the shell's optional
+        arguments of the same names): an error unless specifyParameters(computeLevelFluxes=True) came before the computation."""
         r = self._results
         if r is None:
             raise I3RCError("reportResults: no results available")
+        if (levelFluxUp or levelFluxDown) and "levelFluxUp" not in r:
+            raise I3RCError("reportResults: level fluxes weren't computed (specifyParameters: computeLevelFluxes)")
         ncol = r32(self.nx * self.ny)
         out = dict(meanFluxUp=r["fluxUp"].sum(dtype=np.float32) / ncol, meanFluxDown=r["fluxDown"].sum(dtype=np.float32) / ncol,
                    meanFluxAbsorbed=r["fluxAbsorbed"].sum(dtype=np.float32) / ncol,
@@ -508,6 +530,10 @@ class Integrator:
         if "intensity" in r:
             out["intensity"] = r["intensity"]
             out["meanIntensity"] = r["intensity"].sum(axis=(1, 2), dtype=np.float32) / ncol
+        if levelFluxUp:
+            out["levelFluxUp"] = r["levelFluxUp"]
+        if levelFluxDown:
+            out["levelFluxDown"] = r["levelFluxDown"]
         return out
 
     # -- test hooks

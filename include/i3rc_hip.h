@@ -140,6 +140,32 @@ int i3rc_hip_use_own_stream(i3rc_hip_integrator *h);
 /* computeRadiativeTransfer :296-309: zero all tallies and counters (asynchronous on the stream). */
 int i3rc_hip_zero_tallies(i3rc_hip_integrator *h);
 
+/* LEVEL FLUXES (not in the reference): with on != 0, plain flux launches (i3rc_hip_launch_batch, i3rc_hip_compute_batch) also tally
+ * the upward and the downward flux through every layer interface, per column: levelFluxUp / levelFluxDown [nz + 1][ny][nx], level k
+ * the interface at zEdges[k] (0: the surface, nz: the top), raw sums of photon weights like fluxUp.  A photon that travels between
+ * two events from layer a to layer b (the tracer's 1-based indices; nz + 1: out through the top, 0: onto the surface) adds the weight
+ * it has on that segment to levelFluxUp[a ... b - 1] going up, to levelFluxDown[b ... a - 1] going down; a new photon is counted at the
+ * face of its start layer that lies behind it (a source at the top: levelFluxDown[nz]), a reflected one with its weight after the
+ * reflection at levelFluxUp[0]; a segment that ends in a tracer error adds nothing.  So levelFluxUp[nz] is fluxUp and levelFluxDown[0]
+ * is fluxDown, and without the roulette the net flux into a layer is what the layer absorbs.  The column of a crossing is found from
+ * the segment's end, extrapolated back to the level and wrapped periodically: float32 arithmetic, not the tracer's own cell at
+ * that face.
+ * The two arrays form a block BEHIND the counters of the packed tally buffer: no offset of i3rc_tally_layout moves, layout.total
+ * grows by 2 (nz + 1) nx ny while the feature is on and is what it was once it is off again (zeroing, fetching, binding and an
+ * all-reduce of the packed buffer cover the block).  Switching reallocates the handle's own buffer (cleared); with a caller-bound
+ * buffer in use it is refused.  Off by default: nothing changes then.
+ * While the feature is on, a launch runs photon_kernel<PhiloxLevelStream, false, true, GRID> -- the general flux kernel's photons,
+ * counter for counter -- and is refused, before anything is touched, when radiance directions are set (nDir > 0) or max cross-section
+ * is in use (useRayTracing = 0); i3rc_hip_run_batches, i3rc_hip_run_batches_moments and i3rc_hip_expect_batches are refused;
+ * i3rc_hip_compute_batch does not look ahead.  The replay hook ignores the feature. */
+int i3rc_hip_set_level_fluxes(i3rc_hip_integrator *h, int on);
+/* Offsets (float64 elements) of levelFluxUp and levelFluxDown in the packed buffer, -1 each while the feature is off, and the
+ * buffer's total (= layout.total).  Any of the three may be NULL. */
+int i3rc_hip_get_level_flux_layout(const i3rc_hip_integrator *h, int64_t *up, int64_t *down, int64_t *total);
+/* fluxUp's normalisation (i3rc_hip_normalise: per column, divided by the photons per column, float64 rounded to float32) of a host
+ * copy of the packed tallies: levelFluxUp / levelFluxDown [nz + 1][ny][nx] (either may be NULL).  Fails while the feature is off. */
+int i3rc_hip_normalise_level_fluxes(const i3rc_hip_integrator *h, const double *hostTallies, float *levelFluxUp, float *levelFluxDown);
+
 /* ---- the hot path ---------------------------------------------------------------------------------- */
 
 /* computeRT (:400-707) for one batch of nPhotons, ASYNCHRONOUS on the handle's stream; tallies accumulate.
