@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "tally_block.hpp"
 
 using namespace i3rc;
 
@@ -75,7 +76,8 @@ struct DevBuf {
 struct i3rc_hip_integrator {
   int device = 0;
   int nx = 0, ny = 0, nz = 0, ncomp = 0;
-  std::vector<float> xE, yE, zE;  // host copies (normalisation, checks)
+  std::vector<float> xE, yE, zE;  // host copies (launch parameters, checks)
+  std::vector<double> areaFrac, layerDepth;   // what the normalisation needs of the grid (TallyView::areaFrac, ::dz), worked out once
   DevBuf dxE, dyE, dzE, dExt, dCum, dSsa, dPf;
   DevBuf dCellRec;               // two components: a scattering's reads of its cell as one 16-byte record (DevProblem::cellRec)
   DevBuf dExtBrick;              // totalExt in bricks of 32 cells (DevProblem::extBrick)
@@ -105,8 +107,8 @@ struct i3rc_hip_integrator {
   int uniformPf = 0;         // ... and the phase-function entry every cell shares, else 0
 
   i3rc_tally_layout layout{};
-  bool levelFluxes = false;        // i3rc_hip_set_level_fluxes: plain flux launches also tally levelFluxUp / levelFluxDown ...
-  int64_t oLevelUp = -1, oLevelDown = -1;   // ... in a block behind the counters (offsets in float64 elements; -1: the feature is off)
+  TallyView view{};                // the same block as the normalisation sees it (tally_block.hpp; compute_layout), over the host arrays above
+  bool levelFluxes = false;        // i3rc_hip_set_level_fluxes: plain flux launches also tally levelFluxUp / levelFluxDown (view.levelUp / .levelDown)
   DevBuf ownTally;
   double *tally = nullptr;  // device pointer in use (own or bound)
   DevBuf workCounter;
@@ -161,8 +163,8 @@ struct i3rc_hip_integrator {
   uint32_t aheadEnd = 0;           // ... this seed word (exclusive)
   int fusion = -1;                 // -1: automatic, 0: never fuse, 1: fuse whatever the batch size (i3rc_hip_set_batch_fusion)
   bool fusedAheadFailed = false;   // a fused group could not be launched ahead (memory): look ahead with single batches until the layout changes
-  // i3rc_hip_run_batches_moments: sums and sums of squares over a loop's batches, accumulated on the device (momArea / momDz: what
-  // the normalisation needs of the grid -- column area fractions, layer depths)
+  // i3rc_hip_run_batches_moments: sums and sums of squares over a loop's batches, accumulated on the device (momArea / momDz: the
+  // device copies of areaFrac / layerDepth)
   DevBuf momSum, momSq, momCounters, momArea, momDz;
 
   // XCD-aware photon order (launch): the sorted photon numbers and the slab bookkeeping of a launch, per stream (launches
@@ -217,13 +219,26 @@ static void compute_layout(i3rc_hip_integrator *h) {
   L.intensityByComponent = o; o += (int64_t)(h->ncomp + 1) * h->nDir * ncol;
   L.intensityExcess = o; o += (int64_t)(h->ncomp + 1) * h->nDir;
   L.counters = o; o += I3RC_NUM_COUNTERS;
+  TallyView &V = h->view;
+  V.fluxUp = L.fluxUp; V.fluxDown = L.fluxDown; V.fluxAbsorbed = L.fluxAbsorbed; V.volumeAbsorption = L.volumeAbsorption;
+  V.intensityByComponent = L.intensityByComponent; V.intensityExcess = L.intensityExcess; V.counters = L.counters;
   // level fluxes (while switched on): behind everything else, so that no other offset moves -- where the kernels look for it too
-  h->oLevelUp = h->oLevelDown = -1;
+  V.levelUp = V.levelDown = -1;
   if (h->levelFluxes) {
-    h->oLevelUp = level_block_offset(L.counters); o = h->oLevelUp + (int64_t)(h->nz + 1) * ncol;
-    h->oLevelDown = o; o += (int64_t)(h->nz + 1) * ncol;
+    V.levelUp = level_block_offset(L.counters); o = V.levelUp + (int64_t)(h->nz + 1) * ncol;
+    V.levelDown = o; o += (int64_t)(h->nz + 1) * ncol;
   }
   L.total = o;
+  V.nx = h->nx; V.ny = h->ny; V.nz = h->nz; V.ncomp = h->ncomp; V.nDir = h->nDir; V.xyRegular = h->xyRegular;
+  V.areaFrac = h->areaFrac.data(); V.dz = h->layerDepth.data();
+}
+
+// The handle's view as a call finds it: whether limited contributions are redistributed is a parameter (i3rc_hip_set_params), which
+// changes without the layout.
+static TallyView current_view(const i3rc_hip_integrator *h) {
+  TallyView V = h->view;
+  V.limitContrib = h->nDir > 0 && h->params.limitIntensityContributions;
+  return V;
 }
 
 static int realloc_tally(i3rc_hip_integrator *h) {
@@ -343,6 +358,8 @@ int i3rc_hip_create(i3rc_hip_integrator **out, int device, int nx, int ny, int n
   h->xE.assign(xEdges, xEdges + nx + 1);
   h->yE.assign(yEdges, yEdges + ny + 1);
   h->zE.assign(zEdges, zEdges + nz + 1);
+  h->layerDepth.resize((size_t)nz); h->areaFrac.resize((size_t)nx * ny);
+  grid_fractions(nx, ny, nz, xEdges, yEdges, zEdges, h->areaFrac.data(), h->layerDepth.data());
   const size_t ncell = (size_t)nx * ny * nz;
   CCHK(h->dxE.upload(xEdges, sizeof(float) * (nx + 1)));
   CCHK(h->dyE.upload(yEdges, sizeof(float) * (ny + 1)));
@@ -680,8 +697,8 @@ int i3rc_hip_set_level_fluxes(i3rc_hip_integrator *h, int on) {
 
 int i3rc_hip_get_level_flux_layout(const i3rc_hip_integrator *h, int64_t *up, int64_t *down, int64_t *total) {
   if (!h) return 1;
-  if (up) *up = h->oLevelUp;
-  if (down) *down = h->oLevelDown;
+  if (up) *up = h->view.levelUp;
+  if (down) *down = h->view.levelDown;
   if (total) *total = h->layout.total;
   return 0;
 }
@@ -957,9 +974,9 @@ int make_problem(i3rc_hip_integrator *h, LaunchPlan &plan, hipStream_t stream, d
   P.uniformSsa = h->uniformSsa; P.uniformPf = h->uniformPf;
   if (h->layout.total >= ((int64_t)1 << 31)) return h->fail("tally buffer too large (2^31 elements or more)");
   P.tally = tally;
-  P.oUp = (int)h->layout.fluxUp; P.oDown = (int)h->layout.fluxDown; P.oAbs = (int)h->layout.fluxAbsorbed;
-  P.oVol = (int)h->layout.volumeAbsorption; P.oInt = (int)h->layout.intensityByComponent;
-  P.oExc = (int)h->layout.intensityExcess; P.oCnt = (int)h->layout.counters;
+  const TallyView &V = h->view;
+  P.oUp = (int)V.fluxUp; P.oDown = (int)V.fluxDown; P.oAbs = (int)V.fluxAbsorbed; P.oVol = (int)V.volumeAbsorption;
+  P.oInt = (int)V.intensityByComponent; P.oExc = (int)V.intensityExcess; P.oCnt = (int)V.counters;
   const size_t ncol = (size_t)h->nx * h->ny, ncell = ncol * h->nz;
   size_t lds = sizeof(float) * ((h->nx + 1) + (h->ny + 1) + (h->nz + 1) + 3 * (size_t)h->nDir);
   // radiance runs: every wave's ring of local-estimate events (one record serves the nDir rays of an event) and its
@@ -1022,7 +1039,7 @@ int absorbed_columns(i3rc_hip_integrator *h, hipStream_t stream, double *blocks,
   for (int first = 0; first < nBlocks; first += 65535) {
     const int n = std::min(65535, nBlocks - first);
     hipLaunchKernelGGL(absorbed_columns_kernel, dim3((unsigned)((ncol + 255) / 256), (unsigned)n), dim3(256), 0, stream, blocks + (size_t)first * stride,
-                       stride, (int)h->layout.fluxAbsorbed, (int)h->layout.volumeAbsorption, ncol, h->nz);
+                       stride, (int)h->view.fluxAbsorbed, (int)h->view.volumeAbsorption, ncol, h->nz);
     HIPCHK(h, hipGetLastError());
   }
   return 0;
@@ -1353,56 +1370,36 @@ __global__ void __launch_bounds__(256) reduce_counters_kernel(const double *coun
 
 // ---- batch moments on the device (i3rc_hip_run_batches_moments) ---------------------------------------------------------
 // A driver only ever wants the first two moments over its batches of what reportResults hands out (monteCarloDriver.f95:
-// 300-321, reduced at :333-352): per batch the raw block is normalised exactly as i3rc_hip_normalise does it (:353-395, float64,
-// rounded to the reference's real(4)) and x, x^2 are added up per element -- the per-batch blocks never leave the device.
+// 300-321, reduced at :333-352): per batch the raw block is normalised by the rule of tally_block.hpp, which i3rc_hip_normalise follows too (:353-395,
+// float64, rounded to the reference's real(4)) and x, x^2 are added up per element -- the per-batch blocks never leave the device.
 struct MomentsDev {
-  // the raw tally block (offsets as in DevProblem) ...
-  int oUp, oDown, oAbs, oVol, oInt, oExc, oCnt;
-  int nx, ny, nz, ncomp, nDir, xyRegular, limitContrib;
-  const double *areaFrac;   // [ncol] irregular grids: column area / domain area (:358-366)
-  const double *dz;         // [nz] layer depths (:378-381)
+  TallyView raw;   // the raw tally block, over the device copies of its two arrays ...
   // ... and the moments block (i3rc_moments_layout)
   long long mUp, mDown, mAbs, mVol, mInt, mProfile, mMeanUp, mMeanDown, mMeanAbs, mMeanInt;
 };
-__device__ __forceinline__ double photons_per_column(const MomentsDev &M, const double *raw, int col) {
-  const double nPhot = raw[M.oCnt + I3RC_CNT_PHOTONS];
-  return M.xyRegular ? nPhot / (double)(M.nx * M.ny) : M.areaFrac[col] * nPhot;
-}
-// the radiance of column `col` in direction d as reportResults gives it: components summed, the excess of limited contributions
-// redistributed in proportion (:327-347; excessSums[(j * nDir + d)] = the sum over the columns of component j's field)
-__device__ __forceinline__ float normalised_intensity(const MomentsDev &M, const double *raw, const double *excessSums, int d, int col) {
-  const size_t ncol = (size_t)M.nx * M.ny;
-  double tot = 0.0;
-  for (int j = 0; j <= M.ncomp; ++j) tot += raw[M.oInt + ((size_t)j * M.nDir + d) * ncol + col];
-  if (M.limitContrib)
-    for (int j = 0; j <= M.ncomp; ++j) {
-      const double ex = raw[M.oExc + (size_t)j * M.nDir + d];
-      if (ex > 0.0) tot += (raw[M.oInt + ((size_t)j * M.nDir + d) * ncol + col] / excessSums[j * M.nDir + d]) * ex;
-    }
-  return (float)(tot / photons_per_column(M, raw, col));
-}
 // one normalised field value of a batch; e counts through fluxUp | fluxDown | fluxAbsorbed | volumeAbsorption | intensity
-__device__ __forceinline__ float normalised_value(const MomentsDev &M, const double *raw, const double *excessSums, long long e) {
-  const long long ncol = (long long)M.nx * M.ny, ncell = ncol * M.nz;
+__device__ __forceinline__ float moments_field_value(const TallyView &V, const double *raw, const double *excessSums, long long e) {
+  const long long ncol = (long long)V.nx * V.ny, ncell = ncol * V.nz;
   if (e < 3 * ncol) {
-    const int which = (int)(e / ncol), col = (int)(e - which * ncol);
-    const int o = which == 0 ? M.oUp : (which == 1 ? M.oDown : M.oAbs);
-    return (float)(raw[o + col] / photons_per_column(M, raw, col));
+    const int which = (int)(e / ncol);
+    const long long col = e - which * ncol;
+    return normalised_column_flux(V, raw, (which == 0 ? V.fluxUp : (which == 1 ? V.fluxDown : V.fluxAbsorbed)) + col, col);
   }
   e -= 3 * ncol;
   if (e < ncell) {
-    const int kz = (int)(e / ncol), col = (int)(e - kz * ncol);
-    return (float)(raw[M.oVol + e] / (photons_per_column(M, raw, col) * M.dz[kz]));
+    const int kz = (int)(e / ncol);
+    return normalised_volume_absorption(V, raw, kz, e - kz * ncol);
   }
   e -= ncell;
   const int d = (int)(e / ncol);
-  return normalised_intensity(M, raw, excessSums, d, (int)(e - d * ncol));
+  return normalised_intensity(V, raw, excessSums, d, e - d * ncol);
 }
 // excessSums[b][(j * nDir + d)] = sum over the columns of intensityByComponent(:, :, d, j) of batch b (one workgroup each)
 __global__ void __launch_bounds__(256) moments_excess_kernel(MomentsDev M, const double *blocks, long long stride, double *excessSums) {
-  const int per = (M.ncomp + 1) * M.nDir, b = blockIdx.x / per, jd = blockIdx.x - b * per;
-  const size_t ncol = (size_t)M.nx * M.ny;
-  const double *f = blocks + (size_t)b * stride + M.oInt + (size_t)jd * ncol;
+  const TallyView &V = M.raw;
+  const int per = (V.ncomp + 1) * V.nDir, b = blockIdx.x / per, jd = blockIdx.x - b * per;
+  const size_t ncol = (size_t)V.nx * V.ny;
+  const double *f = blocks + (size_t)b * stride + V.intensityByComponent + (size_t)jd * ncol;
   double v = 0.0;
   for (size_t k = threadIdx.x; k < ncol; k += 256) v += f[k];
   __shared__ double part[4];
@@ -1418,12 +1415,12 @@ __global__ void __launch_bounds__(256) moments_fields_kernel(MomentsDev M, const
                                                              long long nFields, double *sum, double *sumSq) {
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
   if (e >= nFields) return;
-  const int per = (M.ncomp + 1) * M.nDir;
+  const int per = (M.raw.ncomp + 1) * M.raw.nDir;
   const int perSlice = (count + (int)gridDim.y - 1) / (int)gridDim.y;
   const int b0 = (int)blockIdx.y * perSlice, b1 = min(count, b0 + perSlice);
   double s1 = 0.0, s2 = 0.0;
   for (int b = b0; b < b1; ++b) {
-    const double x = (double)normalised_value(M, blocks + (size_t)b * stride, excessSums + (size_t)b * per, e);
+    const double x = (double)moments_field_value(M.raw, blocks + (size_t)b * stride, excessSums + (size_t)b * per, e);
     s1 += x; s2 += x * x;
   }
   // (fields lie in the moments block in the order e counts them: fluxUp | fluxDown | fluxAbsorbed | volumeAbsorption | intensity)
@@ -1433,16 +1430,17 @@ __global__ void __launch_bounds__(256) moments_fields_kernel(MomentsDev M, const
 // domain means (:739-742), the absorption profile (:780) and the mean radiances: one workgroup per (batch, quantity)
 __global__ void __launch_bounds__(256) moments_means_kernel(MomentsDev M, const double *blocks, long long stride, const double *excessSums,
                                                             double *sum, double *sumSq, double *counterTotals) {
-  const int nq = 3 + M.nz + M.nDir, b = blockIdx.x / nq, q = blockIdx.x - b * nq;
+  const TallyView &V = M.raw;
+  const int nq = 3 + V.nz + V.nDir, b = blockIdx.x / nq, q = blockIdx.x - b * nq;
   const double *raw = blocks + (size_t)b * stride;
-  const int per = (M.ncomp + 1) * M.nDir;
-  const long long ncol = (long long)M.nx * M.ny;
-  long long first, at;   // first field element of the quantity (normalised_value's numbering) and its place in the moments block
+  const int per = (V.ncomp + 1) * V.nDir;
+  const long long ncol = (long long)V.nx * V.ny;
+  long long first, at;   // first field element of the quantity (moments_field_value's numbering) and its place in the moments block
   if (q < 3) { first = q * ncol; at = q == 0 ? M.mMeanUp : (q == 1 ? M.mMeanDown : M.mMeanAbs); }
-  else if (q < 3 + M.nz) { first = 3 * ncol + (long long)(q - 3) * ncol; at = M.mProfile + (q - 3); }
-  else { first = 3 * ncol + ncol * M.nz + (long long)(q - 3 - M.nz) * ncol; at = M.mMeanInt + (q - 3 - M.nz); }
+  else if (q < 3 + V.nz) { first = 3 * ncol + (long long)(q - 3) * ncol; at = M.mProfile + (q - 3); }
+  else { first = 3 * ncol + ncol * V.nz + (long long)(q - 3 - V.nz) * ncol; at = M.mMeanInt + (q - 3 - V.nz); }
   double v = 0.0;
-  for (long long k = threadIdx.x; k < ncol; k += 256) v += (double)normalised_value(M, raw, excessSums + (size_t)b * per, first + k);
+  for (long long k = threadIdx.x; k < ncol; k += 256) v += (double)moments_field_value(V, raw, excessSums + (size_t)b * per, first + k);
   __shared__ double part[4];
   v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
@@ -1452,7 +1450,7 @@ __global__ void __launch_bounds__(256) moments_means_kernel(MomentsDev M, const 
     unsafeAtomicAdd(sum + at, x);
     unsafeAtomicAdd(sumSq + at, x * x);
   }
-  if (q == 0 && threadIdx.x < I3RC_NUM_COUNTERS) unsafeAtomicAdd(counterTotals + threadIdx.x, raw[M.oCnt + threadIdx.x]);
+  if (q == 0 && threadIdx.x < I3RC_NUM_COUNTERS) unsafeAtomicAdd(counterTotals + threadIdx.x, raw[V.counters + threadIdx.x]);
 }
 
 // Do the batches of a driver's loop -- nBatches of nPhotons each -- share one grid, group by group (see FusedSlot)?  The specialised
@@ -1569,7 +1567,7 @@ int launch_fused_group(i3rc_hip_integrator *h, i3rc_hip_integrator::FusedSlot &g
   {
     const long long n = (long long)count * I3RC_NUM_COUNTERS;
     hipLaunchKernelGGL(reduce_counters_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g.stream, (const double *)g.counterBlocks.p,
-                       const_cast<double *>(result), (long long)count, (long long)h->layout.total, (int)h->layout.counters);
+                       const_cast<double *>(result), (long long)count, (long long)h->layout.total, (int)h->view.counters);
     HIPCHK(h, hipGetLastError());
   }
   if (moments) {
@@ -1607,14 +1605,8 @@ int begin_moments(i3rc_hip_integrator *h) {
   if (h->momSum.bytes != bytes) { HIPCHK(h, h->momSum.alloc(bytes)); HIPCHK(h, h->momSq.alloc(bytes)); }
   if (!h->momCounters.p) HIPCHK(h, h->momCounters.alloc(I3RC_NUM_COUNTERS * sizeof(double)));
   if (!h->momDz.p) {
-    std::vector<double> dz((size_t)h->nz), area((size_t)h->nx * h->ny);
-    for (int k = 0; k < h->nz; ++k) dz[k] = (double)h->zE[k + 1] - h->zE[k];
-    const double ax = (double)h->xE.back() - h->xE.front(), ay = (double)h->yE.back() - h->yE.front();
-    for (int j = 0; j < h->ny; ++j)
-      for (int i = 0; i < h->nx; ++i)
-        area[(size_t)j * h->nx + i] = (((double)h->yE[j + 1] - h->yE[j]) * ((double)h->xE[i + 1] - h->xE[i])) / (ax * ay);   // (as i3rc_hip_normalise)
-    HIPCHK(h, h->momDz.upload(dz.data(), dz.size() * sizeof(double)));
-    HIPCHK(h, h->momArea.upload(area.data(), area.size() * sizeof(double)));
+    HIPCHK(h, h->momDz.upload(h->layerDepth.data(), h->layerDepth.size() * sizeof(double)));
+    HIPCHK(h, h->momArea.upload(h->areaFrac.data(), h->areaFrac.size() * sizeof(double)));
   }
   HIPCHK(h, hipMemset(h->momSum.p, 0, bytes));
   HIPCHK(h, hipMemset(h->momSq.p, 0, bytes));
@@ -1628,17 +1620,13 @@ int accumulate_moments(i3rc_hip_integrator *h, hipStream_t stream, const double 
   i3rc_moments_layout L;
   moments_layout(h, L);
   MomentsDev M;
-  M.oUp = (int)h->layout.fluxUp; M.oDown = (int)h->layout.fluxDown; M.oAbs = (int)h->layout.fluxAbsorbed;
-  M.oVol = (int)h->layout.volumeAbsorption; M.oInt = (int)h->layout.intensityByComponent; M.oExc = (int)h->layout.intensityExcess;
-  M.oCnt = (int)h->layout.counters;
-  M.nx = h->nx; M.ny = h->ny; M.nz = h->nz; M.ncomp = h->ncomp; M.nDir = h->nDir; M.xyRegular = h->xyRegular;
-  M.limitContrib = h->nDir > 0 && h->params.limitIntensityContributions;
-  M.areaFrac = (const double *)h->momArea.p; M.dz = (const double *)h->momDz.p;
+  M.raw = current_view(h);
+  M.raw.areaFrac = (const double *)h->momArea.p; M.raw.dz = (const double *)h->momDz.p;
   M.mUp = L.fluxUp; M.mDown = L.fluxDown; M.mAbs = L.fluxAbsorbed; M.mVol = L.volumeAbsorption; M.mInt = L.intensity;
   M.mProfile = L.absorbedProfile; M.mMeanUp = L.meanFluxUp; M.mMeanDown = L.meanFluxDown; M.mMeanAbs = L.meanFluxAbsorbed; M.mMeanInt = L.meanIntensity;
   const long long stride = h->layout.total;
   const int per = (h->ncomp + 1) * h->nDir;
-  if (M.limitContrib) {
+  if (M.raw.limitContrib) {
     const size_t need = (size_t)count * per * sizeof(double);
     if (excess.bytes < need) HIPCHK(h, excess.alloc(need));
     hipLaunchKernelGGL(moments_excess_kernel, dim3((unsigned)(count * per)), dim3(256), 0, stream, M, blocks, stride, (double *)excess.p);
@@ -2186,63 +2174,30 @@ int i3rc_hip_last_plan(const i3rc_hip_integrator *h, int32_t *out, int n) {
 int i3rc_hip_normalise(const i3rc_hip_integrator *h, const double *t, float *fluxUp, float *fluxDown, float *fluxAbsorbed,
                        float *volumeAbsorption, float *intensity, float *intensityByComponent) {
   if (!h || !t) return 1;
-  const i3rc_tally_layout &L = h->layout;
+  const TallyView V = current_view(h);
   const size_t ncol = (size_t)h->nx * h->ny;
   const int nDir = h->nDir, ncomp = h->ncomp;
-  const double nPhot = t[L.counters + I3RC_CNT_PHOTONS];
-  // photons per column :353-367 (float64 here; the reference works in real(4))
-  std::vector<double> perCol(ncol);
-  if (h->xyRegular) {
-    for (size_t k = 0; k < ncol; ++k) perCol[k] = nPhot / (double)ncol;
-  } else {
-    const double ax = (double)h->xE.back() - h->xE.front(), ay = (double)h->yE.back() - h->yE.front();
-    for (int j = 0; j < h->ny; ++j)
-      for (int i = 0; i < h->nx; ++i)
-        perCol[(size_t)j * h->nx + i] = (((double)h->yE[j + 1] - h->yE[j]) * ((double)h->xE[i + 1] - h->xE[i])) / (ax * ay) * nPhot;
-  }
   for (size_t k = 0; k < ncol; ++k) {
-    if (fluxUp) fluxUp[k] = (float)(t[L.fluxUp + k] / perCol[k]);
-    if (fluxDown) fluxDown[k] = (float)(t[L.fluxDown + k] / perCol[k]);
-    if (fluxAbsorbed) fluxAbsorbed[k] = (float)(t[L.fluxAbsorbed + k] / perCol[k]);
+    if (fluxUp) fluxUp[k] = normalised_column_flux(V, t, V.fluxUp + k, k);
+    if (fluxDown) fluxDown[k] = normalised_column_flux(V, t, V.fluxDown + k, k);
+    if (fluxAbsorbed) fluxAbsorbed[k] = normalised_column_flux(V, t, V.fluxAbsorbed + k, k);
   }
   if (volumeAbsorption)
     for (int kz = 0; kz < h->nz; ++kz)
-      for (size_t k = 0; k < ncol; ++k)
-        volumeAbsorption[(size_t)kz * ncol + k] =
-            (float)(t[L.volumeAbsorption + (size_t)kz * ncol + k] / (perCol[k] * ((double)h->zE[kz + 1] - h->zE[kz])));
+      for (size_t k = 0; k < ncol; ++k) volumeAbsorption[(size_t)kz * ncol + k] = normalised_volume_absorption(V, t, kz, k);
   if (nDir > 0 && (intensity || intensityByComponent)) {
-    // intensity = sum over components (0 = surface) of intensityByComponent :574-579,:662-667
-    std::vector<double> byc((size_t)(ncomp + 1) * nDir * ncol), tot((size_t)nDir * ncol, 0.0);
-    for (size_t i = 0; i < byc.size(); ++i) byc[i] = t[L.intensityByComponent + i];
-    for (int j = 0; j <= ncomp; ++j)
-      for (size_t i = 0; i < (size_t)nDir * ncol; ++i) tot[i] += byc[(size_t)j * nDir * ncol + i];
-    if (h->params.limitIntensityContributions) {  // :327-347
-      for (int j = 0; j <= ncomp; ++j)
-        for (int d = 0; d < nDir; ++d) {
-          const double ex = t[L.intensityExcess + (size_t)j * nDir + d];
-          if (ex > 0.0) {
-            double *b = byc.data() + ((size_t)j * nDir + d) * ncol;
-            double s = 0.0;
-            for (size_t k = 0; k < ncol; ++k) s += b[k];
-            for (size_t k = 0; k < ncol; ++k) {
-              const double add = (b[k] / s) * ex;
-              tot[(size_t)d * ncol + k] += add;
-              b[k] += add;
-            }
-          }
-        }
-    }
-    if (intensity)
-      for (int d = 0; d < nDir; ++d)
-        for (size_t k = 0; k < ncol; ++k) intensity[(size_t)d * ncol + k] = (float)(tot[(size_t)d * ncol + k] / perCol[k]);
-    if (intensityByComponent)
-      for (int j = 0; j <= ncomp; ++j)
-        for (int d = 0; d < nDir; ++d)
-          for (size_t k = 0; k < ncol; ++k) {
-            const size_t o = ((size_t)j * nDir + d) * ncol + k;
-            // the reference leaves component 0 un-normalised (:390 loops j = 1:numComponents)
-            intensityByComponent[o] = (float)(j == 0 ? byc[o] : byc[o] / perCol[k]);
-          }
+    // the column sums the excess of limited contributions is shared out by (:327-347), added up column after column
+    std::vector<double> excessSums((size_t)(ncomp + 1) * nDir, 0.0);
+    if (V.limitContrib)
+      for (size_t jd = 0; jd < excessSums.size(); ++jd)
+        for (size_t k = 0; k < ncol; ++k) excessSums[jd] += t[V.intensityByComponent + jd * ncol + k];
+    for (int d = 0; d < nDir; ++d)
+      for (size_t k = 0; k < ncol; ++k) {
+        if (intensity) intensity[(size_t)d * ncol + k] = normalised_intensity(V, t, excessSums.data(), d, k);
+        if (intensityByComponent)
+          for (int j = 0; j <= ncomp; ++j)
+            intensityByComponent[((size_t)j * nDir + d) * ncol + k] = normalised_intensity_by_component(V, t, excessSums.data(), j, d, k);
+      }
   }
   return 0;
 }
@@ -2250,20 +2205,12 @@ int i3rc_hip_normalise(const i3rc_hip_integrator *h, const double *t, float *flu
 int i3rc_hip_normalise_level_fluxes(const i3rc_hip_integrator *h, const double *t, float *levelFluxUp, float *levelFluxDown) {
   if (!h || !t) return 1;
   if (!h->levelFluxes) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_level_fluxes: level fluxes are not switched on");
+  const TallyView &V = h->view;
   const size_t ncol = (size_t)h->nx * h->ny;
-  const double nPhot = t[h->layout.counters + I3RC_CNT_PHOTONS];
-  // photons per column, as i3rc_hip_normalise works them out for fluxUp (:353-367)
-  const double ax = (double)h->xE.back() - h->xE.front(), ay = (double)h->yE.back() - h->yE.front();
-  for (int j = 0; j < h->ny; ++j)
-    for (int i = 0; i < h->nx; ++i) {
-      const size_t k = (size_t)j * h->nx + i;
-      const double perCol = h->xyRegular ? nPhot / (double)ncol
-                                         : (((double)h->yE[j + 1] - h->yE[j]) * ((double)h->xE[i + 1] - h->xE[i])) / (ax * ay) * nPhot;
-      for (int lev = 0; lev <= h->nz; ++lev) {
-        if (levelFluxUp) levelFluxUp[(size_t)lev * ncol + k] = (float)(t[h->oLevelUp + (size_t)lev * ncol + k] / perCol);
-        if (levelFluxDown) levelFluxDown[(size_t)lev * ncol + k] = (float)(t[h->oLevelDown + (size_t)lev * ncol + k] / perCol);
-      }
-    }
+  for (size_t e = 0; e < (size_t)(h->nz + 1) * ncol; ++e) {   // (level after level, as the block is laid out)
+    if (levelFluxUp) levelFluxUp[e] = normalised_column_flux(V, t, V.levelUp + e, e % ncol);
+    if (levelFluxDown) levelFluxDown[e] = normalised_column_flux(V, t, V.levelDown + e, e % ncol);
+  }
   return 0;
 }
 

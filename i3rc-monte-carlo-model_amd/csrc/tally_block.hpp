@@ -1,0 +1,81 @@
+// One raw tally block -- where its fields lie, and the rule that turns its float64 sums into the real(4) fields reportResults
+// hands out (computeRadiativeTransfer :327-395) -- stated once for the host (i3rc_hip_normalise, i3rc_hip_normalise_level_fluxes)
+// and for the kernels (the batch moments).  The library is built with -ffp-contract=off, so both sides round alike.
+// Plain C++17: no HIP header is needed (a host compiler alone builds tests/normalise_main.cpp against it).
+#pragma once
+
+#include "../../include/i3rc_hip.h"
+
+#if defined(__HIP__) || defined(__HIPCC__)
+#define I3RC_TALLY_FN __host__ __device__ __forceinline__
+#else
+#define I3RC_TALLY_FN inline
+#endif
+
+namespace i3rc {
+
+// Passed by value, also as a kernel argument; the two arrays are host memory on the host and device memory in a kernel.
+struct TallyView {
+  // offsets in float64 elements (i3rc_tally_layout; the level block lies behind the counters, -1 while it is switched off)
+  long long fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, intensityByComponent, intensityExcess, counters, levelUp, levelDown;
+  int nx, ny, nz, ncomp, nDir, xyRegular;
+  int limitContrib;         // the excess of limited radiance contributions is redistributed (:327-347)
+  const double *areaFrac;   // [nx * ny] column area / domain area (:358-366; read on irregular grids only)
+  const double *dz;         // [nz] layer depths (:378-381)
+};
+
+// What the rule needs of the grid, from its float32 edges: every column's share of the domain's area and every layer's depth.
+inline void grid_fractions(int nx, int ny, int nz, const float *xE, const float *yE, const float *zE, double *areaFrac, double *dz) {
+  for (int k = 0; k < nz; ++k) dz[k] = (double)zE[k + 1] - zE[k];
+  const double ax = (double)xE[nx] - xE[0], ay = (double)yE[ny] - yE[0];
+  for (int j = 0; j < ny; ++j)
+    for (int i = 0; i < nx; ++i) areaFrac[(long long)j * nx + i] = (((double)yE[j + 1] - yE[j]) * ((double)xE[i + 1] - xE[i])) / (ax * ay);
+}
+
+// photons per column :353-367 (float64 here; the reference works in real(4))
+I3RC_TALLY_FN double photons_per_column(const TallyView &V, const double *raw, long long col) {
+  const double nPhot = raw[V.counters + I3RC_CNT_PHOTONS];
+  return V.xyRegular ? nPhot / (double)(V.nx * V.ny) : V.areaFrac[col] * nPhot;
+}
+
+// fluxUp, fluxDown, fluxAbsorbed and the level fluxes (:368-376): `at` is the element's offset in the block, `col` its column
+I3RC_TALLY_FN float normalised_column_flux(const TallyView &V, const double *raw, long long at, long long col) {
+  return (float)(raw[at] / photons_per_column(V, raw, col));
+}
+
+I3RC_TALLY_FN float normalised_volume_absorption(const TallyView &V, const double *raw, int kz, long long col) {
+  const long long ncol = (long long)V.nx * V.ny;
+  return (float)(raw[V.volumeAbsorption + kz * ncol + col] / (photons_per_column(V, raw, col) * V.dz[kz]));
+}
+
+// What component j (0: the surface) adds to the column's radiance in direction d beyond its own sum: its share of the excess of
+// limited contributions, in proportion to the field (:327-347).  excessSums[j * nDir + d] = the sum over the columns of component j's
+// field in direction d; the caller forms it (the host sequentially, moments_excess_kernel in a tree).
+I3RC_TALLY_FN double excess_share(const TallyView &V, const double *raw, const double *excessSums, int j, int d, double own) {
+  const double ex = raw[V.intensityExcess + (long long)j * V.nDir + d];
+  return (own / excessSums[j * V.nDir + d]) * ex;
+}
+I3RC_TALLY_FN bool has_excess(const TallyView &V, const double *raw, int j, int d) {
+  return V.limitContrib && raw[V.intensityExcess + (long long)j * V.nDir + d] > 0.0;
+}
+
+// intensity = the sum over the components of intensityByComponent (:574-579, :662-667), then the excess, then per photon of the column
+I3RC_TALLY_FN float normalised_intensity(const TallyView &V, const double *raw, const double *excessSums, int d, long long col) {
+  const long long ncol = (long long)V.nx * V.ny;
+  const double *f = raw + V.intensityByComponent + d * ncol + col;
+  double tot = 0.0;
+  for (int j = 0; j <= V.ncomp; ++j) tot += f[(long long)j * V.nDir * ncol];
+  for (int j = 0; j <= V.ncomp; ++j)
+    if (has_excess(V, raw, j, d)) tot += excess_share(V, raw, excessSums, j, d, f[(long long)j * V.nDir * ncol]);
+  return (float)(tot / photons_per_column(V, raw, col));
+}
+
+// (the reference leaves component 0 un-normalised: :390 loops j = 1:numComponents)
+I3RC_TALLY_FN float normalised_intensity_by_component(const TallyView &V, const double *raw, const double *excessSums, int j, int d, long long col) {
+  const long long ncol = (long long)V.nx * V.ny;
+  double v = raw[V.intensityByComponent + ((long long)j * V.nDir + d) * ncol + col];
+  if (has_excess(V, raw, j, d)) v += excess_share(V, raw, excessSums, j, d, v);
+  return (float)(j == 0 ? v : v / photons_per_column(V, raw, col));
+}
+
+}  // namespace i3rc

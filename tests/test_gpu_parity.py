@@ -948,3 +948,36 @@ def test_batch_moments_on_the_device_equal_the_drivers_sums():
             assert np.allclose(s1[key], want1, rtol=tol, atol=1e-12), (what, key, np.abs(s1[key] - want1).max())
             assert np.allclose(s2[key], want2, rtol=2 * tol, atol=1e-12), (what, key)
         g.finalize_Integrator()
+
+
+@pytest.mark.parametrize("what", ["step cloud, regular grid, absorbing", "two components, one direction", "irregular grid, one direction"])
+def test_one_batchs_moments_are_the_hosts_normalisation_bit_for_bit(what):
+    """Host and kernels normalise a raw block by one statement of the rule (csrc/tally_block.hpp): the moments of ONE batch are that
+    batch's reportResults() fields exactly, s1 = float64(field) and s2 = s1 * s1 (a float32's square is exact in float64), for every
+    field whose sums run in the same order on both sides -- the fluxes, the volume absorption, and the radiances while contributions
+    are not limited (the excess column sum is a tree on the device).  The domain means and the profile keep the tolerances of
+    test_batch_moments_on_the_device_equal_the_drivers_sums.  (cases.two_component's edges are evenly spaced, so the third problem is
+    the one whose columns and layers differ in size: the area fractions and layer depths of the view.)"""
+    radiance = dict(useRussianRouletteForIntensity=True, zetaMin=0.3, intensityMus=[0.6], intensityPhis=[30.0], surfaceAlbedo=0.2)
+    if what.startswith("step cloud"):
+        g, n = make_gpu(cases.step_cloud(ssa=0.9, nlayers=8), hg_table(), surfaceAlbedo=0.3), 20000
+    elif what.startswith("irregular"):
+        d = cases.irregular_domain()
+        assert all(np.ptp(np.diff(d[k])) > 0.1 for k in ("xe", "ye", "ze"))
+        g, n = make_gpu(d, hg_table(), **radiance), 6000
+    else:
+        tables = [M.PhaseFunctionTable([M.henyey_greenstein(0.85, 32), M.henyey_greenstein(0.6, 16)]),
+                  M.PhaseFunctionTable([M.PhaseFunction(legendre=np.array([0.0, 0.1], np.float32))])]
+        g, n = make_gpu(cases.two_component(), tables, **radiance), 6000
+    s1, s2, cnt = g.computeRadiativeTransferBatchMoments((5, 3), 1, 0.7, 25.0, n)
+    assert cnt["photons"] == n
+    g._results, = g.computeRadiativeTransferBatches((5, 3), 1, 0.7, 25.0, n)
+    want = g.reportResults()
+    keys = ["fluxUp", "fluxDown", "fluxAbsorbed", "volumeAbsorption"] + (["intensity"] if "intensity" in want else [])
+    assert ("intensity" in keys) == (not what.startswith("step cloud"))
+    for key in keys:
+        assert want[key].dtype == np.float32 and np.any(want[key] != 0), (what, key)
+        x = np.float64(want[key])
+        assert np.array_equal(s1[key].view(np.uint64), x.view(np.uint64)), (what, key, np.abs(s1[key] - x).max())
+        assert np.array_equal(s2[key].view(np.uint64), (s1[key] * s1[key]).view(np.uint64)), (what, key)
+    g.finalize_Integrator()
