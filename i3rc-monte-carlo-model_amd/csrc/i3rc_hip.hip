@@ -182,8 +182,8 @@ struct i3rc_hip_integrator {
   int blocksPerCU = 0;  // 0 = from occupancy query
   int kernelVariant = I3RC_KERNEL_AUTO;  // test / tuning knob (i3rc_hip_select_kernel)
   std::string lastKernelName;            // kernel the most recent launch ran (i3rc_hip_last_kernel_name)
-  static constexpr int kPlanWords = 10;
-  int32_t lastPlan[kPlanWords] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // ... and its plan (i3rc_hip_last_plan)
+  static constexpr int kPlanWords = 12;
+  int32_t lastPlan[kPlanWords] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // ... and its plan (i3rc_hip_last_plan)
   int64_t launchLimit = 0;               // photons per kernel launch (i3rc_hip_set_launch_limit); 0 = numCU * 2^22
   std::string err;
 
@@ -831,15 +831,17 @@ int i3rc_hip_set_lds_tallies(i3rc_hip_integrator *h, int on) {
   return 0;
 }
 
-int i3rc_hip_lds_plan(const int32_t *q, int32_t *out) {
-  if (!q || !out) return 1;
+int i3rc_hip_lds_plan(const int32_t *q, int32_t *out) { return i3rc_hip_lds_plan_words(q, 17, out, 12); }
+
+int i3rc_hip_lds_plan_words(const int32_t *q, int nq, int32_t *out, int nout) {
+  if (!q || !out || nq < 17 || nout < 12) return 1;
   DevProblem P;
   std::memset(&P, 0, sizeof(P));
   P.nx = q[0]; P.ny = q[1]; P.nz = q[2]; P.ncomp = q[3]; P.nDir = q[4]; P.ldsTallies = q[5]; P.ldsIntensity = q[6];
   P.rayQueueCap = q[7]; P.clearNx = q[8]; P.clearShift = q[9]; P.ldsVolume = q[16];
-  const LdsPlan lp = lds_plan(P, q[10] != 0, q[11] != 0, q[12], q[13] != 0, q[14], q[15]);
-  const int v[12] = {lp.xE, lp.yE, lp.zE, lp.tallies, lp.dirCos, lp.dirTab, lp.queue, lp.tInt, lp.ext, lp.cosTab, lp.end, lp.tVol};
-  for (int k = 0; k < 12; ++k) out[k] = v[k];
+  const LdsPlan lp = lds_plan(P, q[10] != 0, q[11] != 0, q[12], q[13] != 0, q[14], q[15], nq > 17 && q[17] != 0);
+  const int v[13] = {lp.xE, lp.yE, lp.zE, lp.tallies, lp.dirCos, lp.dirTab, lp.queue, lp.tInt, lp.ext, lp.cosTab, lp.end, lp.tVol, lp.startStore};
+  for (int k = 0; k < std::min(nout, 13); ++k) out[k] = v[k];
   return 0;
 }
 
@@ -1048,11 +1050,15 @@ int absorbed_columns(i3rc_hip_integrator *h, hipStream_t stream, double *blocks,
 // Dynamic LDS of one launch: the end of the kernel's own carve-up (lds_plan, tracer.hpp -- the function photon_kernel sets its
 // pointers from), for the instantiation that is about to run.
 template <class Rng>
-size_t lds_bytes(const i3rc_hip_integrator *h, const LaunchPlan &plan, bool tableInLds) {
+size_t lds_bytes(const i3rc_hip_integrator *h, const LaunchPlan &plan, bool tableInLds, bool startStore) {
   const LdsPlan lp = lds_plan(plan.P, plan.intensity && !Rng::kReplay, direct_rays(h), plan.place, plan.intensity, tableInLds ? 16 : 4,
-                              tableInLds ? plan.P.comp0.nInv : 0);
+                              tableInLds ? plan.P.comp0.nInv : 0, startStore);
   return (sizeof(float) * (size_t)lp.end + 15) & ~(size_t)15;
 }
+// the waves' start stores in a workgroup of `threads` (photon_kernel, STORE; StartSlot, tracer.hpp)
+constexpr size_t start_store_bytes(int threads) { return sizeof(float) * kStartWords * kStartSlots * (size_t)(threads / 64); }
+// what a launch may allocate: a compute unit's LDS less the kernels' static LDS (kStaticLdsBytes, tracer.hpp: the store kernels use all of it)
+constexpr size_t kLdsLaunchMax = 160 * 1024 - kStaticLdsBytes;
 
 int upload_source(i3rc_hip_integrator *h, const i3rc_source *src, int64_t n, RunArgs &A) {
   A.srcKind = src->kind;
@@ -1107,11 +1113,12 @@ struct KernelEntry {
 };
 
 // what i3rc_hip_last_plan reports of a launch: recorded where lastKernelName is, from the values the launch goes on with
-void record_plan(i3rc_hip_integrator *h, const LaunchPlan &plan, bool tableInLds, size_t ldsBytes, int fusedBatches) {
+void record_plan(i3rc_hip_integrator *h, const LaunchPlan &plan, bool tableInLds, size_t ldsBytes, int fusedBatches, size_t startStoreBytes) {
   const DevProblem &P = plan.P;
   const int rec = P.cellRec == nullptr ? 0 : (h->ncomp == 1 ? 8 : (h->ncomp == 2 ? 16 : 32));
   const int32_t v[i3rc_hip_integrator::kPlanWords] = {P.ldsGrid ? 1 : 0, P.ldsTallies ? 1 : 0, P.ldsVolume ? 1 : 0, P.ldsIntensity ? 1 : 0,
-                                                      tableInLds ? 1 : 0, (int32_t)ldsBytes, h->absorbing ? 1 : 0, rec, fusedBatches, plan.place};
+                                                      tableInLds ? 1 : 0, (int32_t)ldsBytes, h->absorbing ? 1 : 0, rec, fusedBatches, plan.place,
+                                                      (int32_t)startStoreBytes, 0 /* the chunk: launch_grid, once it is known */};
   std::memcpy(h->lastPlan, v, sizeof(v));
 }
 
@@ -1194,6 +1201,7 @@ struct KernelChoice {
   const KernelEntry *kern;   // nullptr: the stream has no instantiation for the key
   int threads;
   bool tableInLds;
+  bool startStore;           // the kernel starts its photons from per-wave start stores in LDS (photon_kernel, STORE)
 };
 
 // Which kernel runs a launch (see photon_kernel).  Fused launches (PhiloxBatchStream) are made for the specialised problems only
@@ -1239,15 +1247,26 @@ KernelChoice choose_kernel(const i3rc_hip_integrator *h, const LaunchPlan &plan,
     static const int fusedPlaces = (int)env_int("I3RC_FUSED_TABLE_LDS_PLACES", 11);
     const bool placeOk = fused ? ((fusedPlaces >> place) & 1) && place != GRID_BRICKS
                                : ((plainPlaces >> place) & 1) && place != GRID_COLBASE && h->kernelVariant == I3RC_KERNEL_AUTO;
+    // (the 16 waves' start stores -- photon_kernel, STORE: 16 KB -- count: two workgroups of 1024 threads share a compute unit's 160 KB.
+    // A domain that had room for the table without them runs the 256-thread kernel of its place, as the domains just beyond it always did.)
+    const size_t tblStore = has_start_store<Rng>(plan.intensity, false, place, false) ? start_store_bytes(1024) : 0;
     if (tblOn && simple && !plan.intensity && placeOk && (plan.P.uniformPf >= 1 || h->nInvEntries[0] == 1) &&
-        plan.ldsBytes + sizeof(float) * (size_t)plan.P.comp0.nInv <= 79 * 1024) {
+        plan.ldsBytes + sizeof(float) * (size_t)plan.P.comp0.nInv + tblStore <= 79 * 1024) {
       key.tbl = true;
       threads = 1024;
     }
   }
+  // The start store comes on top of what make_problem has placed in LDS -- edges, tallies, the field: every domain keeps its place --
+  // and is part of the launch's allocation (lds_bytes).  Where that would go beyond a compute unit's LDS (edge vectors of some 154 KB or
+  // more: a column of 39 000 layers) the launch runs the general flux kernel, which has no store, instead of being refused.
+  bool startStore = has_start_store<Rng>(key.intensity, key.general, key.place, key.wide);
+  if (startStore && lds_bytes<Rng>(h, plan, key.tbl, true) > kLdsLaunchMax) {
+    key.general = true; key.tbl = false; threads = 256;
+    startStore = false;
+  }
   for (const KernelEntry &e : stream_kernels<Rng>())
-    if (e.key == key) return {&e, threads, key.tbl};
-  return {nullptr, threads, key.tbl};
+    if (e.key == key) return {&e, threads, key.tbl, startStore};
+  return {nullptr, threads, key.tbl, startStore};
 }
 
 // One grid of the kernel chosen for `plan` on `stream`: the LDS check, the record of the launch (lastKernelName, i3rc_hip_last_plan),
@@ -1257,13 +1276,13 @@ template <class Rng, class Prepare>
 int launch_grid(i3rc_hip_integrator *h, const LaunchPlan &plan, RunArgs &A, hipStream_t stream, int fusedBatches, bool timeIt, Prepare &&prepare) {
   const KernelChoice c = choose_kernel<Rng>(h, plan, A.srcKind);
   const int threads = c.threads;
-  const size_t ldsBytes = lds_bytes<Rng>(h, plan, c.tableInLds);
-  if (ldsBytes > 160 * 1024 - 256) return h->fail("the launch needs more LDS than a compute unit has");
+  const size_t ldsBytes = lds_bytes<Rng>(h, plan, c.tableInLds, c.startStore);
+  if (ldsBytes > kLdsLaunchMax) return h->fail("the launch needs more LDS than a compute unit has");
   if (!c.kern) return h->fail(Rng::kBatched ? "internal: no fused kernel for this problem at this place of the extinction field"
                                             : "internal: no kernel for this problem at this place of the extinction field");
   const void *fn = (const void *)c.kern->fn;
   h->lastKernelName = c.kern->name;
-  record_plan(h, plan, c.tableInLds, ldsBytes, fusedBatches);
+  record_plan(h, plan, c.tableInLds, ldsBytes, fusedBatches, c.startStore ? start_store_bytes(threads) : 0);
   int perCU = h->blocksPerCU;
   if (perCU <= 0) {
     int occ = 0;
@@ -1283,6 +1302,7 @@ int launch_grid(i3rc_hip_integrator *h, const LaunchPlan &plan, RunArgs &A, hipS
   const long long need = (photons + threads - 1) / threads;
   if (blocks > need) blocks = std::max(1ll, need);
   if (prepare(blocks, threads)) return 1;
+  h->lastPlan[i3rc_hip_integrator::kPlanWords - 1] = A.chunk;   // (photons -- fused launches: per chunk number -- a wave takes per visit of the work counter)
   const int slot = (int)(h->timedLaunches % i3rc_hip_integrator::kEventRing);
   if (timeIt) HIPCHK(h, hipEventRecord(h->evStart[slot], stream));
   {

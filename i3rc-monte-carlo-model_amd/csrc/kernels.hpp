@@ -409,6 +409,26 @@ constexpr int planned_waves() {
   if (Rng::kBatched && !TBL) return MULTI ? I3RC_FUSED_WAVES - 2 : I3RC_FUSED_WAVES;
   return I3RC_FLUX_WAVES;   // (the specialised flux kernels; the fused table-in-LDS ones: 1024 threads, two workgroups per CU)
 }
+// What a wave of a STORE kernel (below) needs only when it fills its start store, or where a lane takes a photon from it -- the start
+// layer, the reservoir's end, the count of its refills -- as four words of static LDS of the wave's own, instead of scalar registers
+// that the whole photon loop would carry (eight waves per SIMD leave each 96 of them, and the kernels want more: tests/test_build_isa.py).
+struct WaveStartState {
+  enum Word { kLayer = 0, kEndLo = 1, kEndHi = 2, kRefills = 3, kWords = 4 };
+  int *w = nullptr;
+  __device__ __forceinline__ void save_end(long long end) const { w[kEndLo] = (int)(unsigned)end; w[kEndHi] = (int)(end >> 32); }
+  __device__ __forceinline__ long long end() const {   // (wave-uniform: every lane reads the same words)
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane(w[kEndLo]), hi = (unsigned)__builtin_amdgcn_readfirstlane(w[kEndHi]);
+    return (long long)(((unsigned long long)hi << 32) | lo);
+  }
+};
+// Which instantiations start their photons a wavefront at a time from a per-wave START STORE in LDS (photon_kernel, part B of the event
+// phase; StartSlot, tracer.hpp): the specialised flux kernels of plain launches wherever photon numbers are handed out in order -- the
+// bricked kernels take theirs from the slab-sorted list and keep the start in the event phase, as every other kernel does.  A constant
+// of the instantiation, derived from its template arguments: the host sizes the launch's LDS by the same function.
+template <class Rng>
+constexpr bool has_start_store(bool intensity, bool general, int grid, bool multi) {
+  return !Rng::kReplay && !Rng::kBatched && !LevelFluxes<Rng>::on && !intensity && !general && !multi && grid != GRID_BRICKS;
+}
 // GENERAL = false is the specialisation for the common problem class -- regular grid, ray tracing, one component,
 // Lambertian albedo (no BRDF grid), Directional source, production RNG: the rare paths (grid searches, periodic
 // re-wrapping loops, max-cross-section moves, BRDF lookups, component selection) are compiled out, which shrinks the
@@ -434,10 +454,13 @@ __global__ void __launch_bounds__(TBL ? 1024 : 256, (planned_waves<Rng, INTENSIT
 photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const int lightThreshold) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   Lds L;
+  constexpr bool STORE = has_start_store<Rng>(INTENSITY, GENERAL, GRID, MULTI);   // photons start a wavefront at a time: part B of the event phase
+  lds_float *startSlots = nullptr;   // STORE: this wave's start store (StartSlot, tracer.hpp)
   {
     // (one carve-up for the kernel and for the host's allocation: lds_plan, tracer.hpp)
-    const LdsPlan lp = lds_plan(P, INTENSITY && !Rng::kReplay, DIRECT, GRID, INTENSITY, TBL ? 16 : 4, 0);
+    const LdsPlan lp = lds_plan(P, INTENSITY && !Rng::kReplay, DIRECT, GRID, INTENSITY, TBL ? 16 : 4, 0, STORE);
     lds_float *const base = (lds_float *)smem;
+    if constexpr (STORE) startSlots = base + lp.startStore + (threadIdx.x >> 6) * (kStartWords * kStartSlots);
     const int ncol = P.nx * P.ny;
     L.xE = base + lp.xE; L.yE = base + lp.yE; L.zE = base + lp.zE;
     L.tUp = (lds_tally *)(base + lp.tallies); L.tDown = L.tUp + ncol; L.tVol = (lds_tally *)(base + lp.tVol);
@@ -537,11 +560,24 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   constexpr bool SLABS = GRID == GRID_BRICKS && !Rng::kReplay;
   __shared__ int slabsTried[16];           // per wave (see Reservoir::refill_slabs; 16 waves in the 1024-thread instantiations)
   Reservoir res;
+  int startAvail = 0;                      // STORE: photons made and not yet handed out, the ones in front of res.next (wave-uniform)
   if constexpr (BATCHED) res.refill_batched();
   else if (SLABS && A.slabIds != nullptr) {
     if ((threadIdx.x & 63) == 0) slabsTried[threadIdx.x >> 6] = 0;
     res.refill_slabs(&slabsTried[threadIdx.x >> 6]);
   } else res.refill();
+  // STORE: what a wave needs only when it fills its start store, or where a lane takes a photon from it, lives in a few LDS words of
+  // the wave's own (WaveStartState); the words exist in the STORE instantiations alone.
+  WaveStartState startState;
+  if constexpr (STORE) {
+    __shared__ int startWords[16][WaveStartState::kWords];   // per wave (16 waves in the 1024-thread instantiations)
+    static_assert(sizeof(startWords) <= kStaticLdsBytes && sizeof(slabsTried) <= kStaticLdsBytes && !SLABS,
+                  "an instantiation's static LDS -- the start state or the slab round, never both -- is what the launch's LDS limit leaves room for");
+    startState.w = startWords[threadIdx.x >> 6];
+    startState.w[WaveStartState::kLayer] = izStart;
+    startState.w[WaveStartState::kRefills] = 0;
+    startState.save_end(res.end);
+  }
 
   // ---- BATCHED: work counters per batch --------------------------------------------------------------------------------
   // The wave's scalar counters (wc) cannot tell the batches of its lanes apart: they only steer the thresholds here.  What
@@ -637,7 +673,8 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
 #endif
   enum { R_EMPTY = 0, R_TRACE = 1, R_ENDED = 2 };
   // (the schedule's levels and their measurements: tuning.hpp)
-  constexpr int kTurnMin = Rng::kReplay ? 1 : I3RC_TURN_MIN, kTurnForce = Rng::kReplay ? 1 : I3RC_TURN_FORCE;
+  constexpr int kTurnMin = Rng::kReplay ? 1 : (STORE ? I3RC_STORE_TURN_MIN : I3RC_TURN_MIN);
+  constexpr int kTurnForce = Rng::kReplay ? 1 : (STORE ? I3RC_STORE_TURN_FORCE : I3RC_TURN_FORCE);
   constexpr int kExpandBatch = I3RC_EXPAND_BATCH;   // an expand phase runs when the ready buffer has room for this many rays
   constexpr int kDirectEnter = I3RC_DIRECT_ENTER, kDirectLeave = I3RC_DIRECT_LEAVE;   // DIRECT: the levels of ready / running rays at which a wave turns to its rays / back
   // (an event phase that would not fit -- possible when kDirectEnter is set above kDirectReady - 64 -- sends the wave to its rays first: wantSlots)
@@ -974,6 +1011,8 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
     // Closing a photon and starting the next one is a third of the event phase's instructions and in most event phases
     // two or three lanes need it: turnover lanes therefore sit out until kTurnMin of them have gathered (or kTurnForce
     // of them call for an event phase of their own, or nothing else is left to do).
+    // (The specialised flux kernels of plain launches make their photons' starts a wavefront at a time -- STORE, part B -- and a
+    // turnover lane there closes its photon and reads four words: their quorum is a pair of knobs of its own, tuning.hpp.)
     const bool wantScat = st == ST_EVENT;
     const bool wantTurn = st == ST_EXIT || st == ST_DROPPED || st == ST_NEW;
     const unsigned long long scMask = __ballot(wantScat), tuMask = __ballot(wantTurn);
@@ -1094,6 +1133,86 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
             else rng.start((uint64_t)(Ae.firstPhoton + mine), mineBatch);
           }
         }
+      } else if constexpr (STORE) {
+        // The specialised flux kernels: a Directional photon's start is its stream's block 0 and nothing else -- words 0 and 1 its
+        // position, word 2 its first optical depth; start layer and direction are the wave's.  Worked out where a lane turns over, that
+        // is a third of the event phase's instructions for the two or three lanes that need it.  Here the WAVE works it out, for the
+        // next photon numbers of its reservoir, all lanes at once (uniform control flow: this is part B), into its start store; a
+        // lane that turns over reads its photon's slot.  Photons are counted where they are handed to lanes.  The reservoir is refilled
+        // when it is EMPTY and more are wanted -- the other kernels refill as soon as it is short of a request, so the hand-overs
+        // (flush_counters at every fourth refill, adapt_thresholds at the others: the same rule, without the shadow-step term that is
+        // always zero here) fall at slightly other moments; they only schedule.  Only photons that exist are made: a launch ends with
+        // every slot taken.
+        if (newMask != 0ull) {
+          int need = __popcll(newMask);
+          int rank = lanes_below(newMask);
+          long long mine = -1;
+          for (;;) {   // (uniform: from the store; when that is short, a fill -- after a refill where the reservoir is empty -- and the rest)
+            const int take = need < startAvail ? need : startAvail;
+            if (isNew && mine < 0 && rank >= 0 && rank < take) {
+              mine = res.next - startAvail + rank;   // (the store holds the startAvail photons in front of res.next)
+              const StartSlot::Words s = StartSlot::load(startSlots + kStartWords * ((unsigned)mine & (unsigned)(kStartSlots - 1)));
+              r.x = s.x; r.y = s.y; r.ix = s.ix; r.iy = s.iy; r.target = s.depth;   // (the rest of the start: part C)
+            }
+            startAvail -= take;
+            wc.photons += (unsigned)take;                         // numPhotonsProcessed :459
+            need -= take; rank -= take;
+            if (need == 0) break;
+            long long end = startState.end();
+            if (res.next >= end) {
+              // (the other kernels' test: a reservoir that ends where the launch ends was the last one -- no further visit of the work counter)
+              if (end >= cold_args()->A.nPhotons) break;
+              const unsigned refilled = (unsigned)__builtin_amdgcn_readfirstlane(startState.w[WaveStartState::kRefills]) + 1u;
+              startState.w[WaveStartState::kRefills] = (int)refilled;
+              if ((refilled & 3u) == 0u || wc.steps > 0x40000000u) flush_counters();
+              else adapt_thresholds();
+              res.refill();
+              end = res.end;
+              startState.save_end(end);
+              if (res.next >= end) break;                         // (the launch has no photons left; end == nPhotons now)
+            }
+            // ---- the fill: one photon per lane, the operations of every other kernel's start (part C below) in their order.  A short
+            // last chunk makes fewer than kStartSlots photons: the lanes beyond them work on slots that are never handed out.
+            // (The problem's origin, extent and cell sizes are read where they are used, x and y one after the other: asked for all
+            // at once, beside the round keys, they cost the kernels four more spilled scalar registers.)
+            const long long left = end - res.next;
+            const int n = left < (long long)kStartSlots ? (int)left : kStartSlots;
+            {
+              const long long i = res.next + (long long)(threadIdx.x & 63);
+              const Philox4 o = rng.first_block_of((uint64_t)(cold_args()->A.firstPhoton + i));
+              const float px = u32_to_unit_float(o.v[0]);
+              float py = u32_to_unit_float(o.v[1]);
+#ifdef I3RC_EXPERIMENT_SLAB   // measurement only (tools/locality_experiment.py): all photons start in one eighth of the domain
+              py *= 0.125f;
+#endif
+              const float depth = -fast_log(fmaxf(kTiny, u32_to_unit_float(o.v[2])));
+              float x, y;
+              int ci, cj;
+              {   // findXYIndicies :1359-1369 with the division by the (uniform) cell size done by reciprocal
+                const auto &Px = cold_args()->P;
+                x = Px.x0 + px * (Px.xMax - Px.x0);
+                ci = min((int)exact_div(x - Px.x0, Px.deltaX, refined_rcp(Px.deltaX)) + 1, Px.nx);
+                if (fabsf(L.xE[ci] - x) < spacingf(x)) ci = ci + 1;
+                ci = ci == Px.nx + 1 ? 1 : ci;
+              }
+              {
+                const auto &Py = cold_args()->P;
+                y = Py.y0 + py * (Py.yMax - Py.y0);
+                cj = min((int)exact_div(y - Py.y0, Py.deltaY, refined_rcp(Py.deltaY)) + 1, Py.ny);
+                if (fabsf(L.yE[cj] - y) < spacingf(y)) cj = cj + 1;
+                cj = cj == Py.ny + 1 ? 1 : cj;
+              }
+              StartSlot::store(startSlots + kStartWords * ((unsigned)i & (unsigned)(kStartSlots - 1)), x, y, ci, cj, depth);
+            }
+            __builtin_amdgcn_wave_barrier();   // (the slots are read by other lanes of this wave: no reordering across the fill)
+            res.next += n;
+            startAvail = n;
+          }
+          if (isNew) {
+            if (mine < 0) st = ST_DONE;
+            else RngInit<Rng>::start(rng, Ae, mine);
+          }
+        }
       } else
       if (newMask != 0ull) {
         int need = __popcll(newMask);
@@ -1128,8 +1247,23 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       }
       // ---- part C: one random block per lane for this event, then the event itself
       bool didScatter = false, didRoulette = false, startedTrace = false;   // per-lane flags -> wave counters below
+      bool fromStore = false;                                               // STORE: this lane's photon starts here, from its slot
       if (wantEvent && st != ST_DONE) {
         rng.begin_event();
+        if constexpr (STORE) {
+          // (position, cell and optical depth came from the slot in part B; the block just made is the photon's block 0 once more -- the
+          // stream goes on with block 1 -- and its three deviates are counted here and at path() below)
+          if (st == ST_NEW) {
+            rng.count_draws(2u);
+            r.dx = Ae.solarDx; r.dy = Ae.solarDy; r.dz = Ae.solarDz;
+            order = 0;
+            w = 1.0f;
+            r.z = Pe.z0 + (1.0f - spacingf(1.0f)) * (Pe.zMax - Pe.z0);
+            r.iz = startState.w[WaveStartState::kLayer];
+            fromStore = true;
+            st = ST_TRACE;
+          }
+        } else
         if (st == ST_NEW) {                                               // :453-470
           float px, py, pz;
           if (directional) {   // newPhotonStream_Directional, Code/monteCarloIllumination.f95:91-99
@@ -1339,7 +1473,9 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           // (production streams: hardware log2, within 2 ulp -- an optical depth, not a trajectory's bit pattern; the replay
           // build follows the reference's deviates with libm's logf)
           const float tau = REPLAY ? -sample_log(fmaxf(kTiny, rng.path())) : -fast_log(fmaxf(kTiny, rng.path()));
-          r.acc = 0.0f; r.target = tau;
+          r.acc = 0.0f;
+          if constexpr (STORE) r.target = fromStore ? r.target : tau;   // (a new photon's depth is its slot's: the same word, the same logarithm)
+          else r.target = tau;
           if constexpr (LEVELS) izFrom = min(max(r.iz, 1), Pe.nz);
           if (rayTracing) { startedTrace = true; r.set_direction(L); }
           else {                                                          // :494-496 max cross-section move

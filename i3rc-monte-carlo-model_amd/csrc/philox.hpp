@@ -125,6 +125,13 @@ struct PhiloxStreamT {
     block++;
     return o;
   }
+  // Block 0 of ANOTHER photon's stream, this stream's key (handled as in make_block): what a wave that starts its photons a
+  // wavefront at a time works out for the photon numbers it is about to hand out (photon_kernel, STORE)
+  __device__ inline Philox4 first_block_of(uint64_t photon) const {
+    uint32_t s0 = k0, s1 = k1;
+    asm volatile("" : "+s"(s0), "+s"(s1));
+    return philox4x32_10((uint32_t)photon, (uint32_t)(photon >> 32), 0u, 0u, s0, BATCHED ? s1 + batch : s1);
+  }
   __device__ inline void begin_event() {
     const Philox4 o = make_block();
     e0 = o.v[0]; e1 = o.v[1]; e2 = o.v[2]; e3 = o.v[3];

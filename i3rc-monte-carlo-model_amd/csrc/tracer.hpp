@@ -253,6 +253,32 @@ constexpr int kReadyRays = 64;
 #endif
 constexpr int kDirectReady = I3RC_DIRECT_READY;   // ... of the one-direction radiance kernels, which have no event ring (photon_kernel, DIRECT): a power of two >= 128
 constexpr int kCounterReplicas = 64;   // fused multi-batch launches: copies of a batch's counter block (RunArgs::counterBlocks)
+// One slot of a wave's START STORE (photon_kernel, STORE: the specialised flux kernels start their photons a wavefront at a time): what a
+// Directional photon's first Philox block gives it -- start position, start cell, first optical depth.  A slot is four consecutive words
+// (one 128-bit read); the wave's store is a ring of kStartSlots slots, photon i of the launch in slot i mod kStartSlots.  The cell is
+// ONE word, ix | iy << 16: the edge vectors of a launch lie in LDS (make_problem refuses nx + ny + nz beyond about 39 000), so neither
+// index can reach 2^16.
+constexpr int kStartSlots = 64, kStartWords = 4;
+// The most STATIC LDS an instantiation of photon_kernel declares beside its dynamic carve-up: the store kernels' per-wave start state
+// (16 waves x 4 words = all of it), the bricked kernels' slab rounds (64 bytes).  A launch may allocate a compute unit's 160 KB less
+// this (i3rc_hip.hip, kLdsLaunchMax); photon_kernel asserts that its static arrays fit.
+constexpr int kStaticLdsBytes = 256;
+struct StartSlot {
+  enum Word { kX, kY, kCell, kDepth, kWords };
+  static_assert(kWords == kStartWords, "StartSlot names every word of a slot");
+  static constexpr int kIyShift = 16;
+  struct Words { float x, y; int ix, iy; float depth; };
+  static __device__ __forceinline__ void store(lds_float *slot, float x, float y, int ix, int iy, float depth) {
+    slot[kX] = x; slot[kY] = y; slot[kCell] = __int_as_float(ix | (iy << kIyShift)); slot[kDepth] = depth;
+  }
+  static __device__ __forceinline__ Words load(const lds_float *slot) {
+    Words w;
+    w.x = slot[kX]; w.y = slot[kY]; w.depth = slot[kDepth];
+    const int cell = __float_as_int(slot[kCell]);
+    w.ix = cell & ((1 << kIyShift) - 1); w.iy = (int)((unsigned)cell >> kIyShift);
+    return w;
+  }
+};
 
 // The carve-up of a workgroup's dynamic LDS, in WORDS from its start -- ONE function for both sides: photon_kernel sets its
 // pointers (Lds) from it, the host sizes the launch's allocation from it (i3rc_hip.hip, lds_bytes).  (Round 4 kept two copies of
@@ -261,9 +287,12 @@ constexpr int kCounterReplicas = 64;   // fused multi-batch launches: copies of 
 //   direct        ... of the one-direction form (photon_kernel, DIRECT)
 //   grid          GridPlace of the instantiation;  intensity: its INTENSITY (a bricked field's clear-air map: flux kernels only)
 //   waves         waves per workgroup;  tableWords: the inverse table's cosines behind everything else (TBL), else 0
-struct LdsPlan { int xE, yE, zE, tallies, dirCos, dirTab, queue, tInt, ext, cosTab, end, tVol; };
+//   startStore    the waves' start stores (photon_kernel, STORE), 16-byte aligned, in front of the table: kStartWords * kStartSlots words
+//                 a wave -- 4 KB of a 256-thread workgroup, 16 KB of a 1024-thread one
+struct LdsPlan { int xE, yE, zE, tallies, dirCos, dirTab, queue, tInt, ext, cosTab, end, tVol, startStore; };
 template <class PR>
-__host__ __device__ __attribute__((always_inline)) inline LdsPlan lds_plan(const PR &P, bool queues, bool direct, int grid, bool intensity, int waves, int tableWords) {
+__host__ __device__ __attribute__((always_inline)) inline LdsPlan lds_plan(const PR &P, bool queues, bool direct, int grid, bool intensity, int waves, int tableWords,
+                                                                           bool startStore = false) {
   LdsPlan o;
   int p = 0;
   o.xE = p; p += P.nx + 1;
@@ -289,6 +318,9 @@ __host__ __device__ __attribute__((always_inline)) inline LdsPlan lds_plan(const
   if (grid == 0 /* GRID_LDS */) p += ncol * P.nz;
   if (grid == 2 /* GRID_BRICKS */ && !intensity) p += P.clearNx * (((P.ny - 1) >> P.clearShift) + 1);   // (the clear-air map lives at Lds::ext)
   if (grid == 4 /* GRID_COLBASE */) p += P.nz;                                                           // (the base profile of the column records, likewise)
+  if (startStore) p = (p + 3) & ~3;            // (the 128-bit reads of a slot)
+  o.startStore = p;
+  if (startStore) p += waves * (kStartWords * kStartSlots);
   o.cosTab = p; p += tableWords;
   o.end = p;
   return o;

@@ -54,6 +54,17 @@
 #ifndef I3RC_TURN_FORCE
 #define I3RC_TURN_FORCE 12
 #endif
+// ... of the flux kernels that start their photons from a start store (photon_kernel, STORE): a turnover lane there reads four words
+// instead of working out its photon's start, so the quorum that kept that arithmetic from running at two or three lanes has less to
+// protect.  Measured (step cloud, 1e8 photons, ms per step, two runs each | Landsat-36): quorum 1 27.49 / 27.47 | 75.3 / 75.8; 2 27.17 / 27.17 |
+// 74.2 / 75.8; 2 with forced turnover 8 27.22 / 27.22 | 74.3 / 74.5; 1 with 6 27.43 / 27.44 | 76.1 / 77.6; 4 with 12 26.98 ... 27.05 | 74.0 / 74.4: the
+// other kernels' values stay the best -- the quorum saves the CLOSING of a photon at two or three lanes as well (profiles/r07_start_store.txt)
+#ifndef I3RC_STORE_TURN_MIN
+#define I3RC_STORE_TURN_MIN 4
+#endif
+#ifndef I3RC_STORE_TURN_FORCE
+#define I3RC_STORE_TURN_FORCE 12
+#endif
 #ifndef I3RC_PHOTON_STEP_AHEAD
 #define I3RC_PHOTON_STEP_AHEAD 64   /* off: measured -1.6 % (step cloud) ... +2.8 % (Landsat-36), -3 % on the radar field */
 #endif

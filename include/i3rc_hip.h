@@ -313,10 +313,11 @@ int64_t i3rc_hip_timed_launch_count(const i3rc_hip_integrator *h);
 const char *i3rc_hip_last_kernel_name(const i3rc_hip_integrator *h);
 
 /* Test hook: the plan of the most recent launch (recorded with i3rc_hip_last_kernel_name; reads state, decides nothing).
- * out[0 .. min(n, 10) - 1]: field in LDS, flux tallies in LDS, volume tallies in LDS, radiance tallies in LDS, inverse table in
+ * out[0 .. min(n, 12) - 1]: field in LDS, flux tallies in LDS, volume tallies in LDS, radiance tallies in LDS, inverse table in
  * LDS (0 / 1 each); dynamic LDS bytes; absorbing (0 / 1); cell records passed to the kernel (0: none, else their bytes: 8, 16 or 32); batches of
  * the launch if it was a fused group (else 0); place of the extinction field (0 LDS, 1 global, 2 bricks, 3 column records,
- * 4 column records over a base profile).  All -1 before the first launch.  Returns 0, or 1 on a null argument. */
+ * 4 column records over a base profile); bytes of the waves' start stores in LDS (part of the dynamic LDS bytes; 0: the kernel
+ * starts its photons in the event phase); photons a wave takes per visit of the work counter (RunArgs::chunk).  All -1 before the first launch.  Returns 0, or 1 on a null argument. */
 int i3rc_hip_last_plan(const i3rc_hip_integrator *h, int32_t *out, int n);
 
 /* Experiment knobs (not part of the reference API): lanes that must be waiting before a wavefront runs its
@@ -389,6 +390,11 @@ int i3rc_hip_set_lds_tallies(i3rc_hip_integrator *h, int on);
  *               queues, radiance tallies, extinction grid / clear-air map, inverse table; the end (= words a launch allocates); and
  *               the volume-absorption tallies (which lie between the flux tallies and the directions). */
 int i3rc_hip_lds_plan(const int32_t *q, int32_t *out);
+/* ... and with the lengths of both arrays (nq >= 17, nout >= 12; 1 otherwise), for what came later:
+ *   q[17]   = start stores (the specialised flux kernels of plain launches: 64 slots of 4 words per wave, 16-byte aligned, in front
+ *             of the inverse table); absent: 0
+ *   out[12] = word offset of the start stores */
+int i3rc_hip_lds_plan_words(const int32_t *q, int nq, int32_t *out, int nout);
 
 /* Test hook: the raw Philox4x32-10 blocks (out[n][blocksPerPhoton][4]) of photons firstPhoton..+n-1 and the
  * float32 deviates the photon streams derive from them (outf, same shape). */
