@@ -29,6 +29,7 @@ SYMBOLS = [
     "i3rc_hip_fetch_tallies", "i3rc_hip_normalise", "i3rc_hip_last_kernel_ms", "i3rc_hip_kernel_ms_history", "i3rc_hip_set_tuning", "i3rc_hip_force_general_kernel", "i3rc_hip_select_kernel", "i3rc_hip_set_light_threshold", "i3rc_hip_set_launch_limit",
     "i3rc_hip_set_batch_fusion", "i3rc_hip_select_grid_place", "i3rc_hip_has_column_records", "i3rc_hip_column_records", "i3rc_hip_column_records_base", "i3rc_hip_lds_plan", "i3rc_hip_lds_plan_words", "i3rc_hip_set_lds_tallies", "i3rc_hip_last_kernel_name", "i3rc_hip_last_plan", "i3rc_hip_timed_launch_count", "i3rc_hip_philox_blocks", "i3rc_hip_arith_check", "i3rc_hip_find_index", "i3rc_hip_surface_reflectance", "i3rc_hip_device_count", "i3rc_hip_version",
     "i3rc_hip_set_level_fluxes", "i3rc_hip_get_level_flux_layout", "i3rc_hip_normalise_level_fluxes",
+    "i3rc_hip_set_actinic_flux", "i3rc_hip_get_actinic_flux_layout", "i3rc_hip_normalise_actinic_flux",
 ]
 
 
@@ -59,7 +60,7 @@ class MomentsLayout(C.Structure):
 
 # the words of i3rc_hip_last_plan, in order
 PLAN_NAMES = ["ldsGrid", "ldsTallies", "ldsVolume", "ldsIntensity", "tableInLds", "ldsBytes", "absorbing", "cellRecordBytes",
-              "fusedBatches", "place", "startStoreBytes", "chunk"]
+              "fusedBatches", "place", "startStoreBytes", "chunk", "ldsTrackSums"]
 
 
 class I3RCError(RuntimeError):
@@ -149,6 +150,10 @@ def load():
         L.i3rc_hip_set_level_fluxes.argtypes = [H, C.c_int]
         L.i3rc_hip_get_level_flux_layout.argtypes = [H, lp, lp, lp]
         L.i3rc_hip_normalise_level_fluxes.argtypes = [H, dp, fp, fp]
+    if hasattr(L, "i3rc_hip_set_actinic_flux"):   # (likewise)
+        L.i3rc_hip_set_actinic_flux.argtypes = [H, C.c_int]
+        L.i3rc_hip_get_actinic_flux_layout.argtypes = [H, lp, lp]
+        L.i3rc_hip_normalise_actinic_flux.argtypes = [H, dp, fp]
     L.i3rc_hip_device_count.restype = C.c_int
     L.i3rc_hip_version.restype = C.c_char_p
     _lib = L

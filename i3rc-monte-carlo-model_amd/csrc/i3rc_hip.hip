@@ -109,6 +109,8 @@ struct i3rc_hip_integrator {
   i3rc_tally_layout layout{};
   TallyView view{};                // the same block as the normalisation sees it (tally_block.hpp; compute_layout), over the host arrays above
   bool levelFluxes = false;        // i3rc_hip_set_level_fluxes: plain flux launches also tally levelFluxUp / levelFluxDown (view.levelUp / .levelDown)
+  bool actinicFlux = false;        // i3rc_hip_set_actinic_flux: plain flux launches also tally every cell's track-length sums ...
+  int64_t oActinic = -1;           // ... nx * ny * nz words behind the counters, where the level fluxes would lie (never both); -1: off
   DevBuf ownTally;
   double *tally = nullptr;  // device pointer in use (own or bound)
   DevBuf workCounter;
@@ -182,8 +184,8 @@ struct i3rc_hip_integrator {
   int blocksPerCU = 0;  // 0 = from occupancy query
   int kernelVariant = I3RC_KERNEL_AUTO;  // test / tuning knob (i3rc_hip_select_kernel)
   std::string lastKernelName;            // kernel the most recent launch ran (i3rc_hip_last_kernel_name)
-  static constexpr int kPlanWords = 12;
-  int32_t lastPlan[kPlanWords] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // ... and its plan (i3rc_hip_last_plan)
+  static constexpr int kPlanWords = 13, kPlanChunk = 11;
+  int32_t lastPlan[kPlanWords] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // ... and its plan (i3rc_hip_last_plan)
   int64_t launchLimit = 0;               // photons per kernel launch (i3rc_hip_set_launch_limit); 0 = numCU * 2^22
   std::string err;
 
@@ -228,6 +230,9 @@ static void compute_layout(i3rc_hip_integrator *h) {
     V.levelUp = level_block_offset(L.counters); o = V.levelUp + (int64_t)(h->nz + 1) * ncol;
     V.levelDown = o; o += (int64_t)(h->nz + 1) * ncol;
   }
+  // ... or the actinic flux's track-length sums, one word per cell, in the same place
+  h->oActinic = -1;
+  if (h->actinicFlux) { h->oActinic = level_block_offset(L.counters); o = h->oActinic + ncell; }
   L.total = o;
   V.nx = h->nx; V.ny = h->ny; V.nz = h->nz; V.ncomp = h->ncomp; V.nDir = h->nDir; V.xyRegular = h->xyRegular;
   V.areaFrac = h->areaFrac.data(); V.dz = h->layerDepth.data();
@@ -685,6 +690,9 @@ int i3rc_hip_set_level_fluxes(i3rc_hip_integrator *h, int on) {
   drop_lookahead(h);
   const bool want = on != 0;
   if (want == h->levelFluxes) return 0;
+  if (want && h->actinicFlux)
+    return h->fail("i3rc_hip_set_level_fluxes: the actinic flux is switched on and its block lies where the level fluxes' would; "
+                   "switch it off first (no kernel tallies both)");
   // the tally layout changes: as for a change of nDir, a caller-bound buffer is refused before anything is touched
   if (h->tally != (double *)h->ownTally.p)
     return h->fail("i3rc_hip_set_level_fluxes: a caller-bound tally buffer is in use; unbind it (bind NULL) before switching level fluxes, "
@@ -699,6 +707,31 @@ int i3rc_hip_get_level_flux_layout(const i3rc_hip_integrator *h, int64_t *up, in
   if (!h) return 1;
   if (up) *up = h->view.levelUp;
   if (down) *down = h->view.levelDown;
+  if (total) *total = h->layout.total;
+  return 0;
+}
+
+int i3rc_hip_set_actinic_flux(i3rc_hip_integrator *h, int on) {
+  if (!h) return 1;
+  drop_lookahead(h);
+  const bool want = on != 0;
+  if (want == h->actinicFlux) return 0;
+  if (want && h->levelFluxes)
+    return h->fail("i3rc_hip_set_actinic_flux: level fluxes are switched on and their block lies where the actinic flux's would; "
+                   "switch them off first (no kernel tallies both)");
+  // the tally layout changes: a caller-bound buffer is refused before anything is touched
+  if (h->tally != (double *)h->ownTally.p)
+    return h->fail("i3rc_hip_set_actinic_flux: a caller-bound tally buffer is in use; unbind it (bind NULL) before switching the actinic flux, "
+                   "then bind a buffer of the new layout's size");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // (launches in flight add to the buffer that is about to be replaced)
+  h->actinicFlux = want;
+  return realloc_tally(h);
+}
+
+int i3rc_hip_get_actinic_flux_layout(const i3rc_hip_integrator *h, int64_t *offset, int64_t *total) {
+  if (!h) return 1;
+  if (offset) *offset = h->oActinic;
   if (total) *total = h->layout.total;
   return 0;
 }
@@ -1053,7 +1086,10 @@ template <class Rng>
 size_t lds_bytes(const i3rc_hip_integrator *h, const LaunchPlan &plan, bool tableInLds, bool startStore) {
   const LdsPlan lp = lds_plan(plan.P, plan.intensity && !Rng::kReplay, direct_rays(h), plan.place, plan.intensity, tableInLds ? 16 : 4,
                               tableInLds ? plan.P.comp0.nInv : 0, startStore);
-  return (sizeof(float) * (size_t)lp.end + 15) & ~(size_t)15;
+  size_t words = (size_t)lp.end;
+  if constexpr (TrackLengths<Rng>::on)   // the track-length sums behind the plan's end (launch_tracks decides; photon_kernel, TRACK)
+    if (plan.P.ldsGrid & kLdsGridTrackSums) words = (size_t)track_sums_word(lp.end) + 2 * (size_t)plan.P.nx * plan.P.ny * plan.P.nz;
+  return (sizeof(float) * words + 15) & ~(size_t)15;
 }
 // the waves' start stores in a workgroup of `threads` (photon_kernel, STORE; StartSlot, tracer.hpp)
 constexpr size_t start_store_bytes(int threads) { return sizeof(float) * kStartWords * kStartSlots * (size_t)(threads / 64); }
@@ -1118,13 +1154,15 @@ void record_plan(i3rc_hip_integrator *h, const LaunchPlan &plan, bool tableInLds
   const int rec = P.cellRec == nullptr ? 0 : (h->ncomp == 1 ? 8 : (h->ncomp == 2 ? 16 : 32));
   const int32_t v[i3rc_hip_integrator::kPlanWords] = {P.ldsGrid ? 1 : 0, P.ldsTallies ? 1 : 0, P.ldsVolume ? 1 : 0, P.ldsIntensity ? 1 : 0,
                                                       tableInLds ? 1 : 0, (int32_t)ldsBytes, h->absorbing ? 1 : 0, rec, fusedBatches, plan.place,
-                                                      (int32_t)startStoreBytes, 0 /* the chunk: launch_grid, once it is known */};
+                                                      (int32_t)startStoreBytes, 0 /* the chunk: launch_grid, once it is known */,
+                                                      (P.ldsGrid & kLdsGridTrackSums) ? 1 : 0};
   std::memcpy(h->lastPlan, v, sizeof(v));
 }
 
 template <class Rng>
 constexpr const char *rng_name() {
   if constexpr (LevelFluxes<Rng>::on) return "PhiloxLevelStream";
+  else if constexpr (TrackLengths<Rng>::on) return "PhiloxTrackStream";
   else if constexpr (Rng::kReplay) return "ReplayStream";
   else if constexpr (Rng::kBatched) return "PhiloxBatchStream";
   else return "PhiloxStream";
@@ -1154,7 +1192,7 @@ template <class Rng>
 const std::vector<KernelEntry> &stream_kernels() {
   static const std::vector<KernelEntry> list = [] {
     std::vector<KernelEntry> v;
-    if constexpr (LevelFluxes<Rng>::on) {   // level fluxes: the general flux kernel, at every place
+    if constexpr (LevelFluxes<Rng>::on || TrackLengths<Rng>::on) {   // level fluxes, track lengths: the general flux kernel, at every place
       add<Rng, false, true, false, false, false>(v, AllPlaces{});
     } else if constexpr (Rng::kBatched) {   // fused multi-batch launches
       add<Rng, false, false, false, false, false>(v, NoColbase{});   // flux, the common class
@@ -1197,6 +1235,19 @@ int level_fluxes_refuse_batches(i3rc_hip_integrator *h, const char *who) {
                                     "(switch them off, or call i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)");
 }
 
+// The actinic flux likewise: the general flux kernel of a plain, traced launch (photon_kernel<PhiloxTrackStream, ...>).
+int actinic_flux_refused(i3rc_hip_integrator *h, const char *who) {
+  if (!h->actinicFlux) return 0;
+  if (h->nDir > 0) return h->fail(std::string(who) + ": the actinic flux is tallied by flux launches only; radiance directions are set (nDir > 0)");
+  if (!h->params.useRayTracing) return h->fail(std::string(who) + ": the actinic flux needs ray tracing; max cross-section is in use (useRayTracing = 0)");
+  return 0;
+}
+int actinic_flux_refuse_batches(i3rc_hip_integrator *h, const char *who) {
+  if (!h->actinicFlux) return 0;
+  return h->fail(std::string(who) + ": the actinic flux is tallied by plain launches only; fused or announced batches cannot give it "
+                                    "(switch it off, or call i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)");
+}
+
 struct KernelChoice {
   const KernelEntry *kern;   // nullptr: the stream has no instantiation for the key
   int threads;
@@ -1213,8 +1264,8 @@ KernelChoice choose_kernel(const i3rc_hip_integrator *h, const LaunchPlan &plan,
   const int place = plan.place;
   KernelKey key{plan.intensity, true, place, false, false, false};
   int threads = 256;
-  // (level fluxes: the general flux kernel whatever the problem's class -- the key as it stands)
-  if constexpr (!Rng::kReplay && !LevelFluxes<Rng>::on) {   // (the replay build always runs the general kernel: it keeps the nested local estimate, no queue at all)
+  // (level fluxes, track lengths: the general flux kernel whatever the problem's class -- the key as it stands)
+  if constexpr (!Rng::kReplay && !LevelFluxes<Rng>::on && !TrackLengths<Rng>::on) {   // (the replay build always runs the general kernel: it keeps the nested local estimate, no queue at all)
     bool simple, wide;
     if (fused) {
       // the widened class (several components, irregular x / y, a gridded surface): its own fused kernels, flux ones too -- a driver's
@@ -1302,7 +1353,7 @@ int launch_grid(i3rc_hip_integrator *h, const LaunchPlan &plan, RunArgs &A, hipS
   const long long need = (photons + threads - 1) / threads;
   if (blocks > need) blocks = std::max(1ll, need);
   if (prepare(blocks, threads)) return 1;
-  h->lastPlan[i3rc_hip_integrator::kPlanWords - 1] = A.chunk;   // (photons -- fused launches: per chunk number -- a wave takes per visit of the work counter)
+  h->lastPlan[i3rc_hip_integrator::kPlanChunk] = A.chunk;   // (photons -- fused launches: per chunk number -- a wave takes per visit of the work counter)
   const int slot = (int)(h->timedLaunches % i3rc_hip_integrator::kEventRing);
   if (timeIt) HIPCHK(h, hipEventRecord(h->evStart[slot], stream));
   {
@@ -1740,10 +1791,15 @@ void top_up_groups(i3rc_hip_integrator *h, uint32_t seed0, uint32_t nextIfNone, 
 // long batch the same as several launches over consecutive photon ranges, so very long Directional batches are cut
 // into launches of at most 2^22 photons per compute unit (about 1e9 photons on an MI355X).
 int launch_levels(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt);   // (at the end of this file)
+int launch_tracks(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt);   // (likewise)
 int launch_batch_parts(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
   const int64_t perLaunch = h->launchLimit > 0 ? h->launchLimit : (int64_t)h->numCU << 22;
   // (level fluxes switched on: the same photons through photon_kernel<PhiloxLevelStream, ...>, see launch_levels)
-  const auto run = [&](const RunArgs &part) { return h->levelFluxes ? launch_levels(h, plan, part, stream, timeIt) : launch<PhiloxStream>(h, plan, part, stream, timeIt); };
+  // (the actinic flux: photon_kernel<PhiloxTrackStream, ...>, see launch_tracks)
+  const auto run = [&](const RunArgs &part) {
+    return h->levelFluxes ? launch_levels(h, plan, part, stream, timeIt)
+                          : (h->actinicFlux ? launch_tracks(h, plan, part, stream, timeIt) : launch<PhiloxStream>(h, plan, part, stream, timeIt));
+  };
   if (A.srcKind != 0) return run(A);
   for (int64_t done = 0; done < A.nPhotons; done += perLaunch) {
     RunArgs part = A;
@@ -1783,6 +1839,7 @@ int i3rc_hip_launch_batch(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1
   if (!src) return h->fail("i3rc_hip_launch_batch: null source");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");  // illumination :78-79
   if (level_fluxes_refused(h, "i3rc_hip_launch_batch")) return 1;
+  if (actinic_flux_refused(h, "i3rc_hip_launch_batch")) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   LaunchPlan plan;
   if (make_problem(h, plan, h->stream, h->tally)) return 1;
@@ -1802,6 +1859,7 @@ int i3rc_hip_run_batches(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1,
   if (src->kind != 0) return h->fail("i3rc_hip_run_batches: Directional photon streams only (explicit streams differ from batch to batch)");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
   if (level_fluxes_refuse_batches(h, "i3rc_hip_run_batches")) return 1;
+  if (actinic_flux_refuse_batches(h, "i3rc_hip_run_batches")) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   if (fuse_loop(h, nPhotons, nBatches)) return run_batches_fused(h, seed0, seed1, nBatches, nPhotons, src, hostTallies);
   const int K = std::min(nBatches, inFlight <= 0 ? 6 : std::min(inFlight, (int)i3rc_hip_integrator::kMaxInFlight));
@@ -1847,6 +1905,7 @@ int i3rc_hip_run_batches_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_
   if (src->kind != 0) return h->fail("i3rc_hip_run_batches_moments: Directional photon streams only (explicit streams differ from batch to batch)");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
   if (level_fluxes_refuse_batches(h, "i3rc_hip_run_batches_moments")) return 1;
+  if (actinic_flux_refuse_batches(h, "i3rc_hip_run_batches_moments")) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   drop_lookahead(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1884,9 +1943,10 @@ int i3rc_hip_compute_batch(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed
   if (src->kind != 0) return h->fail("i3rc_hip_compute_batch: Directional photon streams only");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
   if (level_fluxes_refused(h, "i3rc_hip_compute_batch")) return 1;
+  if (actinic_flux_refused(h, "i3rc_hip_compute_batch")) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   // (level fluxes switched on: no look-ahead -- one launch per call)
-  const int depth = h->levelFluxes ? 0 : std::max(0, std::min(lookAhead, (int)i3rc_hip_integrator::kMaxInFlight - 1));
+  const int depth = h->levelFluxes || h->actinicFlux ? 0 : std::max(0, std::min(lookAhead, (int)i3rc_hip_integrator::kMaxInFlight - 1));
   const size_t bytes = (size_t)h->layout.total * sizeof(double);
   if (reset_slots_if_layout_changed(h)) return 1;   // (a change of the layout has dropped the queue already: set_directions)
   auto free_slot = [&]() -> int {
@@ -1966,6 +2026,7 @@ int i3rc_hip_expect_batches(i3rc_hip_integrator *h, uint32_t seed0, uint32_t see
   if (src->kind != 0) return h->fail("i3rc_hip_expect_batches: Directional photon streams only");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
   if (level_fluxes_refuse_batches(h, "i3rc_hip_expect_batches")) return 1;
+  if (actinic_flux_refuse_batches(h, "i3rc_hip_expect_batches")) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   drop_lookahead(h);
   if (!fuse_loop(h, nPhotons, nBatches)) return 0;   // (the caller goes on as it would have)
@@ -1992,6 +2053,7 @@ int i3rc_hip_run_replay(i3rc_hip_integrator *h, int64_t nPhotons, const i3rc_sou
                         int32_t *fateOrder, int32_t *drawsUsed) {
   if (!h) return 1;
   if (!src || !randoms || !drawStart || nPhotons <= 0) return h->fail("i3rc_hip_run_replay: bad arguments");
+  if (h->actinicFlux) return h->fail("i3rc_hip_run_replay: the actinic flux is tallied by the production stream's kernels only; the replay build has no such kernel (switch it off)");
   HIPCHK(h, hipSetDevice(h->device));
   LaunchPlan plan;
   if (make_problem(h, plan, h->stream, h->tally, false, true)) return 1;
@@ -2234,6 +2296,16 @@ int i3rc_hip_normalise_level_fluxes(const i3rc_hip_integrator *h, const double *
   return 0;
 }
 
+int i3rc_hip_normalise_actinic_flux(const i3rc_hip_integrator *h, const double *t, float *actinicFlux) {
+  if (!h || !t || !actinicFlux) return 1;
+  if (!h->actinicFlux) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_actinic_flux: the actinic flux is not switched on");
+  const TallyView &V = h->view;
+  const size_t ncol = (size_t)h->nx * h->ny;
+  for (int kz = 0; kz < h->nz; ++kz)
+    for (size_t k = 0; k < ncol; ++k) actinicFlux[(size_t)kz * ncol + k] = normalised_actinic_flux(V, t, h->oActinic, kz, k);
+  return 0;
+}
+
 }  // extern "C"
 
 namespace {
@@ -2241,5 +2313,17 @@ namespace {
 // kernels are instantiated behind every other kernel of the library).
 int launch_levels(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
   return launch<PhiloxLevelStream>(h, plan, A, stream, timeIt);
+}
+// ... and of photon_kernel<PhiloxTrackStream, ...> (the actinic flux), behind those.  Where the field itself lies in LDS, partial sums in
+// LDS are switched on (i3rc_hip_set_lds_tallies, I3RC_LDS_TALLIES) and the launch's allocation has room for one more float64 word per
+// cell behind the plan's end, the workgroups keep their track-length sums there: bit 1 of ldsGrid tells the kernel, the last plan says so.
+int launch_tracks(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
+  static const bool ldsTalliesEnv = env_on("I3RC_LDS_TALLIES");
+  LaunchPlan p = plan;
+  if (p.place == GRID_LDS && ldsTalliesEnv && h->ldsTalliesOn) {
+    p.P.ldsGrid |= kLdsGridTrackSums;
+    if (lds_bytes<PhiloxTrackStream>(h, p, false, false) > kLdsLaunchMax) p.P.ldsGrid &= ~kLdsGridTrackSums;
+  }
+  return launch<PhiloxTrackStream>(h, p, A, stream, timeIt);
 }
 }  // namespace

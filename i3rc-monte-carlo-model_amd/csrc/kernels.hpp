@@ -212,6 +212,8 @@ struct RngInit<ReplayStream> {
 };
 template <>
 struct RngInit<PhiloxLevelStream> : RngInit<PhiloxStream> {};
+template <>
+struct RngInit<PhiloxTrackStream> : RngInit<PhiloxStream> {};
 
 // LEVEL FLUXES: upward and downward flux through every layer interface, per column (levelFluxUp / levelFluxDown [nz + 1][ny][nx],
 // level k = zEdges[k]).  photon_kernel<PhiloxLevelStream, false, true, GRID> -- the general flux kernel, the production stream under a
@@ -259,6 +261,33 @@ __device__ __forceinline__ void tally_level_crossings(const PR &P, const Lds &L,
     }
     add_global(base + (size_t)k * ncol + col, w);
   }
+}
+
+// ACTINIC FLUX by photon track length: for every cell the sum, over all pieces of photon paths inside it, of w * l -- w the weight the
+// photon carries along the piece (before the event at its end), l the float32 length the tracer itself steps -- as one float64 word per
+// cell [nz][ny][nx]; normalised_actinic_flux (tally_block.hpp) turns it into the cell's mean actinic flux in units of the incident
+// flux.  photon_kernel<PhiloxTrackStream, false, true, GRID> -- the general flux kernel under one more tag -- tallies it in the
+// VOXEL-STEP phase: every step that is no tracer error adds w * step to the cell the photon was in BEFORE the step (trace_step_lazy,
+// LENGTH), whether it reaches a face, snaps an index, wraps or leaves the grid; the arriving step advances nothing there, its length
+// is the part finish_arrival forms in the event phase, tallied in the cell the photon stands in with the weight before the
+// scattering.  The block lies where the level fluxes' does -- behind the counters (level_block_offset): the two are never on together.
+// Where the field itself lies in LDS (GRID_LDS) and the launch has ncell * 8 more bytes of it, a workgroup keeps partial sums there
+// (ds_add_f64 per step, one global atomic per non-zero word at its end): a small domain's few hundred words take a tenth of the
+// scattered atomic rate in global memory, and a photon makes some sixty steps into them.  The region is carved BEHIND what lds_plan
+// returns as its end, 8-byte aligned, in this instantiation and its launch alone; the host says so in bit 1 of DevProblem::ldsGrid,
+// which no kernel reads otherwise.  Elsewhere: float64 atomics in global memory.
+template <class Rng> struct TrackLengths { static constexpr bool on = false; };
+template <> struct TrackLengths<PhiloxTrackStream> { static constexpr bool on = true; };
+constexpr int kLdsGridTrackSums = 2;   // DevProblem::ldsGrid, bit 1 (launches of photon_kernel<PhiloxTrackStream, ...> only)
+// first word of the track sums in a launch's dynamic LDS, given the end of its lds_plan -- the host's allocation and the kernel's pointer both
+__host__ __device__ inline int track_sums_word(int planEnd) { return (planEnd + 1) & ~1; }
+typedef __attribute__((address_space(3))) double lds_f64;
+// one piece of a path: weight * length (exact in float64) into the cell's word -- the workgroup's partial sum, or the block in global memory
+__device__ __forceinline__ void track_add(lds_f64 *sums, double *block, int cell, int ncell, float weight, float length) {
+  const double v = (double)weight * (double)length;
+  const unsigned at = min((unsigned)cell, (unsigned)(ncell - 1));   // (never outside the block, whatever the indices)
+  if (sums) (void)__hip_atomic_fetch_add(sums + at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_add_f64
+  else add_global(block + at, v);
 }
 
 // Wave-private reservoir of photon indices: one returning atomic per `chunk` photons instead of one per respawn
@@ -427,7 +456,7 @@ struct WaveStartState {
 // of the instantiation, derived from its template arguments: the host sizes the launch's LDS by the same function.
 template <class Rng>
 constexpr bool has_start_store(bool intensity, bool general, int grid, bool multi) {
-  return !Rng::kReplay && !Rng::kBatched && !LevelFluxes<Rng>::on && !intensity && !general && !multi && grid != GRID_BRICKS;
+  return !Rng::kReplay && !Rng::kBatched && !LevelFluxes<Rng>::on && !TrackLengths<Rng>::on && !intensity && !general && !multi && grid != GRID_BRICKS;
 }
 // GENERAL = false is the specialisation for the common problem class -- regular grid, ray tracing, one component,
 // Lambertian albedo (no BRDF grid), Directional source, production RNG: the rare paths (grid searches, periodic
@@ -456,6 +485,8 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   Lds L;
   constexpr bool STORE = has_start_store<Rng>(INTENSITY, GENERAL, GRID, MULTI);   // photons start a wavefront at a time: part B of the event phase
   lds_float *startSlots = nullptr;   // STORE: this wave's start store (StartSlot, tracer.hpp)
+  constexpr bool TRACK = TrackLengths<Rng>::on;   // actinic flux by track length (PhiloxTrackStream): tallied by the general flux kernel only
+  lds_f64 *trackSums = nullptr;      // TRACK: the workgroup's partial sums of the block (nullptr: the block in global memory is added to)
   {
     // (one carve-up for the kernel and for the host's allocation: lds_plan, tracer.hpp)
     const LdsPlan lp = lds_plan(P, INTENSITY && !Rng::kReplay, DIRECT, GRID, INTENSITY, TBL ? 16 : 4, 0, STORE);
@@ -466,7 +497,12 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
     L.tUp = (lds_tally *)(base + lp.tallies); L.tDown = L.tUp + ncol; L.tVol = (lds_tally *)(base + lp.tVol);
     L.dirCos = base + lp.dirCos; L.dirTab = base + lp.dirTab; L.queue = base + lp.queue;
     L.tInt = (lds_tally *)(base + lp.tInt); L.ext = base + lp.ext; L.cosTab = base + lp.cosTab;
+    if constexpr (TRACK && GRID == GRID_LDS)
+      if (P.ldsGrid & kLdsGridTrackSums) trackSums = (lds_f64 *)(base + track_sums_word(lp.end));
   }
+  if constexpr (TRACK)
+    if (trackSums != nullptr)
+      for (int i = threadIdx.x; i < P.nx * P.ny * P.nz; i += blockDim.x) trackSums[i] = 0.0;
   for (int i = threadIdx.x; i < 3 * P.nDir; i += blockDim.x) L.dirCos[i] = P.dirCos[i];
   // coalesced staging of the edge vectors (and the extinction grid when it fits)
   for (int i = threadIdx.x; i <= P.nx; i += blockDim.x) L.xE[i] = P.xE[i];
@@ -508,6 +544,8 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   static_assert(!BATCHED || !GENERAL, "fused multi-batch launches: specialised kernels");
   constexpr bool LEVELS = LevelFluxes<Rng>::on;   // level fluxes (PhiloxLevelStream): tallied by the general flux kernel only
   static_assert(!LEVELS || (GENERAL && !INTENSITY && !TBL && !DIRECT && !MULTI), "level fluxes: the general flux kernel");
+  static_assert(!TRACK || (GENERAL && !INTENSITY && !TBL && !DIRECT && !MULTI && !STORE && !BATCHED && !REPLAY && !LEVELS),
+                "track lengths: the general flux kernel, no start store, not batched");
   static_assert(!MULTI || (!GENERAL && !TBL && !Rng::kReplay && (INTENSITY || BATCHED)), "MULTI: the widened class -- radiance kernels, and the fused flux kernels (plain flux launches of the class run the general flux kernel)");
   // Work counters of a fused launch.  Flux kernels: exact per batch, gathered per lane (below).  Radiance kernels have no
   // vector register to spare for that: their counters stay per WAVE and are handed to the batch whose photons the wave was
@@ -1048,6 +1086,13 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       PROF_BEGIN();
       // a photon that has arrived at its optical depth makes the last advance of its trace here (trace_step_lazy / finish_arrival):
       // once per event instead of a division at every voxel step
+      if constexpr (TRACK) {   // ... and its length is the last piece of the segment: in the cell the photon stands in, with the weight before the scattering
+        if (wantEvent && st == ST_EVENT && arrival_pending(r)) {
+          float part = 0.0f;
+          finish_arrival<true>(r, &part);
+          track_add(trackSums, tally.base() + level_block_offset(Pe.oCnt), cell_index(Pe, r.ix, r.iy, r.iz), Pe.nx * Pe.ny * Pe.nz, w, part);
+        }
+      } else
       if (wantEvent && st == ST_EVENT && arrival_pending(r)) finish_arrival(r);
       // ... and one that has left the grid gets its height (finish_exit).  (The general kernels do that where the step ends: here it
       // cost them nine spilled vector registers -- and with max cross-section the layer index says nothing about the height.)
@@ -1543,7 +1588,14 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       PROF_BEGIN();
       if (tracing) {
         if constexpr (LANE_COUNTS) accSteps++;
-        const StepResult s = trace_step_lazy<GRID, !INTENSITY, GENERAL>(P, L, r, true);   // (an arrival is finished by the event phase)
+        StepResult s;
+        if constexpr (TRACK) {   // the piece of path inside the cell the photon is in before the step (a failed step and the arriving one add nothing here)
+          const int cell = cell_index(P, r.ix, r.iy, r.iz);
+          float len = 0.0f;
+          s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, true>(P, L, r, true, &len);
+          if (s == STEP_CONTINUE || s == STEP_EXIT) track_add(trackSums, P.tally + level_block_offset(P.oCnt), cell, P.nx * P.ny * P.nz, w, len);
+        } else
+        s = trace_step_lazy<GRID, !INTENSITY, GENERAL>(P, L, r, true);   // (an arrival is finished by the event phase)
         if (GENERAL && s == STEP_EXIT) finish_exit(P, r);
         // (an exit through the top, or onto a black surface, ends the photon: such lanes wait for the turnover quorum)
         if (s != STEP_CONTINUE)
@@ -1593,6 +1645,15 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
         if (v != (tally_t)0) add_global(out + oVol + i, v);
       }
     }
+    if constexpr (TRACK)
+      if (trackSums != nullptr) {
+        double *const block = out + level_block_offset(ka->P.oCnt);
+        const int ncellT = ka->P.nx * ka->P.ny * ka->P.nz;
+        for (int i = threadIdx.x; i < ncellT; i += blockDim.x) {
+          const double v = trackSums[i];
+          if (v != 0.0) add_global(block + i, v);
+        }
+      }
     if (ka->P.ldsIntensity) {
       const int nInt = (ka->P.ncomp + 1) * ka->P.nDir * ka->P.nx * ka->P.ny;
       const int oInt = ka->P.oInt;

@@ -175,6 +175,9 @@ struct PhiloxBatchStream : PhiloxStreamT<true> {};
 // also tallies the upward and downward flux through every layer interface (kernels.hpp, LevelFluxes).  A stream type and not a template
 // parameter of the kernel: the kernel's parameter list, and with it every other instantiation's name, stays as it is.
 struct PhiloxLevelStream : PhiloxStream {};
+// ... and once more: photon_kernel<PhiloxTrackStream, ...> also tallies every cell's actinic flux by photon track length (kernels.hpp,
+// TrackLengths).  (The name begins with neither "PhiloxStream" nor "PhiloxBatchStream": the kernel audits count kernels by those prefixes.)
+struct PhiloxTrackStream : PhiloxStream {};
 
 // Test stream: deviates come from a buffer (the reference's MT19937 floats); see i3rc_hip_run_replay.
 struct ReplayStream {

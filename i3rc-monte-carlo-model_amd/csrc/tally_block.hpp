@@ -1,5 +1,5 @@
 // One raw tally block -- where its fields lie, and the rule that turns its float64 sums into the real(4) fields reportResults
-// hands out (computeRadiativeTransfer :327-395) -- stated once for the host (i3rc_hip_normalise, i3rc_hip_normalise_level_fluxes)
+// hands out (computeRadiativeTransfer :327-395) -- stated once for the host (i3rc_hip_normalise, i3rc_hip_normalise_level_fluxes, i3rc_hip_normalise_actinic_flux)
 // and for the kernels (the batch moments).  The library is built with -ffp-contract=off, so both sides round alike.
 // Plain C++17: no HIP header is needed (a host compiler alone builds tests/normalise_main.cpp against it).
 #pragma once
@@ -46,6 +46,14 @@ I3RC_TALLY_FN float normalised_column_flux(const TallyView &V, const double *raw
 I3RC_TALLY_FN float normalised_volume_absorption(const TallyView &V, const double *raw, int kz, long long col) {
   const long long ncol = (long long)V.nx * V.ny;
   return (float)(raw[V.volumeAbsorption + kz * ncol + col] / (photons_per_column(V, raw, col) * V.dz[kz]));
+}
+
+// The cell-mean actinic flux from the track-length sums (the block of nx * ny * nz words at `block`, [nz][ny][nx]: i3rc_hip_set_actinic_flux):
+// per photon of the column and per unit of the layer's depth, as volumeAbsorption -- 1 in clear air under a zenith sun, in units of the
+// incident flux on a horizontal surface.
+I3RC_TALLY_FN float normalised_actinic_flux(const TallyView &V, const double *raw, long long block, int kz, long long col) {
+  const long long ncol = (long long)V.nx * V.ny;
+  return (float)(raw[block + kz * ncol + col] / (photons_per_column(V, raw, col) * V.dz[kz]));
 }
 
 // What component j (0: the surface) adds to the column's radiance in direction d beyond its own sum: its share of the excess of

@@ -542,8 +542,11 @@ __device__ __forceinline__ float cell_extinction(const PR &P, const Lds &L, int 
 // which sit at the 168 registers of three waves per SIMD, four spilled vector registers)
 // (SHORT: the three proximity tests behind exec masks of their own -- see below; the photon steps of the ring kernels, whose 96 registers
 // the other form overran by two)
-template <int GRID, bool CLEARMAP = false, bool BRANCHY = false, bool SHORT = false, class PR>
-__device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L, Ray &r, bool hasTarget) {
+// (LENGTH: the step also hands out, in *length, the path it advances inside the cell it began in -- `step`, or 0 in the arriving step,
+// whose length finish_arrival forms; a failed step leaves *length alone.  photon_kernel<PhiloxTrackStream, ...> alone asks for it:
+// every other instantiation compiles to what it compiled to without the flag.)
+template <int GRID, bool CLEARMAP = false, bool BRANCHY = false, bool SHORT = false, bool LENGTH = false, class PR>
+__device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L, Ray &r, bool hasTarget, float *length = nullptr) {
   // the extinction of the current cell is requested first: its latency (LDS, or L2 / HBM for grids that do not fit
   // in LDS) is covered by the three face-distance divisions below
   const float ext = cell_extinction<GRID, CLEARMAP>(P, L, r.ix, r.iy, r.iz);
@@ -592,6 +595,7 @@ __device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L,
   bool reach = false;
   if (hasTarget) reach = r.acc + tauCell > r.target;                  // :1721-1731
   const float adv = reach ? 0.0f : step;                               // (an arrival stays where it is: finish_arrival)
+  if constexpr (LENGTH) *length = adv;
   const float rest = r.target - r.acc;
   r.target = reach ? -ext : r.target;
   r.acc = reach ? rest : r.acc + tauCell;
@@ -644,10 +648,13 @@ __device__ __forceinline__ void finish_exit(const PR &P, Ray &r) {
 // has the trace arrived at its target without its last advance (trace_step_lazy)?
 __device__ __forceinline__ bool arrival_pending(const Ray &r) { return r.target < 0.0f; }
 // the advance of the arriving step :1724-1731, :1736-1738 (the position ends inside the cell: no face, no index, no wrap)
-__device__ __forceinline__ void finish_arrival(Ray &r) {
+// (LENGTH: ... and hands that advance's length out, as trace_step_lazy does)
+template <bool LENGTH = false>
+__device__ __forceinline__ void finish_arrival(Ray &r, float *length = nullptr) {
   const float ext = -r.target, rest = r.acc;
   float part = exact_div(rest, ext, refined_rcp(ext));
   if (__builtin_expect(ext < 1e-20f, 0)) part = rest / ext;
+  if constexpr (LENGTH) *length = part;
   r.x = r.x + part * r.dx; r.y = r.y + part * r.dy; r.z = r.z + part * r.dz;
 }
 // the reference's step: an arrival finished at once, the optical path at its target

@@ -196,6 +196,19 @@ module i3rcHipInterface
       type(c_ptr), value         :: levelFluxUp, levelFluxDown   ! (nx, ny, nz + 1) each
       integer(c_int)             :: rc
     end function
+    function i3rc_hip_set_actinic_flux(h, on) bind(C, name = "i3rc_hip_set_actinic_flux") result(rc)
+      import
+      type(c_ptr), value    :: h
+      integer(c_int), value :: on
+      integer(c_int)        :: rc
+    end function
+    function i3rc_hip_normalise_actinic_flux(h, host, actinicFlux) bind(C, name = "i3rc_hip_normalise_actinic_flux") result(rc)
+      import
+      type(c_ptr), value         :: h
+      real(c_double), intent(in) :: host(*)
+      type(c_ptr), value         :: actinicFlux                  ! (nx, ny, nz)
+      integer(c_int)             :: rc
+    end function
     function i3rc_hip_device_count() bind(C, name = "i3rc_hip_device_count") result(n)
       import
       integer(c_int) :: n

@@ -59,6 +59,10 @@ module monteCarloRadiativeTransfer
     ! (nx, ny, nz + 1): level k is the interface at zPosition(k), 1 the surface, nz + 1 the top (not in the reference)
     logical :: computeLevelFluxes = .false.
     real, dimension(:, :, :),    pointer :: levelFluxUp => null(), levelFluxDown => null()
+    ! ... and, with specifyParameters(computeActinicFlux = .true.), every cell's mean actinic flux by photon track length (nx, ny, nz),
+    ! in units of the incident flux on a horizontal surface (not in the reference)
+    logical :: computeActinicFlux = .false.
+    real, dimension(:, :, :),    pointer :: actinicFlux => null()
     double precision :: photonsProcessed = 0.d0, photonsDropped = 0.d0
     ! raw tallies of the batches of the last computeRadiativeTransferBatches (one column per batch)
     real(c_double), dimension(:, :), pointer :: batchTallies => null()
@@ -159,7 +163,7 @@ contains
                                useHybridPhaseFunsForIntenCalcs, hybridPhaseFunWidth,   &
                                numOrdersOrigPhaseFunIntenCalcs,                        &
                                limitIntensityContributions, maxIntensityContribution,  &
-                               status, computeLevelFluxes)
+                               status, computeLevelFluxes, computeActinicFlux)
     type(integrator),                   intent(inout) :: thisIntegrator
     real,                     optional, intent(in   ) :: surfaceAlbedo
     type(surfaceDescription), optional, intent(in   ) :: surfaceBDRF
@@ -176,6 +180,8 @@ contains
     type(ErrorMessage),                 intent(inout) :: status
     ! (not in the reference, hence behind status: level fluxes, see reportResults)
     logical,                  optional, intent(in   ) :: computeLevelFluxes
+    ! (likewise: the actinic flux of every cell, see reportResults)
+    logical,                  optional, intent(in   ) :: computeActinicFlux
     integer :: i, nDir, nx, ny, nc
     real, dimension(:),    pointer :: xs, ys
     real, dimension(:, :), pointer :: albedoGrid
@@ -332,6 +338,16 @@ contains
         thisIntegrator%levelFluxUp = 0.; thisIntegrator%levelFluxDown = 0.
       end if
       thisIntegrator%computeLevelFluxes = computeLevelFluxes
+    end if
+    if(present(computeActinicFlux)) then
+      if(.not. deviceCall(thisIntegrator, i3rc_hip_set_actinic_flux(thisIntegrator%device, merge(1, 0, computeActinicFlux)), &
+                          "specifyParameters", status)) return
+      if(associated(thisIntegrator%actinicFlux)) deallocate(thisIntegrator%actinicFlux)
+      if(computeActinicFlux) then
+        allocate(thisIntegrator%actinicFlux(size(thisIntegrator%totalExt, 1), size(thisIntegrator%totalExt, 2), size(thisIntegrator%totalExt, 3)))
+        thisIntegrator%actinicFlux = 0.
+      end if
+      thisIntegrator%computeActinicFlux = computeActinicFlux
     end if
     call setStateToSuccess(status)
   end subroutine specifyParameters
@@ -571,6 +587,11 @@ contains
     if(thisIntegrator%computeLevelFluxes) then
       ok = deviceCall(thisIntegrator, i3rc_hip_normalise_level_fluxes(thisIntegrator%device, raw,                           &
                       c_loc(thisIntegrator%levelFluxUp(1, 1, 1)), c_loc(thisIntegrator%levelFluxDown(1, 1, 1))), caller, status)
+      if(.not. ok) return
+    end if
+    if(thisIntegrator%computeActinicFlux) then
+      ok = deviceCall(thisIntegrator, i3rc_hip_normalise_actinic_flux(thisIntegrator%device, raw,                           &
+                      c_loc(thisIntegrator%actinicFlux(1, 1, 1))), caller, status)
       if(.not. ok) return
     end if
     thisIntegrator%photonsProcessed = raw(layout%counters + 1 + I3RC_CNT_PHOTONS)
@@ -885,7 +906,8 @@ contains
   ! Reporting
   ! ------------------------------------------------------------------------------------------------
   subroutine reportResults(thisIntegrator, meanFluxUp, meanFluxDown, meanFluxAbsorbed, fluxUp, fluxDown, fluxAbsorbed, &
-                           absorbedProfile, volumeAbsorption, meanIntensity, intensity, status, levelFluxUp, levelFluxDown)
+                           absorbedProfile, volumeAbsorption, meanIntensity, intensity, status, levelFluxUp, levelFluxDown, &
+                           actinicFlux)
     type(integrator),                   intent(in   ) :: thisIntegrator
     real,                     optional, intent(  out) :: meanFluxUp, meanFluxDown, meanFluxAbsorbed
     real, dimension(:, :),    optional, intent(  out) :: fluxUp, fluxDown, fluxAbsorbed
@@ -896,6 +918,8 @@ contains
     type(ErrorMessage),                 intent(inout) :: status
     ! (not in the reference, hence behind status) (nx, ny, nz + 1): level k is the interface at zPosition(k)
     real, dimension(:, :, :), optional, intent(  out) :: levelFluxUp, levelFluxDown
+    ! (likewise) (nx, ny, nz): the cell's mean actinic flux in units of the incident flux on a horizontal surface
+    real, dimension(:, :, :), optional, intent(  out) :: actinicFlux
     integer :: nColumns, d
 
     if(.not. associated(thisIntegrator%fluxUp)) then
@@ -968,6 +992,15 @@ contains
         levelFluxDown = thisIntegrator%levelFluxDown
       end if
     end if
+    if(present(actinicFlux)) then
+      if(.not. associated(thisIntegrator%actinicFlux)) then
+        call setStateToFailure(status, "reportResults: actinic flux information not available")
+      else if(any(shape(actinicFlux) /= shape(thisIntegrator%actinicFlux))) then
+        call setStateToFailure(status, "reportResults: actinicFlux array is the wrong size")
+      else
+        actinicFlux = thisIntegrator%actinicFlux
+      end if
+    end if
     if(.not. stateIsFailure(status)) call setStateToSuccess(status)
   contains
     subroutine copyField(from, to, name)
@@ -1037,6 +1070,13 @@ contains
         copy%computeLevelFluxes = .true.
       end if
     end if
+    if(original%computeActinicFlux) then
+      if(deviceCall(copy, i3rc_hip_set_actinic_flux(copy%device, 1), "copy_Integrator", status)) then
+        allocate(copy%actinicFlux(nx, ny, nz))
+        copy%actinicFlux = original%actinicFlux
+        copy%computeActinicFlux = .true.
+      end if
+    end if
   end function copy_Integrator
 
   subroutine finalize_Integrator(thisIntegrator)
@@ -1070,7 +1110,8 @@ contains
     if(associated(thisIntegrator%batchTallies))         deallocate(thisIntegrator%batchTallies)
     if(associated(thisIntegrator%momentSums))           deallocate(thisIntegrator%momentSums, thisIntegrator%momentSquares)
     if(associated(thisIntegrator%levelFluxUp))          deallocate(thisIntegrator%levelFluxUp, thisIntegrator%levelFluxDown)
-    thisIntegrator%computeLevelFluxes = .false.
+    if(associated(thisIntegrator%actinicFlux))          deallocate(thisIntegrator%actinicFlux)
+    thisIntegrator%computeLevelFluxes = .false.; thisIntegrator%computeActinicFlux = .false.
     thisIntegrator%readyToCompute = .false.; thisIntegrator%computeIntensity = .false.
     thisIntegrator%useSurfaceBDRF = .false.
   end subroutine finalize_Integrator

@@ -174,7 +174,7 @@ class Integrator:
                    "intensityPhis", "computeIntensity", "useRayTracing", "useRussianRoulette",
                    "useRussianRouletteForIntensity", "zetaMin", "useHybridPhaseFunsForIntenCalcs",
                    "hybridPhaseFunWidth", "numOrdersOrigPhaseFunIntenCalcs", "limitIntensityContributions",
-                   "maxIntensityContribution", "computeLevelFluxes")
+                   "maxIntensityContribution", "computeLevelFluxes", "computeActinicFlux")
 
     def __init__(self, atmosphere, device=0):
         self._h = C.c_void_p()
@@ -204,6 +204,7 @@ class Integrator:
         self.intensityDirections = np.zeros((0, 3), np.float32)
         self.computeIntensity = False
         self.computeLevelFluxes = False
+        self.computeActinicFlux = False
         self._inv_size = [0] * self.ncomp
         self._fwd_size = [0] * self.ncomp
         self._fwd_stale = True
@@ -309,6 +310,19 @@ class Integrator:
             self.computeLevelFluxes = bool(kw["computeLevelFluxes"])
             self._results = None             # (the tally layout has changed)
 
+        if "computeActinicFlux" in kw:
+            # every cell's actinic flux by photon track length (i3rc_hip_set_actinic_flux): not in the reference
+            self._check(self._lib.i3rc_hip_set_actinic_flux(self._h, int(bool(kw["computeActinicFlux"]))), "specifyParameters")
+            self.computeActinicFlux = bool(kw["computeActinicFlux"])
+            self._results = None             # (the tally layout has changed)
+
+    def actinic_flux_layout(self):
+        """(offset of the track-length block, total) of the packed tally buffer, in float64 elements; the offset is -1 while the
+        actinic flux is off (i3rc_hip_get_actinic_flux_layout)."""
+        off, total = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.i3rc_hip_get_actinic_flux_layout(self._h, C.byref(off), C.byref(total)), "actinic_flux_layout")
+        return off.value, total.value
+
     def level_flux_layout(self):
         """(offset of levelFluxUp, offset of levelFluxDown, total) of the packed tally buffer, in float64 elements; the offsets are -1
         while level fluxes are off (i3rc_hip_get_level_flux_layout)."""
@@ -404,6 +418,10 @@ class Integrator:
             res["levelFluxDown"] = np.zeros((self.nz + 1, self.ny, self.nx), np.float32)
             self._check(self._lib.i3rc_hip_normalise_level_fluxes(self._h, raw.ctypes.data_as(B.dp), pf(res["levelFluxUp"]),
                                                                   pf(res["levelFluxDown"])), "computeRadiativeTransfer")
+        if self.computeActinicFlux:
+            res["actinicFlux"] = np.zeros((self.nz, self.ny, self.nx), np.float32)
+            self._check(self._lib.i3rc_hip_normalise_actinic_flux(self._h, raw.ctypes.data_as(B.dp), pf(res["actinicFlux"])),
+                        "computeRadiativeTransfer")
         cnt = raw[lay.counters:lay.counters + B.NUM_COUNTERS]
         res["counters"] = {k: float(cnt[i]) for i, k in enumerate(B.COUNTER_NAMES)}
         res["raw"] = raw
@@ -513,7 +531,7 @@ class Integrator:
         return ms
 
     # -- reportResults :711-826
-    def reportResults(self, levelFluxUp=False, levelFluxDown=False):
+    def reportResults(self, levelFluxUp=False, levelFluxDown=False, actinicFlux=False):
         """levelFluxUp / levelFluxDown = True ask for the level fluxes, (nz + 1, ny, nx) each, level k at zPosition[k] (the shell's optional
         arguments of the same names): an error unless specifyParameters(computeLevelFluxes=True) came before the computation."""
         r = self._results
@@ -521,6 +539,8 @@ class Integrator:
             raise I3RCError("reportResults: no results available")
         if (levelFluxUp or levelFluxDown) and "levelFluxUp" not in r:
             raise I3RCError("reportResults: level fluxes weren't computed (specifyParameters: computeLevelFluxes)")
+        if actinicFlux and "actinicFlux" not in r:   # (actinicFlux = True: the cell-mean actinic flux, (nz, ny, nx); the shell's error text)
+            raise I3RCError("reportResults: actinic flux information not available")
         ncol = r32(self.nx * self.ny)
         out = dict(meanFluxUp=r["fluxUp"].sum(dtype=np.float32) / ncol, meanFluxDown=r["fluxDown"].sum(dtype=np.float32) / ncol,
                    meanFluxAbsorbed=r["fluxAbsorbed"].sum(dtype=np.float32) / ncol,
@@ -534,6 +554,8 @@ class Integrator:
             out["levelFluxUp"] = r["levelFluxUp"]
         if levelFluxDown:
             out["levelFluxDown"] = r["levelFluxDown"]
+        if actinicFlux:
+            out["actinicFlux"] = r["actinicFlux"]
         return out
 
     # -- test hooks

@@ -166,6 +166,35 @@ int i3rc_hip_get_level_flux_layout(const i3rc_hip_integrator *h, int64_t *up, in
  * copy of the packed tallies: levelFluxUp / levelFluxDown [nz + 1][ny][nx] (either may be NULL).  Fails while the feature is off. */
 int i3rc_hip_normalise_level_fluxes(const i3rc_hip_integrator *h, const double *hostTallies, float *levelFluxUp, float *levelFluxDown);
 
+/* ACTINIC FLUX (not in the reference): with on != 0, plain flux launches (i3rc_hip_launch_batch, i3rc_hip_compute_batch, launches
+ * split over photon ranges) also tally, for every cell, the sum over all pieces of photon paths inside it of w * l: w the weight the
+ * photon carries along the piece (before the event at its end), l the float32 length the tracer itself steps -- the track-length
+ * estimator of the actinic flux (scalar irradiance, 4 pi times the mean radiance), defined in clear and in conservative cells too.
+ * Every voxel step that is no tracer error tallies its full length in the cell the photon was in before it; the step in which the
+ * photon arrives at its optical depth tallies the part up to the arrival, with the weight before the scattering.
+ * The block is nx ny nz float64 words, [nz][ny][nx], BEHIND the counters of the packed tally buffer -- where the level fluxes' block
+ * would lie: the two features are never on together.  No offset of i3rc_tally_layout moves; layout.total grows by nx ny nz while the
+ * feature is on and is what it was once it is off again (zeroing, fetching, binding and an all-reduce of the packed buffer cover
+ * the block).  Switching reallocates the handle's own buffer (cleared).  Refused: with a caller-bound buffer in use; switching on
+ * while level fluxes are on (and i3rc_hip_set_level_fluxes while this is on).  Off by default: nothing changes then.
+ * While the feature is on, a launch runs photon_kernel<PhiloxTrackStream, false, true, GRID> -- the general flux kernel's photons,
+ * counter for counter -- and is refused, before anything is touched, when radiance directions are set (nDir > 0) or max cross-section
+ * is in use (useRayTracing = 0); i3rc_hip_run_batches, i3rc_hip_run_batches_moments, i3rc_hip_expect_batches and i3rc_hip_run_replay
+ * are refused; i3rc_hip_compute_batch does not look ahead.  Where the extinction field lies in LDS and the launch's LDS has room for
+ * the block, a workgroup sums in LDS first (i3rc_hip_set_lds_tallies(h, 0) switches that off; i3rc_hip_last_plan reports it).
+ * In a cell WITHOUT extinction the estimate's mean is right but its variance diverges logarithmically (a photon scattered or
+ * reflected into a nearly horizontal direction crosses the layer with l = dz / |mu|): batch standard errors are not to be trusted
+ * there; a gas component that gives every cell some extinction removes the problem. */
+int i3rc_hip_set_actinic_flux(i3rc_hip_integrator *h, int on);
+/* Offset (float64 elements) of the block in the packed buffer, -1 while the feature is off, and the buffer's total (= layout.total).
+ * Either may be NULL. */
+int i3rc_hip_get_actinic_flux_layout(const i3rc_hip_integrator *h, int64_t *offset, int64_t *total);
+/* volumeAbsorption's normalisation (i3rc_hip_normalise: per photon of the column and per unit of the layer's depth, float64 rounded
+ * to float32) of a host copy of the packed tallies: actinicFlux [nz][ny][nx], x fastest, the cell's mean actinic flux in units of the
+ * incident flux on a horizontal surface (1 in clear air under a zenith sun, 1 / mu0 under a slant sun); the expectation of
+ * volumeAbsorption in a cell is sum_j ext_j (1 - omega_j) times it.  Fails while the feature is off. */
+int i3rc_hip_normalise_actinic_flux(const i3rc_hip_integrator *h, const double *hostTallies, float *actinicFlux);
+
 /* ---- the hot path ---------------------------------------------------------------------------------- */
 
 /* computeRT (:400-707) for one batch of nPhotons, ASYNCHRONOUS on the handle's stream; tallies accumulate.
@@ -313,11 +342,11 @@ int64_t i3rc_hip_timed_launch_count(const i3rc_hip_integrator *h);
 const char *i3rc_hip_last_kernel_name(const i3rc_hip_integrator *h);
 
 /* Test hook: the plan of the most recent launch (recorded with i3rc_hip_last_kernel_name; reads state, decides nothing).
- * out[0 .. min(n, 12) - 1]: field in LDS, flux tallies in LDS, volume tallies in LDS, radiance tallies in LDS, inverse table in
+ * out[0 .. min(n, 13) - 1]: field in LDS, flux tallies in LDS, volume tallies in LDS, radiance tallies in LDS, inverse table in
  * LDS (0 / 1 each); dynamic LDS bytes; absorbing (0 / 1); cell records passed to the kernel (0: none, else their bytes: 8, 16 or 32); batches of
  * the launch if it was a fused group (else 0); place of the extinction field (0 LDS, 1 global, 2 bricks, 3 column records,
  * 4 column records over a base profile); bytes of the waves' start stores in LDS (part of the dynamic LDS bytes; 0: the kernel
- * starts its photons in the event phase); photons a wave takes per visit of the work counter (RunArgs::chunk).  All -1 before the first launch.  Returns 0, or 1 on a null argument. */
+ * starts its photons in the event phase); photons a wave takes per visit of the work counter (RunArgs::chunk); the actinic flux's track-length sums in LDS (0 / 1).  All -1 before the first launch.  Returns 0, or 1 on a null argument. */
 int i3rc_hip_last_plan(const i3rc_hip_integrator *h, int32_t *out, int n);
 
 /* Experiment knobs (not part of the reference API): lanes that must be waiting before a wavefront runs its
