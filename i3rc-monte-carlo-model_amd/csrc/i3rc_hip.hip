@@ -107,10 +107,8 @@ struct i3rc_hip_integrator {
   int uniformPf = 0;         // ... and the phase-function entry every cell shares, else 0
 
   i3rc_tally_layout layout{};
-  TallyView view{};                // the same block as the normalisation sees it (tally_block.hpp; compute_layout), over the host arrays above
-  bool levelFluxes = false;        // i3rc_hip_set_level_fluxes: plain flux launches also tally levelFluxUp / levelFluxDown (view.levelUp / .levelDown)
-  bool actinicFlux = false;        // i3rc_hip_set_actinic_flux: plain flux launches also tally every cell's track-length sums ...
-  int64_t oActinic = -1;           // ... nx * ny * nz words behind the counters, where the level fluxes would lie (never both); -1: off
+  TallyView view{};                // the same block as the normalisation sees it (tally_block.hpp, tally_layout), over the host arrays above
+  ExtraTally extra = EXTRA_NONE;   // set_extra_tally: the block plain flux launches also fill, behind the counters (tally_block.hpp)
   DevBuf ownTally;
   double *tally = nullptr;  // device pointer in use (own or bound)
   DevBuf workCounter;
@@ -211,32 +209,13 @@ static float host_spacing(float x) {
 }
 
 static void compute_layout(i3rc_hip_integrator *h) {
-  const int64_t ncol = (int64_t)h->nx * h->ny, ncell = ncol * h->nz;
-  i3rc_tally_layout &L = h->layout;
-  int64_t o = 0;
-  L.fluxUp = o; o += ncol;
-  L.fluxDown = o; o += ncol;
-  L.fluxAbsorbed = o; o += ncol;
-  L.volumeAbsorption = o; o += ncell;
-  L.intensityByComponent = o; o += (int64_t)(h->ncomp + 1) * h->nDir * ncol;
-  L.intensityExcess = o; o += (int64_t)(h->ncomp + 1) * h->nDir;
-  L.counters = o; o += I3RC_NUM_COUNTERS;
   TallyView &V = h->view;
-  V.fluxUp = L.fluxUp; V.fluxDown = L.fluxDown; V.fluxAbsorbed = L.fluxAbsorbed; V.volumeAbsorption = L.volumeAbsorption;
-  V.intensityByComponent = L.intensityByComponent; V.intensityExcess = L.intensityExcess; V.counters = L.counters;
-  // level fluxes (while switched on): behind everything else, so that no other offset moves -- where the kernels look for it too
-  V.levelUp = V.levelDown = -1;
-  if (h->levelFluxes) {
-    V.levelUp = level_block_offset(L.counters); o = V.levelUp + (int64_t)(h->nz + 1) * ncol;
-    V.levelDown = o; o += (int64_t)(h->nz + 1) * ncol;
-  }
-  // ... or the actinic flux's track-length sums, one word per cell, in the same place
-  h->oActinic = -1;
-  if (h->actinicFlux) { h->oActinic = level_block_offset(L.counters); o = h->oActinic + ncell; }
-  L.total = o;
-  V.nx = h->nx; V.ny = h->ny; V.nz = h->nz; V.ncomp = h->ncomp; V.nDir = h->nDir; V.xyRegular = h->xyRegular;
+  (void)tally_layout(h->nx, h->ny, h->nz, h->ncomp, h->nDir, h->extra, h->layout, V);
+  V.xyRegular = h->xyRegular;
   V.areaFrac = h->areaFrac.data(); V.dz = h->layerDepth.data();
 }
+// where the actinic flux's track-length sums lie in the packed buffer, -1 while they are off
+static int64_t track_block(const i3rc_hip_integrator *h) { return h->extra == EXTRA_TRACKS ? extra_block_offset(h->layout.counters) : -1; }
 
 // The handle's view as a call finds it: whether limited contributions are redistributed is a parameter (i3rc_hip_set_params), which
 // changes without the layout.
@@ -278,6 +257,34 @@ static void drop_lookahead(i3rc_hip_integrator *h) {
   }
   h->aheadQueue.clear();
   h->aheadSig.set = false; h->lastSig.set = false;
+}
+
+// The words in which the error texts speak of each kind of the optional diagnostic tally
+struct ExtraWords { const char *setter, *noun, *are, *need, *them, *their, *possessive; };
+static const ExtraWords kExtraWords[] = {
+    {},
+    {"i3rc_hip_set_level_fluxes", "level fluxes", "are", "need", "them", "their", "the level fluxes'"},
+    {"i3rc_hip_set_actinic_flux", "the actinic flux", "is", "needs", "it", "its", "the actinic flux's"}};
+
+// Switches one kind of the optional diagnostic tally on or off (i3rc_hip_set_level_fluxes, i3rc_hip_set_actinic_flux).
+static int set_extra_tally(i3rc_hip_integrator *h, ExtraTally kind, bool on) {
+  if (!h) return 1;
+  drop_lookahead(h);
+  if ((h->extra == kind) == on) return 0;
+  const ExtraWords &w = kExtraWords[kind];
+  if (on && h->extra != EXTRA_NONE) {   // the other kind's block lies in the same place
+    const ExtraWords &o = kExtraWords[h->extra];
+    return h->fail(std::string(w.setter) + ": " + o.noun + " " + o.are + " switched on and " + o.their + " block lies where " + w.possessive +
+                   " would; switch " + o.them + " off first (no kernel tallies both)");
+  }
+  // the tally layout changes: as for a change of nDir, a caller-bound buffer is refused before anything is touched
+  if (h->tally != (double *)h->ownTally.p)
+    return h->fail(std::string(w.setter) + ": a caller-bound tally buffer is in use; unbind it (bind NULL) before switching " + w.noun +
+                   ", then bind a buffer of the new layout's size");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // (launches in flight add to the buffer that is about to be replaced)
+  h->extra = on ? kind : EXTRA_NONE;
+  return realloc_tally(h);
 }
 
 // The slots of i3rc_hip_run_batches / i3rc_hip_compute_batch are kept with the handle (streams and pinned memory are
@@ -685,23 +692,7 @@ int i3rc_hip_zero_tallies(i3rc_hip_integrator *h) {
   return 0;
 }
 
-int i3rc_hip_set_level_fluxes(i3rc_hip_integrator *h, int on) {
-  if (!h) return 1;
-  drop_lookahead(h);
-  const bool want = on != 0;
-  if (want == h->levelFluxes) return 0;
-  if (want && h->actinicFlux)
-    return h->fail("i3rc_hip_set_level_fluxes: the actinic flux is switched on and its block lies where the level fluxes' would; "
-                   "switch it off first (no kernel tallies both)");
-  // the tally layout changes: as for a change of nDir, a caller-bound buffer is refused before anything is touched
-  if (h->tally != (double *)h->ownTally.p)
-    return h->fail("i3rc_hip_set_level_fluxes: a caller-bound tally buffer is in use; unbind it (bind NULL) before switching level fluxes, "
-                   "then bind a buffer of the new layout's size");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));   // (launches in flight add to the buffer that is about to be replaced)
-  h->levelFluxes = want;
-  return realloc_tally(h);
-}
+int i3rc_hip_set_level_fluxes(i3rc_hip_integrator *h, int on) { return set_extra_tally(h, EXTRA_LEVELS, on != 0); }
 
 int i3rc_hip_get_level_flux_layout(const i3rc_hip_integrator *h, int64_t *up, int64_t *down, int64_t *total) {
   if (!h) return 1;
@@ -711,27 +702,11 @@ int i3rc_hip_get_level_flux_layout(const i3rc_hip_integrator *h, int64_t *up, in
   return 0;
 }
 
-int i3rc_hip_set_actinic_flux(i3rc_hip_integrator *h, int on) {
-  if (!h) return 1;
-  drop_lookahead(h);
-  const bool want = on != 0;
-  if (want == h->actinicFlux) return 0;
-  if (want && h->levelFluxes)
-    return h->fail("i3rc_hip_set_actinic_flux: level fluxes are switched on and their block lies where the actinic flux's would; "
-                   "switch them off first (no kernel tallies both)");
-  // the tally layout changes: a caller-bound buffer is refused before anything is touched
-  if (h->tally != (double *)h->ownTally.p)
-    return h->fail("i3rc_hip_set_actinic_flux: a caller-bound tally buffer is in use; unbind it (bind NULL) before switching the actinic flux, "
-                   "then bind a buffer of the new layout's size");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));   // (launches in flight add to the buffer that is about to be replaced)
-  h->actinicFlux = want;
-  return realloc_tally(h);
-}
+int i3rc_hip_set_actinic_flux(i3rc_hip_integrator *h, int on) { return set_extra_tally(h, EXTRA_TRACKS, on != 0); }
 
 int i3rc_hip_get_actinic_flux_layout(const i3rc_hip_integrator *h, int64_t *offset, int64_t *total) {
   if (!h) return 1;
-  if (offset) *offset = h->oActinic;
+  if (offset) *offset = track_block(h);
   if (total) *total = h->layout.total;
   return 0;
 }
@@ -1087,7 +1062,7 @@ size_t lds_bytes(const i3rc_hip_integrator *h, const LaunchPlan &plan, bool tabl
   const LdsPlan lp = lds_plan(plan.P, plan.intensity && !Rng::kReplay, direct_rays(h), plan.place, plan.intensity, tableInLds ? 16 : 4,
                               tableInLds ? plan.P.comp0.nInv : 0, startStore);
   size_t words = (size_t)lp.end;
-  if constexpr (TrackLengths<Rng>::on)   // the track-length sums behind the plan's end (launch_tracks decides; photon_kernel, TRACK)
+  if constexpr (Rng::kExtra == EXTRA_TRACKS)   // the track-length sums behind the plan's end (launch_extra decides; photon_kernel, TRACK)
     if (plan.P.ldsGrid & kLdsGridTrackSums) words = (size_t)track_sums_word(lp.end) + 2 * (size_t)plan.P.nx * plan.P.ny * plan.P.nz;
   return (sizeof(float) * words + 15) & ~(size_t)15;
 }
@@ -1161,8 +1136,8 @@ void record_plan(i3rc_hip_integrator *h, const LaunchPlan &plan, bool tableInLds
 
 template <class Rng>
 constexpr const char *rng_name() {
-  if constexpr (LevelFluxes<Rng>::on) return "PhiloxLevelStream";
-  else if constexpr (TrackLengths<Rng>::on) return "PhiloxTrackStream";
+  if constexpr (Rng::kExtra == EXTRA_LEVELS) return "PhiloxLevelStream";
+  else if constexpr (Rng::kExtra == EXTRA_TRACKS) return "PhiloxTrackStream";
   else if constexpr (Rng::kReplay) return "ReplayStream";
   else if constexpr (Rng::kBatched) return "PhiloxBatchStream";
   else return "PhiloxStream";
@@ -1192,7 +1167,7 @@ template <class Rng>
 const std::vector<KernelEntry> &stream_kernels() {
   static const std::vector<KernelEntry> list = [] {
     std::vector<KernelEntry> v;
-    if constexpr (LevelFluxes<Rng>::on || TrackLengths<Rng>::on) {   // level fluxes, track lengths: the general flux kernel, at every place
+    if constexpr (Rng::kExtra != EXTRA_NONE) {   // an extra tally block: the general flux kernel, at every place
       add<Rng, false, true, false, false, false>(v, AllPlaces{});
     } else if constexpr (Rng::kBatched) {   // fused multi-batch launches
       add<Rng, false, false, false, false, false>(v, NoColbase{});   // flux, the common class
@@ -1221,31 +1196,19 @@ const std::vector<KernelEntry> &stream_kernels() {
   return list;
 }
 
-// Level fluxes are tallied by the general flux kernel of a plain launch, traced: what a launch must be while they are switched on.
-// Called before a launch touches anything; `who` names the entry point in the error text.
-int level_fluxes_refused(i3rc_hip_integrator *h, const char *who) {
-  if (!h->levelFluxes) return 0;
-  if (h->nDir > 0) return h->fail(std::string(who) + ": level fluxes are tallied by flux launches only; radiance directions are set (nDir > 0)");
-  if (!h->params.useRayTracing) return h->fail(std::string(who) + ": level fluxes need ray tracing; max cross-section is in use (useRayTracing = 0)");
+// An extra tally block is filled by the general flux kernel of a plain launch, traced: what a launch must be while one is switched on.
+// Called before a launch touches anything; `who` names the entry point in the error text, `batches` says that it runs a loop of
+// batches (fused or announced), which no such kernel serves.
+int extra_tally_refused(i3rc_hip_integrator *h, const char *who, bool batches) {
+  if (h->extra == EXTRA_NONE) return 0;
+  const ExtraWords &w = kExtraWords[h->extra];
+  const std::string subject = std::string(who) + ": " + w.noun + " ";
+  if (batches)
+    return h->fail(subject + w.are + " tallied by plain launches only; fused or announced batches cannot give " + w.them + " (switch " + w.them +
+                   " off, or call i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)");
+  if (h->nDir > 0) return h->fail(subject + w.are + " tallied by flux launches only; radiance directions are set (nDir > 0)");
+  if (!h->params.useRayTracing) return h->fail(subject + w.need + " ray tracing; max cross-section is in use (useRayTracing = 0)");
   return 0;
-}
-int level_fluxes_refuse_batches(i3rc_hip_integrator *h, const char *who) {
-  if (!h->levelFluxes) return 0;
-  return h->fail(std::string(who) + ": level fluxes are tallied by plain launches only; fused or announced batches cannot give them "
-                                    "(switch them off, or call i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)");
-}
-
-// The actinic flux likewise: the general flux kernel of a plain, traced launch (photon_kernel<PhiloxTrackStream, ...>).
-int actinic_flux_refused(i3rc_hip_integrator *h, const char *who) {
-  if (!h->actinicFlux) return 0;
-  if (h->nDir > 0) return h->fail(std::string(who) + ": the actinic flux is tallied by flux launches only; radiance directions are set (nDir > 0)");
-  if (!h->params.useRayTracing) return h->fail(std::string(who) + ": the actinic flux needs ray tracing; max cross-section is in use (useRayTracing = 0)");
-  return 0;
-}
-int actinic_flux_refuse_batches(i3rc_hip_integrator *h, const char *who) {
-  if (!h->actinicFlux) return 0;
-  return h->fail(std::string(who) + ": the actinic flux is tallied by plain launches only; fused or announced batches cannot give it "
-                                    "(switch it off, or call i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)");
 }
 
 struct KernelChoice {
@@ -1264,8 +1227,8 @@ KernelChoice choose_kernel(const i3rc_hip_integrator *h, const LaunchPlan &plan,
   const int place = plan.place;
   KernelKey key{plan.intensity, true, place, false, false, false};
   int threads = 256;
-  // (level fluxes, track lengths: the general flux kernel whatever the problem's class -- the key as it stands)
-  if constexpr (!Rng::kReplay && !LevelFluxes<Rng>::on && !TrackLengths<Rng>::on) {   // (the replay build always runs the general kernel: it keeps the nested local estimate, no queue at all)
+  // (an extra tally block: the general flux kernel whatever the problem's class -- the key as it stands)
+  if constexpr (!Rng::kReplay && Rng::kExtra == EXTRA_NONE) {   // (the replay build always runs the general kernel: it keeps the nested local estimate, no queue at all)
     bool simple, wide;
     if (fused) {
       // the widened class (several components, irregular x / y, a gridded surface): its own fused kernels, flux ones too -- a driver's
@@ -1790,15 +1753,12 @@ void top_up_groups(i3rc_hip_integrator *h, uint32_t seed0, uint32_t nextIfNone, 
 // that a column's sum could leave the range where float32 still counts (2^24).  Per-photon random streams make a
 // long batch the same as several launches over consecutive photon ranges, so very long Directional batches are cut
 // into launches of at most 2^22 photons per compute unit (about 1e9 photons on an MI355X).
-int launch_levels(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt);   // (at the end of this file)
-int launch_tracks(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt);   // (likewise)
+int launch_extra(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt);   // (at the end of this file)
 int launch_batch_parts(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
   const int64_t perLaunch = h->launchLimit > 0 ? h->launchLimit : (int64_t)h->numCU << 22;
-  // (level fluxes switched on: the same photons through photon_kernel<PhiloxLevelStream, ...>, see launch_levels)
-  // (the actinic flux: photon_kernel<PhiloxTrackStream, ...>, see launch_tracks)
+  // (an extra tally block switched on: the same photons through the general flux kernel under the kind's tag, see launch_extra)
   const auto run = [&](const RunArgs &part) {
-    return h->levelFluxes ? launch_levels(h, plan, part, stream, timeIt)
-                          : (h->actinicFlux ? launch_tracks(h, plan, part, stream, timeIt) : launch<PhiloxStream>(h, plan, part, stream, timeIt));
+    return h->extra == EXTRA_NONE ? launch<PhiloxStream>(h, plan, part, stream, timeIt) : launch_extra(h, plan, part, stream, timeIt);
   };
   if (A.srcKind != 0) return run(A);
   for (int64_t done = 0; done < A.nPhotons; done += perLaunch) {
@@ -1838,8 +1798,7 @@ int i3rc_hip_launch_batch(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1
   if (!h) return 1;
   if (!src) return h->fail("i3rc_hip_launch_batch: null source");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");  // illumination :78-79
-  if (level_fluxes_refused(h, "i3rc_hip_launch_batch")) return 1;
-  if (actinic_flux_refused(h, "i3rc_hip_launch_batch")) return 1;
+  if (extra_tally_refused(h, "i3rc_hip_launch_batch", false)) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   LaunchPlan plan;
   if (make_problem(h, plan, h->stream, h->tally)) return 1;
@@ -1858,8 +1817,7 @@ int i3rc_hip_run_batches(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1,
   if (!src || !hostTallies || nBatches < 1) return h->fail("i3rc_hip_run_batches: bad arguments");
   if (src->kind != 0) return h->fail("i3rc_hip_run_batches: Directional photon streams only (explicit streams differ from batch to batch)");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
-  if (level_fluxes_refuse_batches(h, "i3rc_hip_run_batches")) return 1;
-  if (actinic_flux_refuse_batches(h, "i3rc_hip_run_batches")) return 1;
+  if (extra_tally_refused(h, "i3rc_hip_run_batches", true)) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   if (fuse_loop(h, nPhotons, nBatches)) return run_batches_fused(h, seed0, seed1, nBatches, nPhotons, src, hostTallies);
   const int K = std::min(nBatches, inFlight <= 0 ? 6 : std::min(inFlight, (int)i3rc_hip_integrator::kMaxInFlight));
@@ -1904,8 +1862,7 @@ int i3rc_hip_run_batches_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_
   if (!src || !sum || !sumSquares || nBatches < 1) return h->fail("i3rc_hip_run_batches_moments: bad arguments");
   if (src->kind != 0) return h->fail("i3rc_hip_run_batches_moments: Directional photon streams only (explicit streams differ from batch to batch)");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
-  if (level_fluxes_refuse_batches(h, "i3rc_hip_run_batches_moments")) return 1;
-  if (actinic_flux_refuse_batches(h, "i3rc_hip_run_batches_moments")) return 1;
+  if (extra_tally_refused(h, "i3rc_hip_run_batches_moments", true)) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   drop_lookahead(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1942,11 +1899,10 @@ int i3rc_hip_compute_batch(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed
   if (!src || !hostTallies) return h->fail("i3rc_hip_compute_batch: bad arguments");
   if (src->kind != 0) return h->fail("i3rc_hip_compute_batch: Directional photon streams only");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
-  if (level_fluxes_refused(h, "i3rc_hip_compute_batch")) return 1;
-  if (actinic_flux_refused(h, "i3rc_hip_compute_batch")) return 1;
+  if (extra_tally_refused(h, "i3rc_hip_compute_batch", false)) return 1;
   HIPCHK(h, hipSetDevice(h->device));
-  // (level fluxes switched on: no look-ahead -- one launch per call)
-  const int depth = h->levelFluxes || h->actinicFlux ? 0 : std::max(0, std::min(lookAhead, (int)i3rc_hip_integrator::kMaxInFlight - 1));
+  // (an extra tally block switched on: no look-ahead -- one launch per call)
+  const int depth = h->extra != EXTRA_NONE ? 0 : std::max(0, std::min(lookAhead, (int)i3rc_hip_integrator::kMaxInFlight - 1));
   const size_t bytes = (size_t)h->layout.total * sizeof(double);
   if (reset_slots_if_layout_changed(h)) return 1;   // (a change of the layout has dropped the queue already: set_directions)
   auto free_slot = [&]() -> int {
@@ -2025,8 +1981,7 @@ int i3rc_hip_expect_batches(i3rc_hip_integrator *h, uint32_t seed0, uint32_t see
   if (!src || nBatches < 1) return h->fail("i3rc_hip_expect_batches: bad arguments");
   if (src->kind != 0) return h->fail("i3rc_hip_expect_batches: Directional photon streams only");
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
-  if (level_fluxes_refuse_batches(h, "i3rc_hip_expect_batches")) return 1;
-  if (actinic_flux_refuse_batches(h, "i3rc_hip_expect_batches")) return 1;
+  if (extra_tally_refused(h, "i3rc_hip_expect_batches", true)) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   drop_lookahead(h);
   if (!fuse_loop(h, nPhotons, nBatches)) return 0;   // (the caller goes on as it would have)
@@ -2053,7 +2008,7 @@ int i3rc_hip_run_replay(i3rc_hip_integrator *h, int64_t nPhotons, const i3rc_sou
                         int32_t *fateOrder, int32_t *drawsUsed) {
   if (!h) return 1;
   if (!src || !randoms || !drawStart || nPhotons <= 0) return h->fail("i3rc_hip_run_replay: bad arguments");
-  if (h->actinicFlux) return h->fail("i3rc_hip_run_replay: the actinic flux is tallied by the production stream's kernels only; the replay build has no such kernel (switch it off)");
+  if (h->extra == EXTRA_TRACKS) return h->fail("i3rc_hip_run_replay: the actinic flux is tallied by the production stream's kernels only; the replay build has no such kernel (switch it off)");
   HIPCHK(h, hipSetDevice(h->device));
   LaunchPlan plan;
   if (make_problem(h, plan, h->stream, h->tally, false, true)) return 1;
@@ -2286,7 +2241,7 @@ int i3rc_hip_normalise(const i3rc_hip_integrator *h, const double *t, float *flu
 
 int i3rc_hip_normalise_level_fluxes(const i3rc_hip_integrator *h, const double *t, float *levelFluxUp, float *levelFluxDown) {
   if (!h || !t) return 1;
-  if (!h->levelFluxes) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_level_fluxes: level fluxes are not switched on");
+  if (h->extra != EXTRA_LEVELS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_level_fluxes: level fluxes are not switched on");
   const TallyView &V = h->view;
   const size_t ncol = (size_t)h->nx * h->ny;
   for (size_t e = 0; e < (size_t)(h->nz + 1) * ncol; ++e) {   // (level after level, as the block is laid out)
@@ -2298,32 +2253,37 @@ int i3rc_hip_normalise_level_fluxes(const i3rc_hip_integrator *h, const double *
 
 int i3rc_hip_normalise_actinic_flux(const i3rc_hip_integrator *h, const double *t, float *actinicFlux) {
   if (!h || !t || !actinicFlux) return 1;
-  if (!h->actinicFlux) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_actinic_flux: the actinic flux is not switched on");
+  if (h->extra != EXTRA_TRACKS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_actinic_flux: the actinic flux is not switched on");
   const TallyView &V = h->view;
   const size_t ncol = (size_t)h->nx * h->ny;
   for (int kz = 0; kz < h->nz; ++kz)
-    for (size_t k = 0; k < ncol; ++k) actinicFlux[(size_t)kz * ncol + k] = normalised_actinic_flux(V, t, h->oActinic, kz, k);
+    for (size_t k = 0; k < ncol; ++k) actinicFlux[(size_t)kz * ncol + k] = normalised_actinic_flux(V, t, track_block(h), kz, k);
   return 0;
 }
 
 }  // extern "C"
 
 namespace {
-// The launch of photon_kernel<PhiloxLevelStream, ...> through the one path every plain launch takes (defined last, so that the level
-// kernels are instantiated behind every other kernel of the library).
-int launch_levels(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
-  return launch<PhiloxLevelStream>(h, plan, A, stream, timeIt);
-}
-// ... and of photon_kernel<PhiloxTrackStream, ...> (the actinic flux), behind those.  Where the field itself lies in LDS, partial sums in
-// LDS are switched on (i3rc_hip_set_lds_tallies, I3RC_LDS_TALLIES) and the launch's allocation has room for one more float64 word per
-// cell behind the plan's end, the workgroups keep their track-length sums there: bit 1 of ldsGrid tells the kernel, the last plan says so.
-int launch_tracks(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
-  static const bool ldsTalliesEnv = env_on("I3RC_LDS_TALLIES");
-  LaunchPlan p = plan;
-  if (p.place == GRID_LDS && ldsTalliesEnv && h->ldsTalliesOn) {
-    p.P.ldsGrid |= kLdsGridTrackSums;
-    if (lds_bytes<PhiloxTrackStream>(h, p, false, false) > kLdsLaunchMax) p.P.ldsGrid &= ~kLdsGridTrackSums;
+// The launch of the general flux kernel under the tag of the handle's extra tally block, through the one path every plain launch
+// takes (defined last, so that these kernels are instantiated behind every other kernel of the library: the level kernels, then the
+// track kernels).
+int launch_extra(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
+  switch (h->extra) {
+    case EXTRA_LEVELS: return launch<PhiloxLevelStream>(h, plan, A, stream, timeIt);
+    case EXTRA_TRACKS: {
+      // Where the field itself lies in LDS, partial sums in LDS are switched on (i3rc_hip_set_lds_tallies, I3RC_LDS_TALLIES) and the
+      // launch's allocation has room for one more float64 word per cell behind the plan's end, the workgroups keep their track-length
+      // sums there: bit 1 of ldsGrid tells the kernel, the last plan says so.
+      static const bool ldsTalliesEnv = env_on("I3RC_LDS_TALLIES");
+      LaunchPlan p = plan;
+      if (p.place == GRID_LDS && ldsTalliesEnv && h->ldsTalliesOn) {
+        p.P.ldsGrid |= kLdsGridTrackSums;
+        if (lds_bytes<PhiloxTrackStream>(h, p, false, false) > kLdsLaunchMax) p.P.ldsGrid &= ~kLdsGridTrackSums;
+      }
+      return launch<PhiloxTrackStream>(h, p, A, stream, timeIt);
+    }
+    case EXTRA_NONE: break;
   }
-  return launch<PhiloxTrackStream>(h, p, A, stream, timeIt);
+  return h->fail("internal: no extra tally block is switched on");
 }
 }  // namespace

@@ -28,6 +28,7 @@
 //   * work counters live in scalar registers (advanced by s_bcnt1 of ballots in uniform control flow).
 #pragma once
 #include <cstddef>
+#include "tally_block.hpp"
 #include "tracer.hpp"
 #include "tuning.hpp"
 
@@ -190,10 +191,9 @@ __device__ __forceinline__ void intensity_contribution(const PR &P, const Lds &L
   }
 }
 
+// (the primary template: the production stream, and with it the tag types derived from it)
 template <class Rng>
-struct RngInit;
-template <>
-struct RngInit<PhiloxStream> {
+struct RngInit {
   static __device__ __forceinline__ void init(PhiloxStream &g, const RunArgs &A) { g.init(A.seed0, A.seed1); }
   template <class AR>
   static __device__ __forceinline__ void start(PhiloxStream &g, const AR &A, long long i) {
@@ -210,24 +210,20 @@ struct RngInit<ReplayStream> {
   template <class AR>
   static __device__ __forceinline__ void start(ReplayStream &g, const AR &A, long long i) { g.start(A.drawStart[i]); }
 };
-template <>
-struct RngInit<PhiloxLevelStream> : RngInit<PhiloxStream> {};
-template <>
-struct RngInit<PhiloxTrackStream> : RngInit<PhiloxStream> {};
 
-// LEVEL FLUXES: upward and downward flux through every layer interface, per column (levelFluxUp / levelFluxDown [nz + 1][ny][nx],
-// level k = zEdges[k]).  photon_kernel<PhiloxLevelStream, false, true, GRID> -- the general flux kernel, the production stream under a
-// tag of its own -- tallies them at EVENT time from what the lane holds when its photon arrives: the weight (constant along the
+// THE OPTIONAL DIAGNOSTIC TALLY (ExtraTally, tally_block.hpp): photon_kernel<tag, false, true, GRID> -- the general flux kernel, the
+// production stream under a tag type whose kExtra names the kind -- also fills one more block behind the counters of the packed tally
+// buffer.  Where that block begins, for every kind:
+__device__ __forceinline__ double *extra_block(double *tallyBase, long long countersOffset) { return tallyBase + extra_block_offset(countersOffset); }
+
+// LEVEL FLUXES (EXTRA_LEVELS, PhiloxLevelStream): upward and downward flux through every layer interface, per column (levelFluxUp / levelFluxDown [nz + 1][ny][nx],
+// level k = zEdges[k]).  The kernel tallies them at EVENT time from what the lane holds when its photon arrives: the weight (constant along the
 // straight segment just traced), the direction, the arrival position and the layer the segment began in (one more register).  The
 // tracer is not touched.  A segment from layer a to layer b (the tracer's own 1-based indices; nz + 1: out through the top, 0: onto
 // the surface) adds its weight to levelFluxUp[a ... b - 1] going up, to levelFluxDown[b ... a - 1] going down; a new photon is
 // counted at the face of its start layer that lies behind it, a reflected one at level 0, both in the tracer's own column.  The
-// block lies behind the counters of the packed tally buffer (level_block_offset) and is added to with float64 atomics in global
-// memory: no LDS carve-up changes.
-template <class Rng> struct LevelFluxes { static constexpr bool on = false; };
-template <> struct LevelFluxes<PhiloxLevelStream> { static constexpr bool on = true; };
-// offset of levelFluxUp in the packed tally buffer, levelFluxDown (nz + 1) * nx * ny words behind it -- the host's layout and the kernels' both
-__host__ __device__ inline long long level_block_offset(long long countersOffset) { return countersOffset + I3RC_NUM_COUNTERS; }
+// block -- levelFluxUp, levelFluxDown (nz + 1) * nx * ny words behind it -- is added to with float64 atomics in global memory: no LDS
+// carve-up changes.
 
 // The crossings of one straight segment that arrived at (x, y, z) in column `colArr`, layer index `izTo`, from layer `izFrom` with
 // weight w.  The crossing point of level k is extrapolated BACK from the arrival along the direction and wrapped periodically with one
@@ -263,21 +259,18 @@ __device__ __forceinline__ void tally_level_crossings(const PR &P, const Lds &L,
   }
 }
 
-// ACTINIC FLUX by photon track length: for every cell the sum, over all pieces of photon paths inside it, of w * l -- w the weight the
+// ACTINIC FLUX by photon track length (EXTRA_TRACKS, PhiloxTrackStream): for every cell the sum, over all pieces of photon paths inside it, of w * l -- w the weight the
 // photon carries along the piece (before the event at its end), l the float32 length the tracer itself steps -- as one float64 word per
 // cell [nz][ny][nx]; normalised_actinic_flux (tally_block.hpp) turns it into the cell's mean actinic flux in units of the incident
-// flux.  photon_kernel<PhiloxTrackStream, false, true, GRID> -- the general flux kernel under one more tag -- tallies it in the
-// VOXEL-STEP phase: every step that is no tracer error adds w * step to the cell the photon was in BEFORE the step (trace_step_lazy,
+// flux.  The kernel tallies it in the VOXEL-STEP phase: every step that is no tracer error adds w * step to the cell the photon was in BEFORE the step (trace_step_lazy,
 // LENGTH), whether it reaches a face, snaps an index, wraps or leaves the grid; the arriving step advances nothing there, its length
 // is the part finish_arrival forms in the event phase, tallied in the cell the photon stands in with the weight before the
-// scattering.  The block lies where the level fluxes' does -- behind the counters (level_block_offset): the two are never on together.
+// scattering.
 // Where the field itself lies in LDS (GRID_LDS) and the launch has ncell * 8 more bytes of it, a workgroup keeps partial sums there
 // (ds_add_f64 per step, one global atomic per non-zero word at its end): a small domain's few hundred words take a tenth of the
 // scattered atomic rate in global memory, and a photon makes some sixty steps into them.  The region is carved BEHIND what lds_plan
 // returns as its end, 8-byte aligned, in this instantiation and its launch alone; the host says so in bit 1 of DevProblem::ldsGrid,
 // which no kernel reads otherwise.  Elsewhere: float64 atomics in global memory.
-template <class Rng> struct TrackLengths { static constexpr bool on = false; };
-template <> struct TrackLengths<PhiloxTrackStream> { static constexpr bool on = true; };
 constexpr int kLdsGridTrackSums = 2;   // DevProblem::ldsGrid, bit 1 (launches of photon_kernel<PhiloxTrackStream, ...> only)
 // first word of the track sums in a launch's dynamic LDS, given the end of its lds_plan -- the host's allocation and the kernel's pointer both
 __host__ __device__ inline int track_sums_word(int planEnd) { return (planEnd + 1) & ~1; }
@@ -456,7 +449,7 @@ struct WaveStartState {
 // of the instantiation, derived from its template arguments: the host sizes the launch's LDS by the same function.
 template <class Rng>
 constexpr bool has_start_store(bool intensity, bool general, int grid, bool multi) {
-  return !Rng::kReplay && !Rng::kBatched && !LevelFluxes<Rng>::on && !TrackLengths<Rng>::on && !intensity && !general && !multi && grid != GRID_BRICKS;
+  return !Rng::kReplay && !Rng::kBatched && Rng::kExtra == EXTRA_NONE && !intensity && !general && !multi && grid != GRID_BRICKS;
 }
 // GENERAL = false is the specialisation for the common problem class -- regular grid, ray tracing, one component,
 // Lambertian albedo (no BRDF grid), Directional source, production RNG: the rare paths (grid searches, periodic
@@ -485,7 +478,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   Lds L;
   constexpr bool STORE = has_start_store<Rng>(INTENSITY, GENERAL, GRID, MULTI);   // photons start a wavefront at a time: part B of the event phase
   lds_float *startSlots = nullptr;   // STORE: this wave's start store (StartSlot, tracer.hpp)
-  constexpr bool TRACK = TrackLengths<Rng>::on;   // actinic flux by track length (PhiloxTrackStream): tallied by the general flux kernel only
+  constexpr bool TRACK = Rng::kExtra == EXTRA_TRACKS;   // actinic flux by track length (PhiloxTrackStream): tallied by the general flux kernel only
   lds_f64 *trackSums = nullptr;      // TRACK: the workgroup's partial sums of the block (nullptr: the block in global memory is added to)
   {
     // (one carve-up for the kernel and for the host's allocation: lds_plan, tracer.hpp)
@@ -542,7 +535,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   constexpr bool REPLAY = Rng::kReplay;        // per-photon fates are recorded by i3rc_hip_run_replay only
   constexpr bool BATCHED = Rng::kBatched;      // fused multi-batch launch: every lane knows its photon's batch (rng.batch)
   static_assert(!BATCHED || !GENERAL, "fused multi-batch launches: specialised kernels");
-  constexpr bool LEVELS = LevelFluxes<Rng>::on;   // level fluxes (PhiloxLevelStream): tallied by the general flux kernel only
+  constexpr bool LEVELS = Rng::kExtra == EXTRA_LEVELS;   // level fluxes (PhiloxLevelStream): tallied by the general flux kernel only
   static_assert(!LEVELS || (GENERAL && !INTENSITY && !TBL && !DIRECT && !MULTI), "level fluxes: the general flux kernel");
   static_assert(!TRACK || (GENERAL && !INTENSITY && !TBL && !DIRECT && !MULTI && !STORE && !BATCHED && !REPLAY && !LEVELS),
                 "track lengths: the general flux kernel, no start store, not batched");
@@ -1090,7 +1083,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
         if (wantEvent && st == ST_EVENT && arrival_pending(r)) {
           float part = 0.0f;
           finish_arrival<true>(r, &part);
-          track_add(trackSums, tally.base() + level_block_offset(Pe.oCnt), cell_index(Pe, r.ix, r.iy, r.iz), Pe.nx * Pe.ny * Pe.nz, w, part);
+          track_add(trackSums, extra_block(tally.base(), Pe.oCnt), cell_index(Pe, r.ix, r.iy, r.iz), Pe.nx * Pe.ny * Pe.nz, w, part);
         }
       } else
       if (wantEvent && st == ST_EVENT && arrival_pending(r)) finish_arrival(r);
@@ -1110,7 +1103,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
         // photon's segment tallies nothing).  The layers are the tracer's; an arrival that the tests above take for the top or the
         // surface ends on that level, so that levelFluxUp[nz] / levelFluxDown[0] get what fluxUp / fluxDown get below.
         if (isEv)
-          tally_level_crossings(Pe, L, tally.base() + level_block_offset(Pe.oCnt), r.x, r.y, atTop ? Pe.zMax : r.z, r.dx, r.dy, r.dz, izFrom,
+          tally_level_crossings(Pe, L, extra_block(tally.base(), Pe.oCnt), r.x, r.y, atTop ? Pe.zMax : r.z, r.dx, r.dy, r.dz, izFrom,
                                 atTop ? Pe.nz + 1 : (atSurface ? 0 : r.iz), (r.iy - 1) * Pe.nx + (r.ix - 1), r.ix, r.iy, w);
       }
       wc.dropped += count_lanes(dropped);
@@ -1344,7 +1337,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           if constexpr (LEVELS) {   // a new photon is counted at the face of its start layer that lies behind it (a source at the top: level nz, downward)
             const bool down = !(r.dz > 0.0f);
             const int k = min(max(down ? r.iz : r.iz - 1, 0), Pe.nz), ncolL = Pe.nx * Pe.ny;
-            add_global(tally.base() + level_block_offset(Pe.oCnt) + (size_t)((down ? Pe.nz + 1 : 0) + k) * ncolL + ((r.iy - 1) * Pe.nx + (r.ix - 1)), w);
+            add_global(extra_block(tally.base(), Pe.oCnt) + (size_t)((down ? Pe.nz + 1 : 0) + k) * ncolL + ((r.iy - 1) * Pe.nx + (r.ix - 1)), w);
           }
           st = ST_TRACE;
         }
@@ -1378,7 +1371,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
               if (defer) { pendingShadow = true; wI = w; evInfo = EventInfo::kSurface; }
               else if (INTENSITY)
                 intensity_contribution<GRID>(Pe, L, rng, nested, w, r.x, r.y, r.z, r.ix, r.iy, r.iz, r.dx, r.dy, r.dz, 0, order);
-              if constexpr (LEVELS) add_global(tally.base() + level_block_offset(Pe.oCnt) + c2, w);   // levelFluxUp[0]: the reflected weight, where it was reflected
+              if constexpr (LEVELS) add_global(extra_block(tally.base(), Pe.oCnt) + c2, w);   // levelFluxUp[0]: the reflected weight, where it was reflected
               st = ST_TRACE;
             }
           } else {                                                        // :581-689
@@ -1593,7 +1586,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           const int cell = cell_index(P, r.ix, r.iy, r.iz);
           float len = 0.0f;
           s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, true>(P, L, r, true, &len);
-          if (s == STEP_CONTINUE || s == STEP_EXIT) track_add(trackSums, P.tally + level_block_offset(P.oCnt), cell, P.nx * P.ny * P.nz, w, len);
+          if (s == STEP_CONTINUE || s == STEP_EXIT) track_add(trackSums, extra_block(P.tally, P.oCnt), cell, P.nx * P.ny * P.nz, w, len);
         } else
         s = trace_step_lazy<GRID, !INTENSITY, GENERAL>(P, L, r, true);   // (an arrival is finished by the event phase)
         if (GENERAL && s == STEP_EXIT) finish_exit(P, r);
@@ -1647,7 +1640,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
     }
     if constexpr (TRACK)
       if (trackSums != nullptr) {
-        double *const block = out + level_block_offset(ka->P.oCnt);
+        double *const block = extra_block(out, ka->P.oCnt);
         const int ncellT = ka->P.nx * ka->P.ny * ka->P.nz;
         for (int i = threadIdx.x; i < ncellT; i += blockDim.x) {
           const double v = trackSums[i];

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tally_block.hpp"
+
 namespace i3rc {
 
 struct Philox4 { uint32_t v[4]; };
@@ -85,6 +87,7 @@ template <bool BATCHED>
 struct PhiloxStreamT {
   static constexpr bool kReplay = false;
   static constexpr bool kBatched = BATCHED;
+  static constexpr ExtraTally kExtra = EXTRA_NONE;   // the optional diagnostic tally the kernels of this stream fill (tally_block.hpp)
   uint32_t k0, k1;           // key: the same for every photon of a launch (wave-uniform, lives in scalar registers)
   uint32_t batch;            // BATCHED: batch of this lane's photon, relative to the launch's first (else unused, 0)
   uint32_t id_lo, id_hi, block;
@@ -171,18 +174,18 @@ struct PhiloxStreamT {
 // (types of their own, not aliases: kernel names -- rocprofv3, tools/kernel_resources.py -- keep the plain form)
 struct PhiloxStream : PhiloxStreamT<false> {};
 struct PhiloxBatchStream : PhiloxStreamT<true> {};
-// The production stream once more, as a TAG: photon_kernel<PhiloxLevelStream, ...> draws what photon_kernel<PhiloxStream, ...> draws and
-// also tallies the upward and downward flux through every layer interface (kernels.hpp, LevelFluxes).  A stream type and not a template
-// parameter of the kernel: the kernel's parameter list, and with it every other instantiation's name, stays as it is.
-struct PhiloxLevelStream : PhiloxStream {};
-// ... and once more: photon_kernel<PhiloxTrackStream, ...> also tallies every cell's actinic flux by photon track length (kernels.hpp,
-// TrackLengths).  (The name begins with neither "PhiloxStream" nor "PhiloxBatchStream": the kernel audits count kernels by those prefixes.)
-struct PhiloxTrackStream : PhiloxStream {};
+// The production stream once more, as a TAG per kind of the optional diagnostic tally (ExtraTally, tally_block.hpp): photon_kernel<tag, ...>
+// draws what photon_kernel<PhiloxStream, ...> draws and also fills the block of the tag's kExtra (kernels.hpp).  A stream type and not a
+// template parameter of the kernel: the kernel's parameter list, and with it every other instantiation's name, stays as it is.  (The
+// names begin with neither "PhiloxStream" nor "PhiloxBatchStream": the kernel audits count kernels by those prefixes.)
+struct PhiloxLevelStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_LEVELS; };
+struct PhiloxTrackStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_TRACKS; };
 
 // Test stream: deviates come from a buffer (the reference's MT19937 floats); see i3rc_hip_run_replay.
 struct ReplayStream {
   static constexpr bool kReplay = true;   // consume deviates exactly where the reference does
   static constexpr bool kBatched = false;
+  static constexpr ExtraTally kExtra = EXTRA_NONE;
   const float *buf;
   int64_t pos, end;
   int64_t photonStart;

@@ -16,13 +16,51 @@ namespace i3rc {
 
 // Passed by value, also as a kernel argument; the two arrays are host memory on the host and device memory in a kernel.
 struct TallyView {
-  // offsets in float64 elements (i3rc_tally_layout; the level block lies behind the counters, -1 while it is switched off)
+  // offsets in float64 elements (tally_layout below; the level block lies behind the counters, -1 while it is switched off)
   long long fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, intensityByComponent, intensityExcess, counters, levelUp, levelDown;
   int nx, ny, nz, ncomp, nDir, xyRegular;
   int limitContrib;         // the excess of limited radiance contributions is redistributed (:327-347)
   const double *areaFrac;   // [nx * ny] column area / domain area (:358-366; read on irregular grids only)
   const double *dz;         // [nz] layer depths (:378-381)
 };
+
+// THE OPTIONAL DIAGNOSTIC TALLY: at most one more block, behind the counters of the packed tally buffer, that the general flux kernel of
+// a plain, traced launch fills under a tag type of the production stream (philox.hpp, kExtra).  Which one is on is one value, on the
+// handle and in the kernels alike; the kinds are never on together, so the block of either begins at the same word.
+enum ExtraTally {
+  EXTRA_NONE,
+  EXTRA_LEVELS,   // levelFluxUp | levelFluxDown, [nz + 1][ny][nx] each (i3rc_hip_set_level_fluxes)
+  EXTRA_TRACKS    // the actinic flux's track-length sums, [nz][ny][nx] (i3rc_hip_set_actinic_flux)
+};
+I3RC_TALLY_FN long long extra_block_offset(long long countersOffset) { return countersOffset + I3RC_NUM_COUNTERS; }
+// ... and its length in float64 words
+I3RC_TALLY_FN long long extra_block_words(ExtraTally kind, int nx, int ny, int nz) {
+  const long long ncol = (long long)nx * ny;
+  return kind == EXTRA_LEVELS ? 2 * (nz + 1) * ncol : (kind == EXTRA_TRACKS ? ncol * nz : 0);
+}
+
+// The packed tally buffer of a grid: the fields of i3rc_tally_layout one behind the other, then the extra block, so that switching it
+// moves no other offset.  Fills L, and V's offsets and sizes (levelUp / levelDown: -1 unless the block is EXTRA_LEVELS); returns the
+// extra block's offset, -1 without one.
+inline long long tally_layout(int nx, int ny, int nz, int ncomp, int nDir, ExtraTally extra, i3rc_tally_layout &L, TallyView &V) {
+  const long long ncol = (long long)nx * ny;
+  long long o = 0;
+  L.fluxUp = o; o += ncol;
+  L.fluxDown = o; o += ncol;
+  L.fluxAbsorbed = o; o += ncol;
+  L.volumeAbsorption = o; o += ncol * nz;
+  L.intensityByComponent = o; o += (long long)(ncomp + 1) * nDir * ncol;
+  L.intensityExcess = o; o += (long long)(ncomp + 1) * nDir;
+  L.counters = o; o += I3RC_NUM_COUNTERS;
+  const long long block = extra == EXTRA_NONE ? -1 : extra_block_offset(L.counters);
+  L.total = o + extra_block_words(extra, nx, ny, nz);
+  V.fluxUp = L.fluxUp; V.fluxDown = L.fluxDown; V.fluxAbsorbed = L.fluxAbsorbed; V.volumeAbsorption = L.volumeAbsorption;
+  V.intensityByComponent = L.intensityByComponent; V.intensityExcess = L.intensityExcess; V.counters = L.counters;
+  V.levelUp = extra == EXTRA_LEVELS ? block : -1;
+  V.levelDown = extra == EXTRA_LEVELS ? block + (nz + 1) * ncol : -1;
+  V.nx = nx; V.ny = ny; V.nz = nz; V.ncomp = ncomp; V.nDir = nDir;
+  return block;
+}
 
 // What the rule needs of the grid, from its float32 edges: every column's share of the domain's area and every layer's depth.
 inline void grid_fractions(int nx, int ny, int nz, const float *xE, const float *yE, const float *zE, double *areaFrac, double *dz) {
@@ -48,7 +86,7 @@ I3RC_TALLY_FN float normalised_volume_absorption(const TallyView &V, const doubl
   return (float)(raw[V.volumeAbsorption + kz * ncol + col] / (photons_per_column(V, raw, col) * V.dz[kz]));
 }
 
-// The cell-mean actinic flux from the track-length sums (the block of nx * ny * nz words at `block`, [nz][ny][nx]: i3rc_hip_set_actinic_flux):
+// The cell-mean actinic flux from the track-length sums (the EXTRA_TRACKS block at `block`, [nz][ny][nx]):
 // per photon of the column and per unit of the layer's depth, as volumeAbsorption -- 1 in clear air under a zenith sun, in units of the
 // incident flux on a horizontal surface.
 I3RC_TALLY_FN float normalised_actinic_flux(const TallyView &V, const double *raw, long long block, int kz, long long col) {

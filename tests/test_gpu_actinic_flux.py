@@ -20,6 +20,7 @@ step or scattering of the run, so its order bound counts the voxel steps as well
 rule of tests.test_gpu_parity._assert_3sigma per cell, or 4 standard errors of the batch means, the solver comparison with the 3e-5
 tests/test_plane_parallel.py allows for what the solver does not model."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -27,8 +28,8 @@ import pytest
 
 import i3rc_monte_carlo_model_amd as M
 from tests import kernel_matrix as K
+from tests.extra_tally import IRREGULAR_Z, N, PLACES, old as _old, run, step_cloud_3d as _step_cloud_3d
 from tests.sums import assert_same_sums
-from tests.test_gpu_level_fluxes import IRREGULAR_Z, PLACES, _step_cloud_3d
 from tests.test_gpu_parity import _assert_3sigma, hg_table, make_gpu
 from tools import cases
 
@@ -37,11 +38,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 SEED = (29, 6)
-N = 30_001          # a multiple of neither the 256-photon chunk nor a workgroup
-
-
-def _run(g, n=N, seed=SEED, sun=K.SOURCE):
-    return g.computeRadiativeTransfer(M.new_RandomNumberSequence(seed), M.new_PhotonStream(sun[0], sun[1], n))
+_run = functools.partial(run, seed=SEED)
 
 
 def _block(g, res):
@@ -50,11 +47,6 @@ def _block(g, res):
     n = g.nz * g.ny * g.nx
     assert off == g.layout().counters + M.binding.NUM_COUNTERS and total == off + n == len(res["raw"]) == g.layout().total, (off, total, len(res["raw"]))
     return res["raw"][off:off + n].reshape(g.nz, g.ny, g.nx)
-
-
-def _old(g, res):
-    """the tallies the handle had before the feature: everything in front of the counters"""
-    return res["raw"][:g.layout().counters]
 
 
 def _track_counters(c):

@@ -18,6 +18,7 @@ A scattering makes w' = fl32(w omega) and tallies fl32(w fl32(1 - omega)): witho
 scatterings 2^-24 (largest weight 1) plus the order term of the float64 sums.  Statistical comparisons: 4 standard errors (binomial, or
 of the batch means), the solver comparison with its 3e-5 for what the solver does not model (tests/test_plane_parallel.py)."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -26,6 +27,7 @@ import pytest
 
 import i3rc_monte_carlo_model_amd as M
 from tests import kernel_matrix as K
+from tests.extra_tally import IRREGULAR_Z, N, PLACES, old as _old, run, step_cloud_3d as _step_cloud_3d
 from tests.sums import assert_same_sums, order_rtol
 from tests.test_gpu_parity import _assert_3sigma, hg_table, make_gpu
 from tools import cases
@@ -35,11 +37,11 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 SEED = (23, 4)
-N = 30_001          # a multiple of neither the 256-photon chunk nor a workgroup
 U = 2.0 ** -24      # unit roundoff of float32
 # The exact balances hold for any number of photons, and they want a run without a dropped photon (the reference's tracer error, Q4:
 # about one in 2.6e6 traces on these domains, counted with the CPU oracle): a few thousand photons, some 2e5 traces
 N_EXACT = 6_001
+_run = functools.partial(run, seed=SEED)
 
 
 def _levels(g, res):
@@ -50,20 +52,10 @@ def _levels(g, res):
     return res["raw"][up:up + n].reshape(g.nz + 1, g.ny, g.nx), res["raw"][down:down + n].reshape(g.nz + 1, g.ny, g.nx)
 
 
-def _old(g, res):
-    """the tallies the handle had before the feature: everything in front of the counters"""
-    lay = g.layout()
-    return res["raw"][:lay.counters]
-
-
 def _field(g, res, name):
     lay, ncol = g.layout(), g.nx * g.ny
     o = getattr(lay, name)
     return res["raw"][o:o + ncol].reshape(g.ny, g.nx)
-
-
-def _run(g, n=N, seed=SEED, sun=K.SOURCE):
-    return g.computeRadiativeTransfer(M.new_RandomNumberSequence(seed), M.new_PhotonStream(sun[0], sun[1], n))
 
 
 def _check_boundaries(g, res):
@@ -74,9 +66,6 @@ def _check_boundaries(g, res):
 
 
 # ---- 4, 5: the same photons, once per place of the extinction field ------------------------------------------------------------------
-PLACES = list(zip(K.PLACES, ("two", "three", "step_records", "columns2", "colbase2")))   # the general flux kernel's recipes
-
-
 @pytest.mark.parametrize("place,domain", PLACES, ids=[p for p, _ in PLACES])
 def test_same_photons_as_the_general_kernel(place, domain):
     d, tabs = K.DOMAINS[domain]()
@@ -208,9 +197,6 @@ def test_conservation_with_the_roulette_within_the_batch_noise():
 
 
 # ---- 7: closed forms --------------------------------------------------------------------------------------------------------------------
-IRREGULAR_Z = np.array([0.0, 12.0, 40.0, 47.0, 90.0, 131.0, 160.0, 233.0, 250.0], np.float32)   # 8 irregular layers
-
-
 def _slab(tau, ssa, nx=2, ny=2):
     ext = np.full((8, ny, nx), f32(tau) / f32(250.0), np.float32)
     return dict(xe=f32(250.0) * np.arange(nx + 1, dtype=np.float32), ye=f32(250.0) * np.arange(ny + 1, dtype=np.float32), ze=IRREGULAR_Z,
@@ -246,18 +232,6 @@ def test_empty_domain_over_a_reflecting_surface():
 
 
 # ---- 8: where a crossing lands ----------------------------------------------------------------------------------------------------------
-def _step_cloud_3d(ssa):
-    """8 x 4 x 6 cells, step-cloud-like: thin and thick columns in x, a modulation in y, a clear layer on top"""
-    nx, ny, nz = 8, 4, 6
-    col = np.where(np.arange(nx) < nx // 2, 2.0, 18.0)[None, :] * np.array([1.0, 0.5, 1.5, 0.25])[:, None] / 250.0
-    ext = np.ascontiguousarray(np.broadcast_to(col[None], (nz, ny, nx)), np.float32).copy()
-    ext[nz - 1] = 0.0
-    pf = (ext > 0).astype(np.int32)
-    return dict(xe=f32(62.5) * np.arange(nx + 1, dtype=np.float32), ye=f32(125.0) * np.arange(ny + 1, dtype=np.float32),
-                ze=np.array([0.0, 30.0, 80.0, 120.0, 170.0, 210.0, 250.0], np.float32), ext=ext,
-                ssa=np.where(ext > 0, f32(ssa), f32(0)).astype(np.float32), pf=pf)
-
-
 def _direct_beam(d, mu0, az_deg, sub=96):
     """float64 march: the mean transmission from the top to every level over the crossing points of every column.  Crossing points
     are uniform over a level (the entry points are uniform over the top); each column takes sub x sub of them; the path back up

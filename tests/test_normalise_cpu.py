@@ -3,9 +3,12 @@ program over that header alone -- against a float64 numpy restatement of compute
 
 The blocks are made here: positive float64 sums, whole-number counters, and excess entries that are positive, zero, and positive on
 component 0 (the surface).  The sum over the columns that the redistribution divides by is formed column after column on both sides
-(np.cumsum; np.sum adds pairwise).  Three cases, the smallest that reach every branch of the header: a regular grid without directions
-and with the level block; an irregular grid (unequal x, y and z spacings) with two components and two directions, contributions
-limited; the same block with the limit off."""
+(np.cumsum; np.sum adds pairwise).  Four cases, the smallest that reach every branch of the header: a regular grid without directions
+and with the level block; the same grid with the actinic flux's block (3 x 2 x 2); an irregular grid (unequal x, y and z spacings) with
+two components and two directions, contributions limited; the same block with the limit off.
+
+The block's layout is the header's too (tally_layout): the program lays the block out from the grid sizes and the kind of the extra
+block and reports the offsets and the total, which must be the ones restated here (make_block) -- in every case."""
 import os
 import shutil
 import subprocess
@@ -17,9 +20,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "i3rc-monte-carlo-model_amd", "csrc")
 NUM_COUNTERS, CNT_PHOTONS = 16, 0    # include/i3rc_hip.h
 
-REGULAR = dict(xe=[0.0, 10.0, 20.0, 30.0], ye=[0.0, 7.0, 14.0], ze=[0.0, 5.0, 10.0], ncomp=1, ndir=0, regular=1, limit=0, levels=True)
-IRREGULAR = dict(xe=[0.0, 10.0, 25.0, 31.0], ye=[-3.0, 4.5, 9.0], ze=[0.0, 0.3, 2.0], ncomp=2, ndir=2, regular=0, limit=1, levels=False)
-CASES = {"regular, level block": REGULAR, "irregular, limit on": IRREGULAR, "irregular, limit off": dict(IRREGULAR, limit=0)}
+EXTRA_NONE, EXTRA_LEVELS, EXTRA_TRACKS = 0, 1, 2    # csrc/tally_block.hpp, ExtraTally
+OFFSETS = ("fluxUp", "fluxDown", "fluxAbsorbed", "volumeAbsorption", "intensityByComponent", "intensityExcess", "counters",
+           "levelUp", "levelDown", "extra", "total")
+
+REGULAR = dict(xe=[0.0, 10.0, 20.0, 30.0], ye=[0.0, 7.0, 14.0], ze=[0.0, 5.0, 10.0], ncomp=1, ndir=0, regular=1, limit=0, extra=EXTRA_LEVELS)
+IRREGULAR = dict(xe=[0.0, 10.0, 25.0, 31.0], ye=[-3.0, 4.5, 9.0], ze=[0.0, 0.3, 2.0], ncomp=2, ndir=2, regular=0, limit=1, extra=EXTRA_NONE)
+CASES = {"regular, level block": REGULAR, "regular, actinic block": dict(REGULAR, extra=EXTRA_TRACKS), "irregular, limit on": IRREGULAR,
+         "irregular, limit off": dict(IRREGULAR, limit=0)}
 
 
 @pytest.fixture(scope="module")
@@ -31,16 +39,19 @@ def program(tmp_path_factory):
 
 
 def make_block(c):
-    """offsets (i3rc_tally_layout, the level block behind the counters), and a raw block"""
+    """offsets (i3rc_tally_layout, the extra block behind the counters), and a raw block"""
     nx, ny, nz, ncomp, ndir = len(c["xe"]) - 1, len(c["ye"]) - 1, len(c["ze"]) - 1, c["ncomp"], c["ndir"]
     ncol = nx * ny
     o, at = {}, 0
     for name, n in (("fluxUp", ncol), ("fluxDown", ncol), ("fluxAbsorbed", ncol), ("volumeAbsorption", ncol * nz),
                     ("intensityByComponent", (ncomp + 1) * ndir * ncol), ("intensityExcess", (ncomp + 1) * ndir), ("counters", NUM_COUNTERS)):
         o[name], at = at, at + n
-    o["levelUp"] = o["levelDown"] = -1
-    if c["levels"]:
-        o["levelUp"], o["levelDown"], at = at, at + (nz + 1) * ncol, at + 2 * (nz + 1) * ncol
+    o["levelUp"] = o["levelDown"] = o["extra"] = -1
+    if c["extra"] == EXTRA_LEVELS:
+        o["extra"], o["levelUp"], o["levelDown"], at = at, at, at + (nz + 1) * ncol, at + 2 * (nz + 1) * ncol
+    if c["extra"] == EXTRA_TRACKS:
+        o["extra"], at = at, at + nz * ncol
+    o["total"] = at
     rng = np.random.default_rng(20240607)
     raw = rng.uniform(0.5, 50.0, at)
     raw[o["counters"]:o["counters"] + NUM_COUNTERS] = rng.integers(1, 1000, NUM_COUNTERS)
@@ -82,16 +93,17 @@ def restated(c, o, raw):
     out.append(inten / per_col[None])                                             # :388
     byc[1:] /= per_col[None, None]                                                # :390-393, j = 1:numComponents
     out.append(byc)
-    if c["levels"]:
+    if c["extra"] == EXTRA_LEVELS:
         out += [field(k, nz + 1, ny, nx) / per_col[None] for k in ("levelUp", "levelDown")]
+    if c["extra"] == EXTRA_TRACKS:                                                # as volumeAbsorption
+        out.append(field("extra", nz, ny, nx) / (per_col[None] * (ze[1:] - ze[:-1])[:, None, None]))
     return np.concatenate([np.float32(a).ravel() for a in out])
 
 
 def run(program, c, tmp_path):
     o, raw = make_block(c)
     nx, ny, nz = len(c["xe"]) - 1, len(c["ye"]) - 1, len(c["ze"]) - 1
-    scalars = [o[k] for k in ("fluxUp", "fluxDown", "fluxAbsorbed", "volumeAbsorption", "intensityByComponent", "intensityExcess", "counters",
-                              "levelUp", "levelDown")] + [nx, ny, nz, c["ncomp"], c["ndir"], c["regular"], c["limit"], len(raw)]
+    scalars = [nx, ny, nz, c["ncomp"], c["ndir"], c["regular"], c["limit"], c["extra"]]
     src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
     with open(src, "wb") as f:
         f.write(np.array(scalars, np.int64).tobytes())
@@ -99,7 +111,9 @@ def run(program, c, tmp_path):
             f.write(np.float32(c[k]).tobytes())
         f.write(raw.tobytes())
     subprocess.check_call([program, str(src), str(dst)])
-    return o, raw, np.fromfile(dst, np.float32)
+    header = np.fromfile(dst, np.int64, len(OFFSETS))
+    assert dict(zip(OFFSETS, header.tolist())) == o, (dict(zip(OFFSETS, header.tolist())), o)   # the header's layout is the one restated here
+    return o, raw, np.fromfile(dst, np.float32, offset=header.nbytes)
 
 
 @pytest.mark.parametrize("name", list(CASES))
