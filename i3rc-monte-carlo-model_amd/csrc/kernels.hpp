@@ -148,7 +148,7 @@ __device__ __forceinline__ void intensity_contribution(const PR &P, const Lds &L
     }
     Ray r;
     r.x = x; r.y = y; r.z = z; r.ix = ix; r.iy = iy; r.iz = iz; r.dx = ux; r.dy = uy; r.dz = uz;
-    r.set_direction(L);
+    r.set_direction<true>(L);   // (the general kernels' step: see Ray::slow)
     // ONE loop over the voxel steps of all the legs of this direction, the legs told apart by `stage` as in the light
     // phase of photon_kernel (0: plain local estimate, 1: small contribution, 2 / 3: the two legs of a large one).
     // Two loops one after the other (first leg, second leg) are what the compiler mishandled: see GridPlace.
@@ -477,6 +477,12 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   Lds L;
   constexpr bool STORE = has_start_store<Rng>(INTENSITY, GENERAL, GRID, MULTI);   // photons start a wavefront at a time: part B of the event phase
+  // Which voxel step (trace_step_lazy): the general kernels' guarded division in a branch of its own, and -- CHAIN -- in the fused ring
+  // kernels of a bricked field the specialised step as it was before zero cosines fell out of its minimum: with the minimum these two
+  // instantiations ran out of scalar registers by two and kept the wave-uniform `adaptEvent` as a lane mask in a vector register,
+  // the form tests/test_build_isa.py keeps out of the kernels (GridPlace).  Both want a zero cosine marked in Ray::slow.
+  constexpr bool CHAIN = !GENERAL && Rng::kBatched && INTENSITY && !DIRECT && GRID == GRID_BRICKS;
+  constexpr bool ZERO_IS_SLOW = GENERAL || CHAIN;
   lds_float *startSlots = nullptr;   // STORE: this wave's start store (StartSlot, tracer.hpp)
   constexpr bool TRACK = Rng::kExtra == EXTRA_TRACKS;   // actinic flux by track length (PhiloxTrackStream): tallied by the general flux kernel only
   lds_f64 *trackSums = nullptr;      // TRACK: the workgroup's partial sums of the block (nullptr: the block in global memory is added to)
@@ -526,7 +532,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
     for (int d = threadIdx.x; d < P.nDir; d += blockDim.x) {
       Ray t;
       t.dx = L.dirCos[3 * d]; t.dy = L.dirCos[3 * d + 1]; t.dz = L.dirCos[3 * d + 2];
-      t.set_direction(L);
+      t.set_direction<ZERO_IS_SLOW>(L);
       t.store_direction(L.dirTab + 16 * d);
     }
     __syncthreads();
@@ -568,7 +574,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   RngInit<Rng>::init(rng, A);
   Ray r;
   r.x = r.y = r.z = 0.0f; r.dx = r.dy = 0.0f; r.dz = -1.0f; r.ix = r.iy = r.iz = 1; r.acc = 0.0f; r.target = 0.0f;
-  r.rx = r.ry = r.rz = 0.0f; r.slow = 1;
+  r.rx = r.ry = r.rz = 0.0f; r.slow = ZERO_IS_SLOW ? 1 : 0;   // (dx = dy = 0: see Ray::slow)
   r.ex = r.ey = r.ez = 0; r.cx = r.cy = r.cz = 1; r.nudge = 2.0f;
   float w = 0.0f;
   int order = 0;
@@ -974,7 +980,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
 #ifdef I3RC_NO_DIRTAB   /* (measurement knob: the direction's derived values worked out at every ray start, as before round 4) */
               const int dIdx = RayInfo::direction(sInfo);
               sr.dx = L.dirCos[3 * dIdx]; sr.dy = L.dirCos[3 * dIdx + 1]; sr.dz = L.dirCos[3 * dIdx + 2];
-              sr.set_direction(L);
+              sr.set_direction<ZERO_IS_SLOW>(L);
 #else
               sr.load_direction(L.dirTab + 16 * RayInfo::direction(sInfo));
 #endif
@@ -1014,7 +1020,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
               // (an arrival: see the service phase.  The ray's own stage says whether it has a target: the wave-uniform P.useRRI says the
               // same, and as a run-time flag in this loop it came out as a lane mask made under another loop's exec mask -- GridPlace's trap,
               // caught by tests/test_build_isa.py)
-              if (trace_step_lazy<GRID, false, GENERAL, !DIRECT>(P, L, sr, RayInfo::stage(sInfo) != 0) != STEP_CONTINUE) rst = R_ENDED;   // (ring kernels: the short form, see trace_step_lazy)
+              if (trace_step_lazy<GRID, false, GENERAL, !DIRECT, false, CHAIN>(P, L, sr, RayInfo::stage(sInfo) != 0) != STEP_CONTINUE) rst = R_ENDED;   // (ring kernels: the short form, see trace_step_lazy)
             }
             PROF_END(PH_RAYSTEP, nTracing);
           };
@@ -1032,7 +1038,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
         }
         // what the photons' rays derive from their directions is worked out again here, so that those eleven registers per
         // lane are free during the ray loop (the radiance kernels then fit five waves per SIMD)
-        r.set_direction(L);
+        r.set_direction<ZERO_IS_SLOW>(L);
       }
     }
     // ================================================================================================ PHOTON MODE
@@ -1515,7 +1521,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           if constexpr (STORE) r.target = fromStore ? r.target : tau;   // (a new photon's depth is its slot's: the same word, the same logarithm)
           else r.target = tau;
           if constexpr (LEVELS) izFrom = min(max(r.iz, 1), Pe.nz);
-          if (rayTracing) { startedTrace = true; r.set_direction(L); }
+          if (rayTracing) { startedTrace = true; r.set_direction<ZERO_IS_SLOW>(L); }
           else {                                                          // :494-496 max cross-section move
             r.x = make_periodic(r.x + r.dx * tau / Pe.maxExt, Pe.x0, Pe.xMax);
             r.y = make_periodic(r.y + r.dy * tau / Pe.maxExt, Pe.y0, Pe.yMax);
@@ -1585,10 +1591,10 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
         if constexpr (TRACK) {   // the piece of path inside the cell the photon is in before the step (a failed step and the arriving one add nothing here)
           const int cell = cell_index(P, r.ix, r.iy, r.iz);
           float len = 0.0f;
-          s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, true>(P, L, r, true, &len);
+          s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, true, CHAIN>(P, L, r, true, &len);
           if (s == STEP_CONTINUE || s == STEP_EXIT) track_add(trackSums, extra_block(P.tally, P.oCnt), cell, P.nx * P.ny * P.nz, w, len);
         } else
-        s = trace_step_lazy<GRID, !INTENSITY, GENERAL>(P, L, r, true);   // (an arrival is finished by the event phase)
+        s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, false, CHAIN>(P, L, r, true);   // (an arrival is finished by the event phase)
         if (GENERAL && s == STEP_EXIT) finish_exit(P, r);
         // (an exit through the top, or onto a black surface, ends the photon: such lanes wait for the turnover quorum)
         if (s != STEP_CONTINUE)

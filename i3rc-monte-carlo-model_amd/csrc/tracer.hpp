@@ -344,8 +344,9 @@ __device__ __forceinline__ float two_spacingf(float x) {
 // once gives r1 ~ 1/d; n/d is then q0 = n*r1 followed by two fused residual corrections -- the tail of the IEEE
 // division expansion hipcc emits, minus its per-call reciprocal and range scaling: 5 FMA-class instructions instead
 // of ~13, same correctly rounded quotient (bit-identity with `/` is checked on the device by
-// tests/test_gpu_parity.py::test_exact_arithmetic_helpers and by the bit-exact tracer tests).  Valid for
-// 1e-20 <= |d| and results far from overflow, which callers guarantee (else they use `/`).
+// tests/test_gpu_parity.py::test_exact_arithmetic_helpers and by the bit-exact tracer tests).  The quotient is the
+// IEEE one for 1e-20 <= |d| and results far from overflow, which callers guarantee (else they use `/`) -- and NaN
+// for d = +-0 with its refined reciprocal, for every n, which the voxel step relies on (trace_step_lazy).
 __device__ __forceinline__ float refined_rcp(float d) {
   const float r0 = __builtin_amdgcn_rcpf(d);
   return __builtin_fmaf(__builtin_fmaf(-d, r0, 1.0f), r0, r0);
@@ -427,15 +428,25 @@ struct Ray {
   float x, y, z;
   float dx, dy, dz;
   float rx, ry, rz;   // refined reciprocals of the direction cosines (set_direction)
-  int slow;           // 1: some |direction cosine| < 1e-20 -> plain IEEE division (and the 2*tiny test) per step
+  int slow;           // 1: some direction cosine is too small for the reciprocal-based division -> plain IEEE division (and the 2*tiny
+                      // test) per step.  The specialised kernels' step: 0 < |cosine| < 1e-20 -- an exact +-0 does not set it, its quotient
+                      // is NaN and falls out of the step's minimum (trace_step_lazy); the general kernels' (ZERO_IS_SLOW): |cosine| < 1e-20
   int ix, iy, iz;
   float acc, target;
   // what a trace needs of its direction at every voxel step, worked out once per trace (set_direction):
   int ex, ey, ez;     // LDS byte address of edge 0 of the face the ray moves towards: face coordinate = [e + 4 index]
   int cx, cy, cz;     // cell increment (+1 / -1) along each axis
   float nudge;        // 2 cx as a float: the periodic wrap moves the position by nudge * spacing() (:1774-1788)
+  template <bool ZERO_IS_SLOW = false>
   __device__ __forceinline__ void set_direction(const Lds &L) {
-    slow = fminf(fminf(fabsf(dx), fabsf(dy)), fabsf(dz)) < 1e-20f;
+    if (ZERO_IS_SLOW) {
+      slow = fminf(fminf(fabsf(dx), fabsf(dy)), fabsf(dz)) < 1e-20f;
+    } else {
+      // (the bit patterns shifted left, which drops the sign, less one as unsigned: zero becomes the largest value, so that one 3-way
+      // minimum and one compare find a cosine in (0, 1e-20) -- a shift-and-add per axis, v_min3_u32, v_cmp)
+      const uint32_t ux = (__float_as_uint(dx) << 1) - 1u, uy = (__float_as_uint(dy) << 1) - 1u, uz = (__float_as_uint(dz) << 1) - 1u;
+      slow = min(min(ux, uy), uz) < (__float_as_uint(1e-20f) << 1) - 1u;
+    }
     rx = refined_rcp(dx); ry = refined_rcp(dy); rz = refined_rcp(dz);
     const bool px = dx >= 0.0f, py = dy >= 0.0f, pz = dz >= 0.0f;
     // edges are stored from index 0; cell i (1-based) lies between edge i - 1 and edge i
@@ -545,7 +556,10 @@ __device__ __forceinline__ float cell_extinction(const PR &P, const Lds &L, int 
 // (LENGTH: the step also hands out, in *length, the path it advances inside the cell it began in -- `step`, or 0 in the arriving step,
 // whose length finish_arrival forms; a failed step leaves *length alone.  photon_kernel<PhiloxTrackStream, ...> alone asks for it:
 // every other instantiation compiles to what it compiled to without the flag.)
-template <int GRID, bool CLEARMAP = false, bool BRANCHY = false, bool SHORT = false, bool LENGTH = false, class PR>
+// (CHAIN: the minimum of the three quotients as a chain of `<` selects, which lets a NaN in stx through: for rays whose zero cosines
+// are marked in Ray::slow -- set_direction<true> --, so that the guarded path has replaced every such quotient.  Two instantiations
+// keep it: see photon_kernel.)
+template <int GRID, bool CLEARMAP = false, bool BRANCHY = false, bool SHORT = false, bool LENGTH = false, bool CHAIN = false, class PR>
 __device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L, Ray &r, bool hasTarget, float *length = nullptr) {
   // the extinction of the current cell is requested first: its latency (LDS, or L2 / HBM for grids that do not fit
   // in LDS) is covered by the three face-distance divisions below
@@ -564,14 +578,21 @@ __device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L,
       stz = exact_div(ez - r.z, r.dz, r.rz);
     }
   } else {
-  // (every lane, every axis: on an axis whose cosine is below 1e-20 the quotient is rubbish and is replaced below)
+  // (every lane, every axis: on an axis whose cosine is +-0 the quotient is NaN, see below; for 0 < |cosine| < 1e-20 it is rubbish
+  // and is replaced below)
   stx = exact_div(ex - r.x, r.dx, r.rx); sty = exact_div(ey - r.y, r.dy, r.ry); stz = exact_div(ez - r.z, r.dz, r.rz);
-  // A direction cosine of (almost) zero: the reference's guarded division (:1697-1704: a face is never reached along an axis whose
-  // |cosine| is below 2 tiny).  Such lanes are the rule, not the exception -- a sun at the zenith gives every photon dx = dy = 0
-  // until its first scattering, a nadir radiance direction every ray of it -- so that in nine voxel-step phases of ten SOME lane
-  // of the wave is one: a branch of its own for them (three guarded IEEE divisions behind three exec masks, then the fast path
-  // for the others) was twenty vector and as many scalar instructions on top of every such phase.  Now: one uniform test, three
-  // selects for the lanes concerned; only cosines between 2 tiny and 1e-20 (none in practice) still take the IEEE division.
+  // A direction cosine of zero: the reference's guarded division (:1697-1704) says that a face is never reached along an axis whose
+  // |cosine| is below 2 tiny -- its quotient is huge.  Such rays are the rule, not the exception: a sun at the zenith gives every
+  // photon dx = dy = 0 until its first scattering, a nadir radiance direction every ray of it, so that in nine voxel-step phases of
+  // ten SOME lane of the wave is one.  They cost nothing here: for d = +-0 refined_rcp is NaN (v_rcp_f32 gives +-inf, and its
+  // refinement's fma(-d, inf, 1) is 0 * inf), hence n * NaN and every fma of exact_div is NaN WHATEVER the numerator n -- zero,
+  // negative or infinite.  A NaN says "never reached" as huge does: the minimum below is fminf, which returns its other operand
+  // (v_min_f32 / v_min3_f32 in IEEE mode; all three NaN gives NaN and the error exit), and the face tests `stx <= step` are ordered
+  // compares, false for NaN as for huge.  (So a NaN quotient of any origin, a NaN position or direction, now drops its axis where
+  // it used to end the trace if the axis was x and to be dropped if it was y or z; the host refuses such photons.)
+  // What is left for the guarded path are cosines with 0 < |d| < 1e-20 (Ray::slow; none in practice), where the reciprocal-based
+  // quotient is not the IEEE one: one uniform test, three selects -- for d = +-0 too, in such a wave -- and the IEEE division from
+  // 2 tiny up.  Without the NaN rule the test was true, and the repair paid, in those nine phases of ten.
   if (__ballot(r.slow != 0) != 0ull) {
     const float adx = fabsf(r.dx), ady = fabsf(r.dy), adz = fabsf(r.dz);
     const bool tx = adx < 1e-20f, ty = ady < 1e-20f, tz = adz < 1e-20f;
@@ -584,9 +605,15 @@ __device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L,
     }
   }
   }
-  float step = stx;
-  step = sty < step ? sty : step;
-  step = stz < step ? stz : step;
+  static_assert(!(BRANCHY && CHAIN), "CHAIN: the step without a branch of its own");
+  float step;
+  if (BRANCHY || CHAIN) {
+    step = stx;
+    step = sty < step ? sty : step;
+    step = stz < step ? stz : step;
+  } else {
+    step = fminf(stx, fminf(sty, stz));   // (one v_min3_f32 either way; nested the other way round, four instantiations each spilled a vector register)
+  }
   // :1711-1714 `if(thisStep <= 0.)`, written so that a NaN step (a NaN direction or position) ends the trace as well:
   // the reference's comparison lets NaN through and its loop never ends
   if (__builtin_expect(!(step > 0.0f), 0)) { r.acc = -2.0f; return STEP_ERROR; }
