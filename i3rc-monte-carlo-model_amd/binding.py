@@ -30,6 +30,7 @@ SYMBOLS = [
     "i3rc_hip_set_batch_fusion", "i3rc_hip_select_grid_place", "i3rc_hip_has_column_records", "i3rc_hip_column_records", "i3rc_hip_column_records_base", "i3rc_hip_lds_plan", "i3rc_hip_lds_plan_words", "i3rc_hip_set_lds_tallies", "i3rc_hip_last_kernel_name", "i3rc_hip_last_plan", "i3rc_hip_timed_launch_count", "i3rc_hip_philox_blocks", "i3rc_hip_arith_check", "i3rc_hip_find_index", "i3rc_hip_surface_reflectance", "i3rc_hip_device_count", "i3rc_hip_version",
     "i3rc_hip_set_level_fluxes", "i3rc_hip_get_level_flux_layout", "i3rc_hip_normalise_level_fluxes",
     "i3rc_hip_set_actinic_flux", "i3rc_hip_get_actinic_flux_layout", "i3rc_hip_normalise_actinic_flux",
+    "i3rc_hip_problem_facts", "i3rc_hip_plan_launch",
 ]
 
 
@@ -61,6 +62,53 @@ class MomentsLayout(C.Structure):
 # the words of i3rc_hip_last_plan, in order
 PLAN_NAMES = ["ldsGrid", "ldsTallies", "ldsVolume", "ldsIntensity", "tableInLds", "ldsBytes", "absorbing", "cellRecordBytes",
               "fusedBatches", "place", "startStoreBytes", "chunk", "ldsTrackSums"]
+
+
+# the words of i3rc_hip_problem_facts, in order ...
+FACT_NAMES = ["nx", "ny", "nz", "ncomp", "xyRegular", "zRegular", "empty", "absorbing", "uniformSsa", "uniformPf", "cellRecordBytes",
+              "columnRecords", "columnBase", "bsx", "bsy", "bsz", "nbx", "nby", "nbz", "clearShift", "clearNx", "clearWords", "maxPfIndex"]
+# ... and of i3rc_hip_plan_launch: what the setters and the handle's knobs add to them, the switches of the process (with their
+# defaults), the kinds of stream, and what follows the words of PLAN_NAMES in its answer
+SETUP_NAMES = ["nDir", "inverseTables", "forwardTables", "inverseSteps", "inverseEntries", "useSurfaceBDRF", "useRayTracing", "surfaceNx",
+               "surfaceNy", "surfaceSet", "extra", "kernelVariant", "gridPlace", "ldsTalliesOn"]
+ENV_DEFAULTS = {"I3RC_COLUMNS": 1, "I3RC_LDS_TALLIES": 1, "I3RC_TABLE_LDS": 1, "I3RC_TABLE_LDS_PLACES": 11, "I3RC_FUSED_TABLE_LDS_PLACES": 11,
+                "I3RC_DIRECT": 1, "I3RC_CELL_RECORDS": 1}
+STREAM_KINDS = {"plain": 0, "fused": 1, "replay": 2, "level": 3, "track": 4}
+PLAN_EXTRA_NAMES = ["ldsEstimate", "rayQueueCap", "threads"]
+
+
+def _env_words(env):
+    """the switches of the process as i3rc_hip_problem_facts / i3rc_hip_plan_launch take them: None (the process's own), or a dict of
+    ENV_DEFAULTS' names over their defaults"""
+    if env is None:
+        return None
+    unknown = set(env) - set(ENV_DEFAULTS)
+    if unknown:
+        raise KeyError(f"not a switch a launch reads: {sorted(unknown)}")
+    return (C.c_int32 * len(ENV_DEFAULTS))(*[int(env.get(k, v)) for k, v in ENV_DEFAULTS.items()])
+
+
+def problem_facts(nx, ny, nz, ncomp, xe, ye, ze, total, cum, ssa, pfi, env=None):
+    """i3rc_hip_problem_facts on the arrays of i3rc_hip_create (float32 / int32, contiguous): a dict of FACT_NAMES.  No device needed."""
+    out = (C.c_int32 * len(FACT_NAMES))()
+    rc = load().i3rc_hip_problem_facts(nx, ny, nz, ncomp, pf(xe), pf(ye), pf(ze), pf(total), pf(cum), pf(ssa), pfi.ctypes.data_as(ip),
+                                       _env_words(env), out, len(FACT_NAMES))
+    if rc != 0:
+        raise I3RCError("i3rc_hip_problem_facts: " + (load().i3rc_hip_last_error(None).decode() if rc == 1 else "bad arguments"))
+    return dict(zip(FACT_NAMES, (int(v) for v in out)))
+
+
+def plan_launch(facts, setup, stream="plain", source=0, fused_batches=0, env=None):
+    """i3rc_hip_plan_launch: (kernel name, dict of PLAN_NAMES + PLAN_EXTRA_NAMES), or (refusal text, None).  facts: a dict of FACT_NAMES;
+    setup: a dict of SETUP_NAMES.  No device needed."""
+    n = len(PLAN_NAMES) + len(PLAN_EXTRA_NAMES)
+    out, text = (C.c_int32 * n)(), C.create_string_buffer(512)
+    rc = load().i3rc_hip_plan_launch((C.c_int32 * len(FACT_NAMES))(*[int(facts[k]) for k in FACT_NAMES]),
+                                     (C.c_int32 * len(SETUP_NAMES))(*[int(setup[k]) for k in SETUP_NAMES]), _env_words(env),
+                                     (C.c_int32 * 3)(STREAM_KINDS[stream], int(source), int(fused_batches)), out, n, text, len(text))
+    if rc == 2:
+        raise I3RCError("i3rc_hip_plan_launch: bad arguments")
+    return text.value.decode(), (dict(zip(PLAN_NAMES + PLAN_EXTRA_NAMES, (int(v) for v in out))) if rc == 0 else None)
 
 
 class I3RCError(RuntimeError):
@@ -154,6 +202,9 @@ def load():
         L.i3rc_hip_set_actinic_flux.argtypes = [H, C.c_int]
         L.i3rc_hip_get_actinic_flux_layout.argtypes = [H, lp, lp]
         L.i3rc_hip_normalise_actinic_flux.argtypes = [H, dp, fp]
+    if hasattr(L, "i3rc_hip_plan_launch"):   # (likewise)
+        L.i3rc_hip_problem_facts.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp, ip, ip, ip, C.c_int]
+        L.i3rc_hip_plan_launch.argtypes = [ip, ip, ip, ip, ip, C.c_int, C.c_char_p, C.c_int]
     L.i3rc_hip_device_count.restype = C.c_int
     L.i3rc_hip_version.restype = C.c_char_p
     _lib = L

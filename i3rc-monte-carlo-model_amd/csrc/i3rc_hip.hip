@@ -2,20 +2,13 @@
 #include "../../include/i3rc_hip.h"
 
 #include <hip/hip_runtime.h>
-#include <cstdlib>
-#include <map>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
 #include <ctime>
-#include <string>
+#include <map>
 #include <utility>
-#include <vector>
 
 #include "kernels.hpp"
 #include "tally_block.hpp"
+#include "launch_plan.hpp"
 
 using namespace i3rc;
 
@@ -35,13 +28,6 @@ double trace_ms() {
   static const double t0 = ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
   return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6 - t0;
 }
-
-// Environment knobs (I3RC_*, read once per process where they are used): a switch that is on unless set to 0, ...
-bool env_on(const char *name) { const char *v = std::getenv(name); return !(v && std::atoi(v) == 0); }
-// ... an integer with a default, ...
-long long env_int(const char *name, long long dflt) { const char *v = std::getenv(name); return v ? std::atoll(v) : dflt; }
-// ... and a pair of integers "a,b" (false where unset or not of that form)
-bool env_pair(const char *name, int &a, int &b) { const char *v = std::getenv(name); return v && std::sscanf(v, "%d,%d", &a, &b) == 2; }
 
 
 struct DevBuf {
@@ -73,42 +59,25 @@ struct DevBuf {
 
 }  // namespace
 
-struct i3rc_hip_integrator {
+struct i3rc_hip_integrator : ProblemFacts {   // (the facts every launch is decided from: launch_plan.hpp)
   int device = 0;
-  int nx = 0, ny = 0, nz = 0, ncomp = 0;
   std::vector<float> xE, yE, zE;  // host copies (launch parameters, checks)
   std::vector<double> areaFrac, layerDepth;   // what the normalisation needs of the grid (TallyView::areaFrac, ::dz), worked out once
   DevBuf dxE, dyE, dzE, dExt, dCum, dSsa, dPf;
   DevBuf dCellRec;               // two components: a scattering's reads of its cell as one 16-byte record (DevProblem::cellRec)
   DevBuf dExtBrick;              // totalExt in bricks of 32 cells (DevProblem::extBrick)
   DevBuf dClearMap;              // ... and its clear-air map (DevProblem::clearMap)
-  int clearShift = 0, clearNx = 1, clearWords = 1;
   DevBuf dColRec;                // one record per column where every column is one run of one value (DevProblem::colRec); else empty
   DevBuf dColBase;               // ... over a base profile (DevProblem::colBase, nz floats): the records then hold what lies ON the profile
-  int gridPlace = I3RC_GRID_AUTO;   // test / tuning knob (i3rc_hip_select_grid_place)
   bool compDirty = true;         // comp[] changed since its device copy (dComp) was made
-  int bsx = 0, bsy = 0, bsz = 0, nbx = 0, nby = 0, nbz = 0;
   std::vector<DevBuf> dInv, dInvCos, dFwd, dFwdOrig;   // per component (sized by i3rc_hip_create)
-  std::vector<CompTables> comp;
-  std::vector<int> nInvEntries, nFwdEntries;
   DevBuf dComp;
   DevBuf dXs, dYs, dBrdf;
-  int nxs = 0, nys = 0;
-  bool ldsTalliesOn = true;   // i3rc_hip_set_lds_tallies
   float brdf0 = 0.f;          // reflectance of the first surface cell (a 1 x 1 surface grid is a plain Lambertian albedo)
   DevBuf dDir;
-  int nDir = 0;
-  i3rc_params params{};
-  float maxExt = 0.f;
-  int xyRegular = 0, zRegular = 0;
-  std::vector<int> maxPfIndex;
-  float uniformSsa = -1.f;   // one-component domains: the value every cell shares, else -1
-  bool absorbing = false;    // some cell of some component has omega < 1: launches tally volume absorption, and fluxAbsorbed is formed from it (absorbed_columns_kernel)
-  int uniformPf = 0;         // ... and the phase-function entry every cell shares, else 0
 
   i3rc_tally_layout layout{};
   TallyView view{};                // the same block as the normalisation sees it (tally_block.hpp, tally_layout), over the host arrays above
-  ExtraTally extra = EXTRA_NONE;   // set_extra_tally: the block plain flux launches also fill, behind the counters (tally_block.hpp)
   DevBuf ownTally;
   double *tally = nullptr;  // device pointer in use (own or bound)
   DevBuf workCounter;
@@ -180,9 +149,7 @@ struct i3rc_hip_integrator {
   int evThreshold = 0;        // lanes waiting before a wave runs its event phase; 0 = adapted per wave
   int lightThreshold = 0;     // lanes with an ended shadow ray before a wave runs its light phase; 0 = adapted per wave
   int blocksPerCU = 0;  // 0 = from occupancy query
-  int kernelVariant = I3RC_KERNEL_AUTO;  // test / tuning knob (i3rc_hip_select_kernel)
   std::string lastKernelName;            // kernel the most recent launch ran (i3rc_hip_last_kernel_name)
-  static constexpr int kPlanWords = 13, kPlanChunk = 11;
   int32_t lastPlan[kPlanWords] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // ... and its plan (i3rc_hip_last_plan)
   int64_t launchLimit = 0;               // photons per kernel launch (i3rc_hip_set_launch_limit); 0 = numCU * 2^22
   std::string err;
@@ -199,14 +166,6 @@ struct i3rc_hip_integrator {
     hipError_t e__ = (call);                              \
     if (e__ != hipSuccess) return (h)->hipfail(#call, e__); \
   } while (0)
-
-static float host_spacing(float x) {
-  if (x == 0.0f) return FLT_MIN;
-  int e;
-  (void)std::frexp(std::fabs(x), &e);
-  float r = std::ldexp(1.0f, e - 24);
-  return r < FLT_MIN ? FLT_MIN : r;
-}
 
 static void compute_layout(i3rc_hip_integrator *h) {
   TallyView &V = h->view;
@@ -344,19 +303,21 @@ int i3rc_hip_create(i3rc_hip_integrator **out, int device, int nx, int ny, int n
   for (int i = 0; i < nx; ++i) if (!(xEdges[i + 1] > xEdges[i])) { g_createError = "i3rc_hip_create: x edges must increase"; return 1; }
   for (int i = 0; i < ny; ++i) if (!(yEdges[i + 1] > yEdges[i])) { g_createError = "i3rc_hip_create: y edges must increase"; return 1; }
   for (int i = 0; i < nz; ++i) if (!(zEdges[i + 1] > zEdges[i])) { g_createError = "i3rc_hip_create: z edges must increase"; return 1; }
+  // the facts of the field, from the host arrays alone and before anything touches the device (launch_plan.hpp)
+  auto *h = new i3rc_hip_integrator();
+  ColumnRecords cols;
+  g_createError = derive_facts(*h, EnvKnobs::process(), nx, ny, nz, ncomp, xEdges, yEdges, zEdges, totalExt, cumExt, ssa, pfIndex, &cols);
+  if (!g_createError.empty()) { delete h; return 1; }
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev < 1) {
     g_createError = "i3rc_hip_create: no HIP device available (the integrator has no CPU fallback)";
+    delete h;
     return 2;
   }
-  if (device < 0 || device >= ndev) { g_createError = "i3rc_hip_create: device index out of range"; return 1; }
-
-  auto *h = new i3rc_hip_integrator();
+  if (device < 0 || device >= ndev) { g_createError = "i3rc_hip_create: device index out of range"; delete h; return 1; }
   h->device = device;
-  h->nx = nx; h->ny = ny; h->nz = nz; h->ncomp = ncomp;
   h->dInv = std::vector<DevBuf>(ncomp); h->dInvCos = std::vector<DevBuf>(ncomp); h->dFwd = std::vector<DevBuf>(ncomp); h->dFwdOrig = std::vector<DevBuf>(ncomp);
-  h->comp.assign(ncomp, CompTables{}); h->nInvEntries.assign(ncomp, 0); h->nFwdEntries.assign(ncomp, 0); h->maxPfIndex.assign(ncomp, 0);
   auto bail = [&](const char *what, hipError_t er) {
     g_createError = std::string(what) + ": " + hipGetErrorString(er);
     delete h;
@@ -384,21 +345,6 @@ int i3rc_hip_create(i3rc_hip_integrator **out, int device, int nx, int ny, int n
     CCHK(h->dExt.upload(padded.data(), sizeof(float) * padded.size()));
   }
   {
-    // bricks of 32 cells: 8 deep where the grid has the layers for it (photon paths and shadow rays cross z faces
-    // most often in cloud fields, whose cells are flatter than wide), the rest shared by x and y
-    auto log2le = [](int n, int cap) { int s = 0; while ((2 << s) <= n && s + 1 <= cap) ++s; return s; };
-    h->bsz = log2le(nz, 3);
-    h->bsy = log2le(ny, (5 - h->bsz) / 2);
-    int bz, by;   // tuning knob: "<log2 depth>,<log2 width in y>" (the rest of the 32 cells in x)
-    if (env_pair("I3RC_BRICK", bz, by) && bz >= 0 && by >= 0 && bz + by <= 5) { h->bsz = log2le(nz, bz); h->bsy = log2le(ny, by); }
-    h->bsx = 5 - h->bsz - h->bsy;
-    h->nbx = (nx + (1 << h->bsx) - 1) >> h->bsx; h->nby = (ny + (1 << h->bsy) - 1) >> h->bsy;
-    h->nbz = (nz + 1 + (1 << h->bsz) - 1) >> h->bsz;   // (room for the layer nz + 1 of zeros, as in dExt)
-    if ((int64_t)h->nbx * h->nby >= ((int64_t)1 << 24) || (int64_t)h->nbx * h->nby * h->nbz >= ((int64_t)1 << 26)) {
-      g_createError = "i3rc_hip_create: domain too large for the bricked extinction copy";
-      delete h;
-      return 1;
-    }
     std::vector<float> brick((size_t)h->nbx * h->nby * h->nbz * 32, 0.0f);
     for (int k = 0; k < nz; ++k)
       for (int j = 0; j < ny; ++j)
@@ -409,12 +355,7 @@ int i3rc_hip_create(i3rc_hip_integrator **out, int device, int nx, int ny, int n
           brick[b * 32 + w] = totalExt[((size_t)k * ny + j) * nx + i];
         }
     CCHK(h->dExtBrick.upload(brick.data(), sizeof(float) * brick.size()));
-    // clear-air map: lowest / highest layer with any extinction per footprint of 2^s x 2^s columns, at most 1024 words
-    int sft = 0;
-    while ((size_t)(((nx - 1) >> sft) + 1) * (size_t)(((ny - 1) >> sft) + 1) > 1024) ++sft;
-    h->clearShift = sft; h->clearNx = ((nx - 1) >> sft) + 1;
-    const int cny = ((ny - 1) >> sft) + 1;
-    h->clearWords = h->clearNx * cny;
+    const int sft = h->clearShift;
     std::vector<uint32_t> lo((size_t)h->clearWords, 0xffffu), hi((size_t)h->clearWords, 0u), map((size_t)h->clearWords);
     for (int k = 0; k < nz; ++k)
       for (int j = 0; j < ny; ++j)
@@ -427,37 +368,29 @@ int i3rc_hip_create(i3rc_hip_integrator **out, int device, int nx, int ny, int n
     for (size_t c = 0; c < map.size(); ++c) map[c] = lo[c] | (hi[c] << 16);
     CCHK(h->dClearMap.upload(map.data(), sizeof(uint32_t) * map.size()));
   }
-  {
-    std::vector<uint32_t> rec(2 * (size_t)nx * ny);
-    std::vector<float> base((size_t)nz);
-    if (i3rc_hip_column_records(nx, ny, nz, totalExt, rec.data()) == 1) CCHK(h->dColRec.upload(rec.data(), sizeof(uint32_t) * rec.size()));
-    else if (i3rc_hip_column_records_base(nx, ny, nz, totalExt, rec.data(), base.data()) == 1) {   // the same over a value per layer (a uniform gas under / around the clouds)
-      CCHK(h->dColRec.upload(rec.data(), sizeof(uint32_t) * rec.size()));
-      CCHK(h->dColBase.upload(base.data(), sizeof(float) * base.size()));
-    }
-  }
+  if (h->colRecords) CCHK(h->dColRec.upload(cols.rec.data(), sizeof(uint32_t) * cols.rec.size()));
+  if (h->colBase) CCHK(h->dColBase.upload(cols.base.data(), sizeof(float) * cols.base.size()));
   CCHK(h->dCum.upload(cumExt, sizeof(float) * ncell * ncomp));
   CCHK(h->dSsa.upload(ssa, sizeof(float) * ncell * ncomp));
   CCHK(h->dPf.upload(pfIndex, sizeof(int32_t) * ncell * ncomp));
-  static const bool cellRecordsOn = env_on("I3RC_CELL_RECORDS");   // (DevProblem::cellRec; 0: the kernels read the plain arrays)
-  if (ncomp == 2 || ncomp == 3) {
-    bool fits = cellRecordsOn;
-    for (size_t i = 0; i < 2 * ncell && fits; ++i) fits = pfIndex[i] >= 0 && pfIndex[i] < 65536;   // (the first two entries share a word)
-    if (fits) {
-      auto bits = [](float v) { uint32_t b; std::memcpy(&b, &v, 4); return b; };
-      const size_t words = ncomp == 2 ? 4 : 8;
-      std::vector<uint32_t> rec(words * ncell, 0u);
-      for (size_t i = 0; i < ncell; ++i) {
-        uint32_t *r = &rec[words * i];
-        const uint32_t pf01 = (uint32_t)pfIndex[i] | ((uint32_t)pfIndex[ncell + i] << 16);
-        if (ncomp == 2) { r[0] = bits(cumExt[i]); r[1] = bits(ssa[i]); r[2] = bits(ssa[ncell + i]); r[3] = pf01; }
-        else {
-          r[0] = bits(cumExt[i]); r[1] = bits(cumExt[ncell + i]); r[2] = bits(ssa[i]); r[3] = bits(ssa[ncell + i]);
-          r[4] = bits(ssa[2 * ncell + i]); r[5] = pf01; r[6] = (uint32_t)pfIndex[2 * ncell + i];
-        }
+  if (h->cellRecBytes == 8) {   // one component: {ssa, pfIndex}
+    std::vector<uint32_t> rec(2 * ncell);
+    for (size_t i = 0; i < ncell; ++i) { std::memcpy(&rec[2 * i], &ssa[i], 4); rec[2 * i + 1] = (uint32_t)pfIndex[i]; }
+    if (h->dCellRec.upload(rec.data(), sizeof(uint32_t) * rec.size()) != hipSuccess) { g_createError = "i3rc_hip_create: device allocation of the cell records failed"; delete h; return 1; }
+  } else if (h->cellRecBytes) {
+    auto bits = [](float v) { uint32_t b; std::memcpy(&b, &v, 4); return b; };
+    const size_t words = ncomp == 2 ? 4 : 8;
+    std::vector<uint32_t> rec(words * ncell, 0u);
+    for (size_t i = 0; i < ncell; ++i) {
+      uint32_t *r = &rec[words * i];
+      const uint32_t pf01 = (uint32_t)pfIndex[i] | ((uint32_t)pfIndex[ncell + i] << 16);
+      if (ncomp == 2) { r[0] = bits(cumExt[i]); r[1] = bits(ssa[i]); r[2] = bits(ssa[ncell + i]); r[3] = pf01; }
+      else {
+        r[0] = bits(cumExt[i]); r[1] = bits(cumExt[ncell + i]); r[2] = bits(ssa[i]); r[3] = bits(ssa[ncell + i]);
+        r[4] = bits(ssa[2 * ncell + i]); r[5] = pf01; r[6] = (uint32_t)pfIndex[2 * ncell + i];
       }
-      CCHK(h->dCellRec.upload(rec.data(), sizeof(uint32_t) * rec.size()));
     }
+    CCHK(h->dCellRec.upload(rec.data(), sizeof(uint32_t) * rec.size()));
   }
   CCHK(h->workCounter.alloc(sizeof(unsigned long long)));
   CCHK(h->dComp.alloc(sizeof(CompTables) * ncomp));
@@ -469,60 +402,6 @@ int i3rc_hip_create(i3rc_hip_integrator **out, int device, int nx, int ny, int n
     CCHK(hipEventCreate(&h->evStop[i]));
   }
 #undef CCHK
-  // regular-spacing flags, new_Integrator :193-211
-  {
-    const float dx = xEdges[1] - xEdges[0], dy = yEdges[1] - yEdges[0], dz = zEdges[1] - zEdges[0];
-    int xy = 1, z = 1;
-    for (int i = 0; i < nx; ++i) if (!(std::fabs((xEdges[i + 1] - xEdges[i]) - dx) <= 2.0f * host_spacing(xEdges[i + 1]))) xy = 0;
-    for (int i = 0; i < ny; ++i) if (!(std::fabs((yEdges[i + 1] - yEdges[i]) - dy) <= 2.0f * host_spacing(yEdges[i + 1]))) xy = 0;
-    for (int i = 0; i < nz; ++i) if (!(std::fabs((zEdges[i + 1] - zEdges[i]) - dz) <= host_spacing(zEdges[i + 1]))) z = 0;
-    h->xyRegular = xy; h->zRegular = z;
-  }
-  h->maxExt = totalExt[0];
-  for (size_t i = 1; i < ncell; ++i) h->maxExt = std::max(h->maxExt, totalExt[i]);  // computeRT :438-439
-  for (int c = 0; c < ncomp; ++c) {
-    int m = 0;
-    for (size_t i = 0; i < ncell; ++i) m = std::max(m, pfIndex[(size_t)c * ncell + i]);
-    h->maxPfIndex[c] = m;
-  }
-  // Absorbing: some component has omega < 1 in a cell where the kernels can select it -- the rule of uniformSsa below, for several
-  // components.  They pick component 1 + (the number of k < ncomp - 1 with rc >= cumExt[k]) for a deviate rc in [0, 1] -- 1.0 itself
-  // included (u32_to_unit_float rounds the largest words up to it) --, so component c is selected on [cumExt[c - 1], cumExt[c]), the
-  // first from below 0 and the last up to above 1: it can be selected where that interval meets [0, 1].  A component without
-  // extinction in a cell is never selected there unless it is the last one, which a deviate of 1.0 selects wherever the slices before
-  // it reach 1.  (So a gas that is zero in some cells with omega = 0 there does not make a conservative domain absorbing as the first
-  // component, and does as the last: its omega is then used, rarely, and the absorbed weight must reach fluxAbsorbed.)
-  for (size_t i = 0; i < ncell && !h->absorbing; ++i) {
-    if (totalExt[i] == 0.0f) continue;
-    for (int c = 0; c < ncomp && !h->absorbing; ++c) {
-      const float lo = c == 0 ? -INFINITY : cumExt[(size_t)(c - 1) * ncell + i];
-      const float hi = c == ncomp - 1 ? INFINITY : cumExt[(size_t)c * ncell + i];
-      const bool selectable = lo <= 1.0f && hi > 0.0f && hi > lo;
-      h->absorbing = selectable && ssa[(size_t)c * ncell + i] < 1.0f;
-    }
-  }
-  if (ncomp == 1) {
-    // Values that every cell WITH EXTINCTION shares travel in the kernel arguments (specialised kernels: ray tracing, where a
-    // photon can only be scattered in a cell of positive extinction -- the tracer never stops in any other --, so what the
-    // clear cells hold is never read: the I3RC cloud fields have omega = 0 and phase-function entry 0 there).  Without this
-    // every scattering reads two more words from two more arrays of the field's size, which on the Landsat fields
-    // do not fit in L2 beside it.
-    bool sameSsa = true, samePf = true, any = false;
-    float ssa0 = 1.f; int32_t pf0 = 1;
-    for (size_t i = 0; i < ncell && (sameSsa || samePf); ++i) {
-      if (totalExt[i] == 0.0f) continue;
-      if (!any) { any = true; ssa0 = ssa[i]; pf0 = pfIndex[i]; continue; }
-      sameSsa = sameSsa && ssa[i] == ssa0;
-      samePf = samePf && pfIndex[i] == pf0;
-    }
-    h->uniformSsa = (sameSsa && ssa0 >= 0.f) ? ssa0 : -1.f;
-    h->uniformPf = (samePf && pf0 >= 1) ? pf0 : 0;
-  }
-  if (ncomp == 1 && h->uniformSsa < 0.0f && h->uniformPf < 1 && cellRecordsOn) {   // one component, neither albedo nor entry shared: {ssa, pfIndex}, 8 bytes a cell
-    std::vector<uint32_t> rec(2 * ncell);
-    for (size_t i = 0; i < ncell; ++i) { std::memcpy(&rec[2 * i], &ssa[i], 4); rec[2 * i + 1] = (uint32_t)pfIndex[i]; }
-    if (h->dCellRec.upload(rec.data(), sizeof(uint32_t) * rec.size()) != hipSuccess) { g_createError = "i3rc_hip_create: device allocation of the cell records failed"; delete h; return 1; }
-  }
   // defaults of type(integrator) :54-129
   h->params.surfaceAlbedo = 0.f; h->params.useSurfaceBDRF = 0; h->params.useRayTracing = 1; h->params.useRussianRoulette = 1;
   h->params.useHybridPhaseFunsForIntenCalcs = 0; h->params.numOrdersOrigPhaseFunIntenCalcs = 0;
@@ -612,7 +491,7 @@ int i3rc_hip_set_params(i3rc_hip_integrator *h, const i3rc_params *p) {
   if (!p) return h->fail("i3rc_hip_set_params: null params");
   if (!p->useSurfaceBDRF && (p->surfaceAlbedo > 1.f || p->surfaceAlbedo < 0.f))
     return h->fail("specifyParameters: surface albedo out of range.");  // :878-879
-  if (p->useSurfaceBDRF && !h->dBrdf.p) return h->fail("specifyParameters: surface description isn't valid.");  // :882-883
+  if (p->useSurfaceBDRF && !h->surfaceSet) return h->fail("specifyParameters: surface description isn't valid.");  // :882-883
   if (p->zetaMin < 0.f) return h->fail("specifyParameters: zetaMin must be >= 0.");
   h->params = *p;
   return 0;
@@ -630,7 +509,7 @@ int i3rc_hip_set_surface(i3rc_hip_integrator *h, int nxs, int nys, const float *
   HIPCHK(h, h->dXs.upload(xs, sizeof(float) * (nxs + 1)));
   HIPCHK(h, h->dYs.upload(ys, sizeof(float) * (nys + 1)));
   HIPCHK(h, h->dBrdf.upload(brdf, sizeof(float) * (size_t)nxs * nys));
-  h->nxs = nxs; h->nys = nys;
+  h->nxs = nxs; h->nys = nys; h->surfaceSet = true;
   h->brdf0 = brdf[0];
   return 0;
 }
@@ -748,14 +627,14 @@ int i3rc_hip_select_grid_place(i3rc_hip_integrator *h, int place) {
   if (!h) return 1;
   drop_lookahead(h);
   if (place < I3RC_GRID_AUTO || place > I3RC_GRID_COLUMNS) return h->fail("i3rc_hip_select_grid_place: unknown place");
-  if (place == I3RC_GRID_COLUMNS && !h->dColRec.p)
+  if (place == I3RC_GRID_COLUMNS && !h->colRecords)
     return h->fail("i3rc_hip_select_grid_place: the field has no column records (some column holds more than one run of one value)");
   if (place == I3RC_GRID_BRICKS && h->nz > 65534) return h->fail("i3rc_hip_select_grid_place: more than 65534 layers keep the linear field");
   h->gridPlace = place;
   return 0;
 }
 
-int i3rc_hip_has_column_records(const i3rc_hip_integrator *h) { return h && h->dColRec.p ? 1 : 0; }
+int i3rc_hip_has_column_records(const i3rc_hip_integrator *h) { return h && h->colRecords ? 1 : 0; }
 
 /* Column records (DevProblem::colRec) of a field [nz][ny][nx]: possible when the cells with extinction of every column are ONE run
  * of layers that hold ONE value -- compared bit by bit; "no extinction" is the bit pattern of +0, which is what a record gives
@@ -871,63 +750,12 @@ int i3rc_hip_force_general_kernel(i3rc_hip_integrator *h, int on) {
 
 namespace {
 
-struct LaunchPlan {
-  DevProblem P;
-  size_t ldsBytes;
-  bool intensity;
-  int place;     // GridPlace: where the kernels read the extinction field (make_problem)
-};
+// A launch as it goes to the device: what was decided (launch_plan.hpp) and the kernels' view of the problem
+struct Launch { LaunchDecision d; DevProblem P; };
 
-constexpr size_t kLdsBudget = 64 * 1024;  // per workgroup: leaves room for >= 2 workgroups per CU
-// ... which what a launch MUST have in LDS -- the edge vectors, the directions, the ray queues -- may exceed, up to the 160 KB of a
-// compute unit (less the kernels' few static words): a 2-D domain of 20 000 columns runs with one workgroup per CU, slowly,
-// instead of being refused
-constexpr size_t kLdsHard = 158 * 1024;
-
-// Which kernel runs a launch (see photon_kernel): the common problem class -- regular grid,
-// ray tracing, one component, no BRDF grid, Directional source -- has specialised kernels.
-// A surface description with a single cell (new_SurfaceDescription((/ albedo /)), the form BASELINE.json's Landsat
-// radiance case uses) reflects like surfaceAlbedo: computeSurfaceReflectance returns its one parameter wherever the
-// photon lands (Code/surfaceProperties.f95:121-162), and the weight is multiplied by the same float.
-bool uniform_surface(const i3rc_hip_integrator *h) { return h->params.useSurfaceBDRF && h->nxs == 1 && h->nys == 1; }
-
-// ray tracing asked for, or max cross-section on an optically empty domain (see make_problem)
-bool traced(const i3rc_hip_integrator *h) {
-  const float width = std::min(h->xE.back() - h->xE.front(), h->yE.back() - h->yE.front());
-  return h->params.useRayTracing || !(h->maxExt * width > 1e-5f);
-}
-
-bool common_class(const i3rc_hip_integrator *h, int srcKind) {
-  const bool gridSurface = h->params.useSurfaceBDRF && !uniform_surface(h);
-  return h->xyRegular && traced(h) && !gridSurface && h->ncomp == 1 && srcKind == 0;
-}
-// ... and the same class widened: several components (photon_kernel, MULTI; round 5).
-// (... and, since the kernels that run it keep those two paths behind run-time switches, with an irregular x / y grid or a gridded surface)
-bool multi_class(const i3rc_hip_integrator *h, int srcKind) { return traced(h) && srcKind == 0; }
-
-// One radiance direction (nadir views: BASELINE.json's radar case): the radiance kernels without an event ring (photon_kernel,
-// DIRECT).  I3RC_DIRECT=0 keeps the ring for them too.
-#ifdef I3RC_NESTED_BUILD   /* measurement build: radiance problems run the general kernels with the nested local estimate (kernels.hpp) */
-constexpr bool kNestedBuild = true;
-#else
-constexpr bool kNestedBuild = false;
-#endif
-bool direct_rays(const i3rc_hip_integrator *h) {
-  static const bool on = env_on("I3RC_DIRECT");
-  return on && h->nDir == 1 && h->kernelVariant != I3RC_KERNEL_RING && !kNestedBuild;
-}
-
-size_t ncell_bytes(const i3rc_hip_integrator *h) { return sizeof(float) * (size_t)h->nx * h->ny * h->nz; }
-
-// (stream: where the launch goes, tally: the buffer it adds to)
-int make_problem(i3rc_hip_integrator *h, LaunchPlan &plan, hipStream_t stream, double *tally, bool fused = false, bool replay = false) {
-  DevProblem &P = plan.P;
+// The geometry of the domain and its extinction field in every packed form: what tracing alone needs of a DevProblem.
+void fill_geometry(const i3rc_hip_integrator *h, DevProblem &P) {
   std::memset(&P, 0, sizeof(P));
-  for (int c = 0; c < h->ncomp; ++c)
-    if (!h->comp[c].inv) return h->fail("computeRadiativeTransfer: problem not completely specified (inverse phase function table missing).");
-  if (h->nDir > 0)
-    for (int c = 0; c < h->ncomp; ++c)
-      if (!h->comp[c].fwd) return h->fail("computeRadiativeTransfer: problem not completely specified (forward phase function table missing).");
   P.nx = h->nx; P.ny = h->ny; P.nz = h->nz; P.ncomp = h->ncomp;
   P.xyRegular = h->xyRegular; P.zRegular = h->zRegular;
   P.x0 = h->xE.front(); P.xMax = h->xE.back();
@@ -935,23 +763,21 @@ int make_problem(i3rc_hip_integrator *h, LaunchPlan &plan, hipStream_t stream, d
   P.z0 = h->zE.front(); P.zMax = h->zE.back();
   P.deltaX = h->xE[1] - h->xE[0]; P.deltaY = h->yE[1] - h->yE[0]; P.deltaZ = h->zE[1] - h->zE[0];
   P.xE = (const float *)h->dxE.p; P.yE = (const float *)h->dyE.p; P.zE = (const float *)h->dzE.p;
-  // bricks pay off once the field no longer fits in one XCD's 4 MB of L2
-  // (the clear-air map of a bricked field holds layer numbers in 16 bits: domains of more layers than that keep the linear field)
-  // Column records where the field has them (and does not fit in LDS, below): the whole field in 8 bytes per column.  Measured:
-  // I3RC_COLUMNS=0 switches them off for the process.
-  static const bool columnsOn = env_on("I3RC_COLUMNS");
-  // (records over a base profile -- GRID_COLBASE -- are read by the kernels of domains with several components, the general and the
-  // several-components ones: the one-component specialisations and the replay build are not instantiated for them)
-  const bool baseForm = h->dColBase.p != nullptr;
-  const bool baseOk = h->ncomp > 1 && !replay;
-  const bool columns = (h->gridPlace == I3RC_GRID_COLUMNS || (h->gridPlace == I3RC_GRID_AUTO && columnsOn && h->dColRec.p != nullptr)) && (!baseForm || baseOk);
-  P.colRec = columns ? (const uint2 *)h->dColRec.p : nullptr;
-  P.colBase = columns && baseForm ? (const float *)h->dColBase.p : nullptr;
-  const bool bricks = h->gridPlace == I3RC_GRID_BRICKS || (h->gridPlace == I3RC_GRID_AUTO && !columns && ncell_bytes(h) > ((size_t)4 << 20) && h->nz <= 65534);
-  P.extBrick = bricks ? (const float *)h->dExtBrick.p : nullptr;
+  P.colRec = (const uint2 *)h->dColRec.p; P.colBase = (const float *)h->dColBase.p;
+  P.extBrick = (const float *)h->dExtBrick.p;
   P.bsx = h->bsx; P.bsy = h->bsy; P.bsz = h->bsz; P.nbx = h->nbx; P.nbxy = h->nbx * h->nby;
   P.clearMap = (const uint32_t *)h->dClearMap.p; P.clearShift = h->clearShift; P.clearNx = h->clearNx;
-  P.totalExt = (const float *)h->dExt.p; P.cumExt = (const float *)h->dCum.p; P.ssa = (const float *)h->dSsa.p;
+  P.totalExt = (const float *)h->dExt.p;
+}
+
+// The DevProblem of a launch that `d` has decided (not refused).  (stream: where the launch goes, tally: the buffer it adds to)
+int make_problem(i3rc_hip_integrator *h, const LaunchDecision &d, DevProblem &P, hipStream_t stream, double *tally) {
+  fill_geometry(h, P);
+  // (the kernels take the packed form of the decision's place, and no other)
+  if (d.place != GRID_COLUMNS && d.place != GRID_COLBASE) P.colRec = nullptr;
+  if (d.place != GRID_COLBASE) P.colBase = nullptr;
+  if (d.place != GRID_BRICKS) P.extBrick = nullptr;
+  P.cumExt = (const float *)h->dCum.p; P.ssa = (const float *)h->dSsa.p;
   P.pfIndex = (const int32_t *)h->dPf.p;
   P.cellRec = (const uint4 *)h->dCellRec.p;
   if (h->compDirty) {
@@ -966,70 +792,22 @@ int make_problem(i3rc_hip_integrator *h, LaunchPlan &plan, hipStream_t stream, d
   P.comp = (const CompTables *)h->dComp.p;
   P.comp0 = h->comp[0];
   P.albedo = h->params.surfaceAlbedo; P.useBDRF = h->params.useSurfaceBDRF;
-  if (uniform_surface(h)) { P.albedo = h->brdf0; P.useBDRF = 0; }
+  if (uniform_surface(*h)) { P.albedo = h->brdf0; P.useBDRF = 0; }
   P.nxs = h->nxs; P.nys = h->nys;
   P.xsE = (const float *)h->dXs.p; P.ysE = (const float *)h->dYs.p; P.brdf = (const float *)h->dBrdf.p;
-  if (P.useBDRF && !P.brdf) return h->fail("computeRadiativeTransfer: surfaceBDRF requested but no surface description set");
-  // Max cross-section divides the optical depth by the largest extinction of the domain (:494-496): with no extinction
-  // anywhere that is a step of infinite length and the reference's makePeriodic never returns -- nor does it once the
-  // step exceeds 2^24 domain widths, where subtracting a width no longer changes a float32.  A photon in such an
-  // (optically empty: width * maxExtinction <= 1e-5) domain flies straight to the boundary, which is what ray
-  // tracing gives: such a domain is traced.
-  P.useRayTracing = traced(h) ? 1 : 0; P.useRR = h->params.useRussianRoulette;
+  P.useRayTracing = traced(*h) ? 1 : 0; P.useRR = h->params.useRussianRoulette;
   P.nDir = h->nDir; P.useHybrid = h->params.useHybridPhaseFunsForIntenCalcs;
   P.numOrdersOrig = h->params.numOrdersOrigPhaseFunIntenCalcs; P.useRRI = h->params.useRussianRouletteForIntensity;
   P.limitContrib = h->params.limitIntensityContributions; P.zetaMin = h->params.zetaMin;
   P.maxContrib = h->params.maxIntensityContribution; P.maxExt = h->maxExt;
   P.dirCos = (const float *)h->dDir.p;
   P.uniformSsa = h->uniformSsa; P.uniformPf = h->uniformPf;
-  if (h->layout.total >= ((int64_t)1 << 31)) return h->fail("tally buffer too large (2^31 elements or more)");
   P.tally = tally;
   const TallyView &V = h->view;
   P.oUp = (int)V.fluxUp; P.oDown = (int)V.fluxDown; P.oAbs = (int)V.fluxAbsorbed; P.oVol = (int)V.volumeAbsorption;
   P.oInt = (int)V.intensityByComponent; P.oExc = (int)V.intensityExcess; P.oCnt = (int)V.counters;
-  const size_t ncol = (size_t)h->nx * h->ny, ncell = ncol * h->nz;
-  size_t lds = sizeof(float) * ((h->nx + 1) + (h->ny + 1) + (h->nz + 1) + 3 * (size_t)h->nDir);
-  // radiance runs: every wave's ring of local-estimate events (one record serves the nDir rays of an event) and its
-  // buffer of ready-made rays (photon_kernel, ray mode)
-  // (one direction: no ring, a ready store of two wavefronts -- photon_kernel, DIRECT)
-  P.rayQueueCap = h->nDir > 0 && !direct_rays(h) ? 64 : 0;   // (an event phase pushes at most 64 records; the rays go on to the ready buffer)
-  if (h->nDir > 0) lds += sizeof(float) * 4 * (kRecWords * (size_t)P.rayQueueCap + kReadyWords * (size_t)(direct_rays(h) ? kDirectReady : kReadyRays));
-  if (h->nDir > 0) lds += sizeof(float) * (16 * (size_t)h->nDir + 3);   // per direction: what a ray derives from it (Lds::dirTab, 16-byte aligned)
-  // (`lds` steers the decisions below and is an upper bound; what a launch allocates is lds_plan's own end: lds_bytes)
-  if (h->nDir > 0)
-    for (int c = 0; c < h->ncomp; ++c)
-      if (h->maxPfIndex[c] >= 65536) return h->fail("radiance runs take at most 65535 phase-function table entries per component");
-  if (lds > kLdsHard) return h->fail("domain edge vectors do not fit in LDS (nx + ny + nz beyond about 39 000)");
-  // (records over a base profile keep the profile in LDS as well: where edges and profile together are beyond what a launch may
-  // have, the automatic place reads the field as it would without the records -- in bricks beyond 4 MB, else linearly -- instead of
-  // planning a launch that launch's own check refuses)
-  if (P.colBase && h->gridPlace == I3RC_GRID_AUTO && lds + sizeof(float) * (size_t)h->nz > kLdsHard) {
-    P.colRec = nullptr; P.colBase = nullptr;
-    if (ncell_bytes(h) > ((size_t)4 << 20) && h->nz <= 65534) P.extBrick = (const float *)h->dExtBrick.p;
-  }
-  const size_t budget = kLdsBudget;
-  P.ldsTallies = 0;
-  // (a fused multi-batch launch tallies per batch, straight into global memory: no partial sums in LDS)
-  // (float64 partial sums: tracer.hpp, tally_t; + 4: their 8-byte alignment.  I3RC_LDS_TALLIES=0 / i3rc_hip_set_lds_tallies(h, 0): every
-  // tally straight to the float64 buffer in global memory -- a measurement knob, and one more order of the same float64 additions)
-  static const bool ldsTalliesEnv = env_on("I3RC_LDS_TALLIES");
-  const bool privatise = !fused && ldsTalliesEnv && h->ldsTalliesOn;
-  if (privatise && lds + 2 * ncol * sizeof(tally_t) + 4 <= kLdsBudget / 2) { P.ldsTallies = 1; lds += 2 * ncol * sizeof(tally_t) + 4; }
-  // (an absorbing domain of few cells -- the step cloud's 512 or 1024 --: its volume-absorption tallies, which every scattering adds to)
-  P.ldsVolume = 0;
-  if (privatise && h->absorbing && lds + ncell * sizeof(tally_t) + 4 <= kLdsBudget / 2) { P.ldsVolume = 1; lds += ncell * sizeof(tally_t) + 4; }
-  P.ldsIntensity = 0;
-  {
-    const size_t nInt = (size_t)(h->ncomp + 1) * h->nDir * ncol * sizeof(tally_t) + 4;
-    if (privatise && h->nDir > 0 && nInt <= 16 * 1024 && lds + nInt <= kLdsBudget) { P.ldsIntensity = 1; lds += nInt; }
-  }
-  P.ldsGrid = 0;
-  if (h->gridPlace == I3RC_GRID_AUTO && lds + ncell * sizeof(float) <= budget) { P.ldsGrid = 1; lds += ncell * sizeof(float); P.colRec = nullptr; P.colBase = nullptr; P.extBrick = nullptr; }   // (never when the edges alone are beyond the budget)
-  else if (P.extBrick && h->nDir == 0) lds += sizeof(uint32_t) * (size_t)h->clearWords;          // bricked field, flux kernels: its clear-air map
-  if (P.colBase) lds += sizeof(float) * (size_t)h->nz;                                            // column records over a base profile: the profile
-  plan.ldsBytes = (lds + 15) & ~(size_t)15;
-  plan.intensity = h->nDir > 0;
-  plan.place = P.ldsGrid ? GRID_LDS : (P.colRec ? (P.colBase ? GRID_COLBASE : GRID_COLUMNS) : (P.extBrick ? GRID_BRICKS : GRID_GLOBAL));
+  P.rayQueueCap = d.rayQueueCap;
+  P.ldsTallies = d.ldsTallies; P.ldsVolume = d.ldsVolume; P.ldsIntensity = d.ldsIntensity; P.ldsGrid = d.ldsGrid;
   return 0;
 }
 
@@ -1054,22 +832,6 @@ int absorbed_columns(i3rc_hip_integrator *h, hipStream_t stream, double *blocks,
   }
   return 0;
 }
-
-// Dynamic LDS of one launch: the end of the kernel's own carve-up (lds_plan, tracer.hpp -- the function photon_kernel sets its
-// pointers from), for the instantiation that is about to run.
-template <class Rng>
-size_t lds_bytes(const i3rc_hip_integrator *h, const LaunchPlan &plan, bool tableInLds, bool startStore) {
-  const LdsPlan lp = lds_plan(plan.P, plan.intensity && !Rng::kReplay, direct_rays(h), plan.place, plan.intensity, tableInLds ? 16 : 4,
-                              tableInLds ? plan.P.comp0.nInv : 0, startStore);
-  size_t words = (size_t)lp.end;
-  if constexpr (Rng::kExtra == EXTRA_TRACKS)   // the track-length sums behind the plan's end (launch_extra decides; photon_kernel, TRACK)
-    if (plan.P.ldsGrid & kLdsGridTrackSums) words = (size_t)track_sums_word(lp.end) + 2 * (size_t)plan.P.nx * plan.P.ny * plan.P.nz;
-  return (sizeof(float) * words + 15) & ~(size_t)15;
-}
-// the waves' start stores in a workgroup of `threads` (photon_kernel, STORE; StartSlot, tracer.hpp)
-constexpr size_t start_store_bytes(int threads) { return sizeof(float) * kStartWords * kStartSlots * (size_t)(threads / 64); }
-// what a launch may allocate: a compute unit's LDS less the kernels' static LDS (kStaticLdsBytes, tracer.hpp: the store kernels use all of it)
-constexpr size_t kLdsLaunchMax = 160 * 1024 - kStaticLdsBytes;
 
 int upload_source(i3rc_hip_integrator *h, const i3rc_source *src, int64_t n, RunArgs &A) {
   A.srcKind = src->kind;
@@ -1105,34 +867,26 @@ int upload_source(i3rc_hip_integrator *h, const i3rc_source *src, int64_t n, Run
   return 0;
 }
 
+// A launch's decision, its DevProblem and its source, in the order a call reports what it refuses: the problem's completeness, the
+// source (upload_source), then LDS.
+int prepare_launch(i3rc_hip_integrator *h, const StreamKind &s, const i3rc_source *src, int64_t n, hipStream_t stream, double *tally,
+                   Launch &L, RunArgs &A) {
+  L.d = plan_launch(*h, EnvKnobs::process(), {s, src->kind});
+  if (!L.d.refusal.empty() && L.d.early) return h->fail(L.d.refusal);
+  if (upload_source(h, src, n, A)) return 1;
+  if (!L.d.refusal.empty()) return h->fail(L.d.refusal);
+  return make_problem(h, L.d, L.P, stream, tally);
+}
+
 // A production instantiation of photon_kernel: its template arguments after the stream -- the key a launch looks it up by --, the kernel
 // and its name, formatted from the same arguments in the form tools/kernel_resources.demangle_photon_kernel gives the code object's
 // symbol.  lastKernelName is set from the entry that is launched, so a name a test asserts on is the kernel that ran.
 using Kernel = void (*)(DevProblem, RunArgs, int, int);
-struct KernelKey {
-  bool intensity, general;
-  int place;                 // GridPlace
-  bool tbl, direct, wide;    // (the inverse table in LDS; one radiance direction without the event ring; the widened class, MULTI)
-  bool operator==(const KernelKey &o) const {
-    return intensity == o.intensity && general == o.general && place == o.place && tbl == o.tbl && direct == o.direct && wide == o.wide;
-  }
-};
 struct KernelEntry {
   KernelKey key;
   Kernel fn;
   const char *name;
 };
-
-// what i3rc_hip_last_plan reports of a launch: recorded where lastKernelName is, from the values the launch goes on with
-void record_plan(i3rc_hip_integrator *h, const LaunchPlan &plan, bool tableInLds, size_t ldsBytes, int fusedBatches, size_t startStoreBytes) {
-  const DevProblem &P = plan.P;
-  const int rec = P.cellRec == nullptr ? 0 : (h->ncomp == 1 ? 8 : (h->ncomp == 2 ? 16 : 32));
-  const int32_t v[i3rc_hip_integrator::kPlanWords] = {P.ldsGrid ? 1 : 0, P.ldsTallies ? 1 : 0, P.ldsVolume ? 1 : 0, P.ldsIntensity ? 1 : 0,
-                                                      tableInLds ? 1 : 0, (int32_t)ldsBytes, h->absorbing ? 1 : 0, rec, fusedBatches, plan.place,
-                                                      (int32_t)startStoreBytes, 0 /* the chunk: launch_grid, once it is known */,
-                                                      (P.ldsGrid & kLdsGridTrackSums) ? 1 : 0};
-  std::memcpy(h->lastPlan, v, sizeof(v));
-}
 
 template <class Rng>
 constexpr const char *rng_name() {
@@ -1159,7 +913,7 @@ void add(std::vector<KernelEntry> &v, std::integer_sequence<int, GRID...>) {
 }
 using AllPlaces = std::integer_sequence<int, GRID_LDS, GRID_GLOBAL, GRID_BRICKS, GRID_COLUMNS, GRID_COLBASE>;
 // (GRID_COLBASE -- column records over a base profile -- exists for the kernels that run domains of several components: the general
-// ones and the widened ones; make_problem never plans it for anything else, nor for the replay build)
+// ones and the widened ones; plan_launch never plans it for anything else, nor for the replay build)
 using NoColbase = std::integer_sequence<int, GRID_LDS, GRID_GLOBAL, GRID_BRICKS, GRID_COLUMNS>;
 
 // The production instantiations, once per stream.  Template arguments after the stream: INTENSITY, GENERAL, TBL, DIRECT, MULTI.
@@ -1211,92 +965,25 @@ int extra_tally_refused(i3rc_hip_integrator *h, const char *who, bool batches) {
   return 0;
 }
 
-struct KernelChoice {
-  const KernelEntry *kern;   // nullptr: the stream has no instantiation for the key
-  int threads;
-  bool tableInLds;
-  bool startStore;           // the kernel starts its photons from per-wave start stores in LDS (photon_kernel, STORE)
-};
-
-// Which kernel runs a launch (see photon_kernel).  Fused launches (PhiloxBatchStream) are made for the specialised problems only
-// (fuse_loop): the common class, or the widened one.  Plain launches run the specialised kernels when the problem is in the common
-// class, the widened radiance kernels for radiance problems of the widened class, else the general kernel.
-template <class Rng>
-KernelChoice choose_kernel(const i3rc_hip_integrator *h, const LaunchPlan &plan, int srcKind) {
-  constexpr bool fused = Rng::kBatched;
-  const int place = plan.place;
-  KernelKey key{plan.intensity, true, place, false, false, false};
-  int threads = 256;
-  // (an extra tally block: the general flux kernel whatever the problem's class -- the key as it stands)
-  if constexpr (!Rng::kReplay && Rng::kExtra == EXTRA_NONE) {   // (the replay build always runs the general kernel: it keeps the nested local estimate, no queue at all)
-    bool simple, wide;
-    if (fused) {
-      // the widened class (several components, irregular x / y, a gridded surface): its own fused kernels, flux ones too -- a driver's
-      // loop of 1e6-photon batches on Landsat-36 + gas then costs 1.1 ms per batch instead of 2.6 (profiles/r05_fused_wide.txt)
-      simple = common_class(h, srcKind);
-      wide = !simple;
-    } else {
-      simple = common_class(h, srcKind) && h->kernelVariant != I3RC_KERNEL_GENERAL && !(kNestedBuild && plan.intensity);
-      // several components, otherwise the common class: RADIANCE problems run photon_kernel<..., MULTI> (+20 % on the Landsat scene + gas
-      // with seven directions against the general radiance kernels' 166 registers and three waves per SIMD).  Flux problems stay with
-      // the general flux kernel: its several-components specialisation was built and measured -- 5.78 against 5.71e8 photons/s on
-      // Landsat-119 + gas, 9.13 against 9.08e8 on Landsat-36 + gas: the voxel steps are the same code, and a flux event's few extra
-      // reads do not show (profiles/r05_ab_experiments.txt) -- and is not in the tree.
-      wide = !simple && plan.intensity && multi_class(h, srcKind) && h->kernelVariant != I3RC_KERNEL_GENERAL && !kNestedBuild;
-    }
-    key.general = !simple && !wide;
-    key.wide = wide;
-    key.direct = plan.intensity && direct_rays(h);
-    // Flux problems of the common class with ONE phase-function entry keep the inverse table's cosines (40 KB) in LDS, in
-    // workgroups of 1024 threads, two per compute unit (photon_kernel, TBL): the two dependent table reads of a scattering come
-    // from LDS instead of L2 -- or, where the extinction field fills the L2 (Landsat-36: 2.4 MB of 4), instead of the fabric.
-    // Step cloud 29.75 -> 29.29 ms per 1e8 photons (+1.6 %), radar 640 +2 %, Landsat-36 87.0 -> 71.0 ms (+22 %).  The fused
-    // instantiations are planned for eight waves per SIMD -- two workgroups per compute unit -- and pay for it with two vector
-    // registers in scratch.  I3RC_TABLE_LDS=0 switches both off.
-    static const bool tblOn = env_on("I3RC_TABLE_LDS");
-    // (grid places as a bit mask: LDS, global memory and column records.  Plain launches on bricked fields: Landsat-119 -2.5 %, the
-    // scene tiled 2 x 2 +10 %: left out.  Fused: Landsat-36 +13 %, radar 640 +12 %, step cloud +1.5 ... 3 % in the kernels' own time;
-    // on column records +1 ... 2.5 %)
-    static const int plainPlaces = (int)env_int("I3RC_TABLE_LDS_PLACES", 11);
-    static const int fusedPlaces = (int)env_int("I3RC_FUSED_TABLE_LDS_PLACES", 11);
-    const bool placeOk = fused ? ((fusedPlaces >> place) & 1) && place != GRID_BRICKS
-                               : ((plainPlaces >> place) & 1) && place != GRID_COLBASE && h->kernelVariant == I3RC_KERNEL_AUTO;
-    // (the 16 waves' start stores -- photon_kernel, STORE: 16 KB -- count: two workgroups of 1024 threads share a compute unit's 160 KB.
-    // A domain that had room for the table without them runs the 256-thread kernel of its place, as the domains just beyond it always did.)
-    const size_t tblStore = has_start_store<Rng>(plan.intensity, false, place, false) ? start_store_bytes(1024) : 0;
-    if (tblOn && simple && !plan.intensity && placeOk && (plan.P.uniformPf >= 1 || h->nInvEntries[0] == 1) &&
-        plan.ldsBytes + sizeof(float) * (size_t)plan.P.comp0.nInv + tblStore <= 79 * 1024) {
-      key.tbl = true;
-      threads = 1024;
-    }
-  }
-  // The start store comes on top of what make_problem has placed in LDS -- edges, tallies, the field: every domain keeps its place --
-  // and is part of the launch's allocation (lds_bytes).  Where that would go beyond a compute unit's LDS (edge vectors of some 154 KB or
-  // more: a column of 39 000 layers) the launch runs the general flux kernel, which has no store, instead of being refused.
-  bool startStore = has_start_store<Rng>(key.intensity, key.general, key.place, key.wide);
-  if (startStore && lds_bytes<Rng>(h, plan, key.tbl, true) > kLdsLaunchMax) {
-    key.general = true; key.tbl = false; threads = 256;
-    startStore = false;
-  }
-  for (const KernelEntry &e : stream_kernels<Rng>())
-    if (e.key == key) return {&e, threads, key.tbl, startStore};
-  return {nullptr, threads, key.tbl, startStore};
+const char *no_kernel_text(bool fused) {
+  return fused ? "internal: no fused kernel for this problem at this place of the extinction field"
+               : "internal: no kernel for this problem at this place of the extinction field";
 }
 
-// One grid of the kernel chosen for `plan` on `stream`: the LDS check, the record of the launch (lastKernelName, i3rc_hip_last_plan),
+// One grid of the kernel decided for the launch on `stream`: the record of the launch (lastKernelName, i3rc_hip_last_plan),
 // occupancy and block count, then `prepare(blocks, threads)` -- what the caller puts on the stream in front of the kernel, and may
 // change A -- and the launch between the events of the timing ring.  fusedBatches: the batches of a fused launch (0: a plain one).
 template <class Rng, class Prepare>
-int launch_grid(i3rc_hip_integrator *h, const LaunchPlan &plan, RunArgs &A, hipStream_t stream, int fusedBatches, bool timeIt, Prepare &&prepare) {
-  const KernelChoice c = choose_kernel<Rng>(h, plan, A.srcKind);
-  const int threads = c.threads;
-  const size_t ldsBytes = lds_bytes<Rng>(h, plan, c.tableInLds, c.startStore);
-  if (ldsBytes > kLdsLaunchMax) return h->fail("the launch needs more LDS than a compute unit has");
-  if (!c.kern) return h->fail(Rng::kBatched ? "internal: no fused kernel for this problem at this place of the extinction field"
-                                            : "internal: no kernel for this problem at this place of the extinction field");
-  const void *fn = (const void *)c.kern->fn;
-  h->lastKernelName = c.kern->name;
-  record_plan(h, plan, c.tableInLds, ldsBytes, fusedBatches, c.startStore ? start_store_bytes(threads) : 0);
+int launch_grid(i3rc_hip_integrator *h, const Launch &L, RunArgs &A, hipStream_t stream, int fusedBatches, bool timeIt, Prepare &&prepare) {
+  const KernelEntry *kern = nullptr;
+  for (const KernelEntry &e : stream_kernels<Rng>())
+    if (e.key == L.d.key) kern = &e;
+  if (!kern) return h->fail(no_kernel_text(Rng::kBatched));
+  const int threads = L.d.threads;
+  const size_t ldsBytes = L.d.ldsBytes;
+  const void *fn = (const void *)kern->fn;
+  h->lastKernelName = kern->name;
+  plan_words(*h, L.d, fusedBatches, h->lastPlan);
   int perCU = h->blocksPerCU;
   if (perCU <= 0) {
     int occ = 0;
@@ -1307,7 +994,7 @@ int launch_grid(i3rc_hip_integrator *h, const LaunchPlan &plan, RunArgs &A, hipS
     // kernels have the registers for five at most; fields within L2 gain up to 7.)
     // With the XCD-aware photon order: Landsat-119 5 ... 8 alike (6.5e8); the scene tiled 2 x 2 (31 MB): 4 workgroups 5.41e8,
     // 5 5.02e8, 6-8 4.6e8.
-    if (plan.place == GRID_BRICKS) perCU = std::min(perCU, ncell_bytes(h) > ((size_t)16 << 20) ? 4 : 5);
+    if (L.d.place == GRID_BRICKS) perCU = std::min(perCU, ncell_bytes(*h) > ((size_t)16 << 20) ? 4 : 5);
   }
   if (ldsBytes > 48 * 1024)
     HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
@@ -1316,14 +1003,14 @@ int launch_grid(i3rc_hip_integrator *h, const LaunchPlan &plan, RunArgs &A, hipS
   const long long need = (photons + threads - 1) / threads;
   if (blocks > need) blocks = std::max(1ll, need);
   if (prepare(blocks, threads)) return 1;
-  h->lastPlan[i3rc_hip_integrator::kPlanChunk] = A.chunk;   // (photons -- fused launches: per chunk number -- a wave takes per visit of the work counter)
+  h->lastPlan[kPlanChunk] = A.chunk;   // (photons -- fused launches: per chunk number -- a wave takes per visit of the work counter)
   const int slot = (int)(h->timedLaunches % i3rc_hip_integrator::kEventRing);
   if (timeIt) HIPCHK(h, hipEventRecord(h->evStart[slot], stream));
   {
     // thresholds the caller did not fix are adapted per wave (photon_kernel); negative = adaptive, starting value
     const int evThreshold = h->evThreshold > 0 ? h->evThreshold : -40;
     const int lightThreshold = h->lightThreshold > 0 ? h->lightThreshold : -24;
-    hipLaunchKernelGGL(c.kern->fn, dim3((unsigned)blocks), dim3(threads), ldsBytes, stream, plan.P, A, evThreshold, lightThreshold);
+    hipLaunchKernelGGL(kern->fn, dim3((unsigned)blocks), dim3(threads), ldsBytes, stream, L.P, A, evThreshold, lightThreshold);
   }
   HIPCHK(h, hipGetLastError());
   if (timeIt) { HIPCHK(h, hipEventRecord(h->evStop[slot], stream)); h->timedLaunches++; }
@@ -1331,9 +1018,9 @@ int launch_grid(i3rc_hip_integrator *h, const LaunchPlan &plan, RunArgs &A, hipS
 }
 
 template <class Rng>
-int launch(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
+int launch(i3rc_hip_integrator *h, const Launch &L, const RunArgs &A, hipStream_t stream, bool timeIt) {
   RunArgs B = A;   // photon indices are handed to waves in chunks (one returning atomic per chunk)
-  const int rc = launch_grid<Rng>(h, plan, B, stream, 0, timeIt, [&](long long blocks, int threads) -> int {
+  const int rc = launch_grid<Rng>(h, L, B, stream, 0, timeIt, [&](long long blocks, int threads) -> int {
     // XCD-aware photon order.  A field beyond an XCD's L2 (bricks) is shared by eight L2s that each see all of it: when
     // the photons a wave traces start in "its" eighth of the domain -- workgroups are dealt round-robin over the XCDs, the
     // kernel reads its XCC id -- an XCD's L2 has an eighth of the field (and its surroundings) to hold.  The launch's
@@ -1346,7 +1033,7 @@ int launch(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hip
     static const bool slabsOn = env_on("I3RC_SLABS");
     B.slabIds = nullptr; B.slabMeta = nullptr;
     if constexpr (!Rng::kReplay) {
-      if (slabsOn && plan.place == GRID_BRICKS && (!plan.intensity || ncell_bytes(h) > ((size_t)16 << 20)) && A.srcKind == 0 && A.nPhotons >= 1024 && A.nPhotons < ((long long)1 << 32)) {
+      if (slabsOn && L.d.place == GRID_BRICKS && (!L.d.key.intensity || ncell_bytes(*h) > ((size_t)16 << 20)) && A.srcKind == 0 && A.nPhotons >= 1024 && A.nPhotons < ((long long)1 << 32)) {
         auto &sb = h->slabBufs[stream];
         if (sb.ids.bytes < (size_t)A.nPhotons * sizeof(uint32_t)) HIPCHK(h, sb.ids.alloc((size_t)A.nPhotons * sizeof(uint32_t)));
         if (!sb.meta.p || sb.meta.bytes != sizeof(SlabMeta)) HIPCHK(h, sb.meta.alloc(sizeof(SlabMeta)));
@@ -1375,7 +1062,7 @@ int launch(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hip
     return 0;
   });
   if (rc) return 1;
-  return absorbed_columns(h, stream, plan.P.tally, 1, 0);
+  return absorbed_columns(h, stream, L.P.tally, 1, 0);
 }
 
 // ---- fused multi-batch launches ---------------------------------------------------------------------------------------
@@ -1499,7 +1186,7 @@ bool fuse_loop(const i3rc_hip_integrator *h, int64_t nPhotons, int nBatches) {
   static const bool radianceOff = !env_on("I3RC_FUSED_RADIANCE");
   if (h->nDir > 0 && (radianceOff || kNestedBuild)) return false;
   // (round 5: the widened class too -- several components, an irregular x / y grid, a gridded surface: photon_kernel<PhiloxBatchStream, ..., MULTI>)
-  return (common_class(h, 0) || multi_class(h, 0)) && h->kernelVariant != I3RC_KERNEL_GENERAL && nPhotons < ((int64_t)1 << 31) &&
+  return (common_class(*h, 0) || multi_class(*h, 0)) && h->kernelVariant != I3RC_KERNEL_GENERAL && nPhotons < ((int64_t)1 << 31) &&
          h->layout.total * (int64_t)sizeof(double) <= ((int64_t)256 << 20) && (h->fusion == 1 || (nBatches >= 2 && nPhotons <= 20000000));
 }
 
@@ -1562,12 +1249,12 @@ int launch_fused_group(i3rc_hip_integrator *h, i3rc_hip_integrator::FusedSlot &g
                        int64_t nPhotons, const i3rc_source *src, bool timeIt, int reserve = 0, bool moments = false) {
   const int R = fused_replicas(h);
   if (ready_fused_slot(h, g, count, R, reserve, !moments)) return 1;
-  LaunchPlan plan;
+  Launch L;
   RunArgs A;
   std::memset(&A, 0, sizeof(A));
   A.seed0 = seed0; A.seed1 = seed1; A.firstPhoton = 0; A.nPhotons = nPhotons;
   A.workCounter = (unsigned long long *)g.counter.p;
-  if (make_problem(h, plan, g.stream, (double *)g.blocks.p, true) || upload_source(h, src, nPhotons, A)) return 1;
+  if (prepare_launch(h, stream_of<PhiloxBatchStream>(), src, nPhotons, g.stream, (double *)g.blocks.p, L, A)) return 1;
   // (chunks: a wave takes this many photons of ONE batch per visit of the work counter; a lane hands its counts over when
   // its batch changes, so longer chunks mean fewer atomics, shorter ones a shorter end of the launch)
   static const int chunk = (int)std::max(64ll, env_int("I3RC_FUSED_CHUNK", 512));
@@ -1581,7 +1268,7 @@ int launch_fused_group(i3rc_hip_integrator *h, i3rc_hip_integrator::FusedSlot &g
   A.counterBlocks = (double *)g.counterBlocks.p;
   if ((uint64_t)count * R >= ((uint64_t)1 << 31)) return h->fail("fused launch: too many tally blocks");
   const size_t outBytes = (size_t)count * h->layout.total * sizeof(double);
-  const int rc = launch_grid<PhiloxBatchStream>(h, plan, A, g.stream, count, timeIt, [&](long long, int) -> int {
+  const int rc = launch_grid<PhiloxBatchStream>(h, L, A, g.stream, count, timeIt, [&](long long, int) -> int {
     *g.abortFlag = 0;
     HIPCHK(h, hipMemsetAsync(g.blocks.p, 0, outBytes * R, g.stream));
     HIPCHK(h, hipMemsetAsync(g.counter.p, 0, sizeof(unsigned long long), g.stream));
@@ -1753,12 +1440,12 @@ void top_up_groups(i3rc_hip_integrator *h, uint32_t seed0, uint32_t nextIfNone, 
 // that a column's sum could leave the range where float32 still counts (2^24).  Per-photon random streams make a
 // long batch the same as several launches over consecutive photon ranges, so very long Directional batches are cut
 // into launches of at most 2^22 photons per compute unit (about 1e9 photons on an MI355X).
-int launch_extra(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt);   // (at the end of this file)
-int launch_batch_parts(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
+int launch_extra(i3rc_hip_integrator *h, const Launch &L, const RunArgs &A, hipStream_t stream, bool timeIt);   // (at the end of this file)
+int launch_batch_parts(i3rc_hip_integrator *h, const Launch &L, const RunArgs &A, hipStream_t stream, bool timeIt) {
   const int64_t perLaunch = h->launchLimit > 0 ? h->launchLimit : (int64_t)h->numCU << 22;
   // (an extra tally block switched on: the same photons through the general flux kernel under the kind's tag, see launch_extra)
   const auto run = [&](const RunArgs &part) {
-    return h->extra == EXTRA_NONE ? launch<PhiloxStream>(h, plan, part, stream, timeIt) : launch_extra(h, plan, part, stream, timeIt);
+    return h->extra == EXTRA_NONE ? launch<PhiloxStream>(h, L, part, stream, timeIt) : launch_extra(h, L, part, stream, timeIt);
   };
   if (A.srcKind != 0) return run(A);
   for (int64_t done = 0; done < A.nPhotons; done += perLaunch) {
@@ -1774,15 +1461,15 @@ int launch_batch_parts(i3rc_hip_integrator *h, const LaunchPlan &plan, const Run
 // the slot's stream.  `who` names the caller in the error texts.
 int run_batch_in_slot(i3rc_hip_integrator *h, i3rc_hip_integrator::PipeSlot &sl, uint32_t seed0, uint32_t seed1, int64_t nPhotons,
                       const i3rc_source *src, bool timeIt, bool copyBack, const char *who) {
-  LaunchPlan plan;
+  Launch L;
   RunArgs A;
   std::memset(&A, 0, sizeof(A));
   A.seed0 = seed0; A.seed1 = seed1; A.firstPhoton = 0; A.nPhotons = nPhotons;
   A.workCounter = (unsigned long long *)sl.counter.p;
-  if (make_problem(h, plan, sl.stream, (double *)sl.tally.p) || upload_source(h, src, nPhotons, A)) return 1;
+  if (prepare_launch(h, plain_stream(h->extra), src, nPhotons, sl.stream, (double *)sl.tally.p, L, A)) return 1;
   const size_t bytes = (size_t)h->layout.total * sizeof(double);
   if (hipMemsetAsync(sl.tally.p, 0, bytes, sl.stream) != hipSuccess) return h->fail(std::string(who) + ": clearing a tally buffer failed");
-  if (launch_batch_parts(h, plan, A, sl.stream, timeIt)) return 1;
+  if (launch_batch_parts(h, L, A, sl.stream, timeIt)) return 1;
   if (copyBack && (hipMemcpyAsync(sl.pinned, sl.tally.p, bytes, hipMemcpyDeviceToHost, sl.stream) != hipSuccess ||
                    hipEventRecord(sl.done, sl.stream) != hipSuccess))
     return h->fail(std::string(who) + ": copying a batch's tallies back failed");
@@ -1800,14 +1487,13 @@ int i3rc_hip_launch_batch(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1
   if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");  // illumination :78-79
   if (extra_tally_refused(h, "i3rc_hip_launch_batch", false)) return 1;
   HIPCHK(h, hipSetDevice(h->device));
-  LaunchPlan plan;
-  if (make_problem(h, plan, h->stream, h->tally)) return 1;
+  Launch L;
   RunArgs A;
   std::memset(&A, 0, sizeof(A));
   A.seed0 = seed0; A.seed1 = seed1; A.firstPhoton = firstPhoton; A.nPhotons = nPhotons;
   A.workCounter = (unsigned long long *)h->workCounter.p;
-  if (upload_source(h, src, nPhotons, A)) return 1;
-  return launch_batch_parts(h, plan, A, h->stream, true);
+  if (prepare_launch(h, plain_stream(h->extra), src, nPhotons, h->stream, h->tally, L, A)) return 1;
+  return launch_batch_parts(h, L, A, h->stream, true);
 }
 
 // The batch loop of a driver (Example-Drivers/monteCarloDriver.f95:283-326) as one call: see include/i3rc_hip.h
@@ -1986,8 +1672,7 @@ int i3rc_hip_expect_batches(i3rc_hip_integrator *h, uint32_t seed0, uint32_t see
   drop_lookahead(h);
   if (!fuse_loop(h, nPhotons, nBatches)) return 0;   // (the caller goes on as it would have)
   {   // the problem must be complete before anything is launched (as i3rc_hip_compute_batch would find out)
-    LaunchPlan plan;
-    if (make_problem(h, plan, h->stream, h->tally, true)) return 1;
+    if (const char *missing = incomplete(*h)) return h->fail(missing);
   }
   i3rc_hip_integrator::BatchSignature sig;
   sig.seed0 = seed0; sig.n = nPhotons; sig.mu = src->solarMu; sig.az = src->solarAzimuth; sig.set = true;
@@ -2010,13 +1695,12 @@ int i3rc_hip_run_replay(i3rc_hip_integrator *h, int64_t nPhotons, const i3rc_sou
   if (!src || !randoms || !drawStart || nPhotons <= 0) return h->fail("i3rc_hip_run_replay: bad arguments");
   if (h->extra == EXTRA_TRACKS) return h->fail("i3rc_hip_run_replay: the actinic flux is tallied by the production stream's kernels only; the replay build has no such kernel (switch it off)");
   HIPCHK(h, hipSetDevice(h->device));
-  LaunchPlan plan;
-  if (make_problem(h, plan, h->stream, h->tally, false, true)) return 1;
+  Launch L;
   RunArgs A;
   std::memset(&A, 0, sizeof(A));
   A.nPhotons = nPhotons;
   A.workCounter = (unsigned long long *)h->workCounter.p;
-  if (upload_source(h, src, nPhotons, A)) return 1;
+  if (prepare_launch(h, stream_of<ReplayStream>(), src, nPhotons, h->stream, h->tally, L, A)) return 1;
   DevBuf dR, dS, dFate, dCol, dW, dOrd, dUsed;
   HIPCHK(h, dR.upload(randoms, sizeof(float) * (size_t)nRandoms));
   HIPCHK(h, dS.upload(drawStart, sizeof(int64_t) * (size_t)nPhotons));
@@ -2029,7 +1713,7 @@ int i3rc_hip_run_replay(i3rc_hip_integrator *h, int64_t nPhotons, const i3rc_sou
     A.fate = (int32_t *)dFate.p; A.fateColumn = (int32_t *)dCol.p; A.fateWeight = (float *)dW.p;
     A.fateOrder = (int32_t *)dOrd.p; A.drawsUsed = (int32_t *)dUsed.p;
   }
-  if (launch<ReplayStream>(h, plan, A, h->stream, false)) return 1;
+  if (launch<ReplayStream>(h, L, A, h->stream, false)) return 1;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (rec) {
     HIPCHK(h, hipMemcpy(fate, dFate.p, sizeof(int32_t) * nPhotons, hipMemcpyDeviceToHost));
@@ -2051,36 +1735,22 @@ int i3rc_hip_trace_rays(i3rc_hip_integrator *h, int64_t n, const float *dir, flo
       return h->fail("i3rc_hip_trace_rays: start cell outside the domain");
   }
   HIPCHK(h, hipSetDevice(h->device));
-  LaunchPlan plan;
-  // tables are not needed for bare tracing: build the problem without the completeness checks
-  const std::vector<CompTables> saved = h->comp;
-  static const float dummy = 0.f;
-  for (int c = 0; c < h->ncomp; ++c) if (!h->comp[c].inv) h->comp[c].inv = &dummy;
-  const int savedDir = h->nDir;
-  h->nDir = 0;
-  const int rc = make_problem(h, plan, h->stream, h->tally);
-  h->nDir = savedDir;
-  h->comp = saved;
-  h->compDirty = true;
-  if (rc) return 1;
-  plan.P.ldsGrid = 0; plan.P.ldsTallies = 0;
-  // the hook reads the bricked copy (its index is checked bit for bit) unless i3rc_hip_select_grid_place asked for the plain
-  // field or the column records
-  const int hookPlace = h->gridPlace == I3RC_GRID_LINEAR ? GRID_GLOBAL : (h->gridPlace == I3RC_GRID_COLUMNS ? (h->dColBase.p ? GRID_COLBASE : GRID_COLUMNS) : GRID_BRICKS);
-  plan.P.extBrick = (const float *)h->dExtBrick.p;
-  plan.P.colRec = (const uint2 *)h->dColRec.p;
-  plan.P.colBase = (const float *)h->dColBase.p;
+  // tables are not needed for bare tracing: the geometry and the field alone, in every packed form.  The hook reads the bricked copy
+  // (its index is checked bit for bit) unless i3rc_hip_select_grid_place asked for the plain field or the column records
+  DevProblem P;
+  fill_geometry(h, P);
+  const int hookPlace = h->gridPlace == I3RC_GRID_LINEAR ? GRID_GLOBAL : (h->gridPlace == I3RC_GRID_COLUMNS ? (h->colBase ? GRID_COLBASE : GRID_COLUMNS) : GRID_BRICKS);
   DevBuf dDir, dPos, dIdx, dTar, dTau, dSteps;
   HIPCHK(h, dDir.upload(dir, sizeof(float) * 3 * n)); HIPCHK(h, dPos.upload(pos, sizeof(float) * 3 * n));
   HIPCHK(h, dIdx.upload(idx, sizeof(int32_t) * 3 * n)); HIPCHK(h, dTar.upload(target, sizeof(float) * n));
   HIPCHK(h, dTau.alloc(sizeof(float) * n)); HIPCHK(h, dSteps.alloc(sizeof(int32_t) * n));
   const size_t lds = sizeof(float) * ((h->nx + 1) + (h->ny + 1) + (h->nz + 1)) + sizeof(uint32_t) * std::max((size_t)h->clearWords, (size_t)h->nz);
-  if (lds > 64 * 1024) return h->fail("i3rc_hip_trace_rays: domain edge vectors do not fit in LDS");
+  if (lds > kLdsBudget) return h->fail("i3rc_hip_trace_rays: domain edge vectors do not fit in LDS");
   // (more than 65534 layers: the clear-air map's 16-bit layer numbers do not reach the top -- the hook reads the bricks without it)
   auto *const hook = hookPlace == GRID_GLOBAL ? trace_rays_kernel<GRID_GLOBAL, false>
                    : (hookPlace == GRID_COLUMNS ? trace_rays_kernel<GRID_COLUMNS, false> : hookPlace == GRID_COLBASE ? trace_rays_kernel<GRID_COLBASE, false>
                                                 : (h->nz <= 65534 ? trace_rays_kernel<GRID_BRICKS, true> : trace_rays_kernel<GRID_BRICKS, false>));
-  hipLaunchKernelGGL(hook, dim3((unsigned)((n + 255) / 256)), dim3(256), lds, h->stream, plan.P, (long long)n,
+  hipLaunchKernelGGL(hook, dim3((unsigned)((n + 255) / 256)), dim3(256), lds, h->stream, P, (long long)n,
                      (const float *)dDir.p, (float *)dPos.p, (int32_t *)dIdx.p, (const float *)dTar.p, (float *)dTau.p,
                      (int32_t *)dSteps.p);
   HIPCHK(h, hipGetLastError());
@@ -2204,7 +1874,7 @@ const char *i3rc_hip_last_kernel_name(const i3rc_hip_integrator *h) { return h ?
 
 int i3rc_hip_last_plan(const i3rc_hip_integrator *h, int32_t *out, int n) {
   if (!h || !out) return 1;
-  for (int k = 0; k < std::min(n, i3rc_hip_integrator::kPlanWords); ++k) out[k] = h->lastPlan[k];
+  for (int k = 0; k < std::min(n, kPlanWords); ++k) out[k] = h->lastPlan[k];
   return 0;
 }
 
@@ -2267,23 +1937,82 @@ namespace {
 // The launch of the general flux kernel under the tag of the handle's extra tally block, through the one path every plain launch
 // takes (defined last, so that these kernels are instantiated behind every other kernel of the library: the level kernels, then the
 // track kernels).
-int launch_extra(i3rc_hip_integrator *h, const LaunchPlan &plan, const RunArgs &A, hipStream_t stream, bool timeIt) {
+int launch_extra(i3rc_hip_integrator *h, const Launch &L, const RunArgs &A, hipStream_t stream, bool timeIt) {
   switch (h->extra) {
-    case EXTRA_LEVELS: return launch<PhiloxLevelStream>(h, plan, A, stream, timeIt);
-    case EXTRA_TRACKS: {
-      // Where the field itself lies in LDS, partial sums in LDS are switched on (i3rc_hip_set_lds_tallies, I3RC_LDS_TALLIES) and the
-      // launch's allocation has room for one more float64 word per cell behind the plan's end, the workgroups keep their track-length
-      // sums there: bit 1 of ldsGrid tells the kernel, the last plan says so.
-      static const bool ldsTalliesEnv = env_on("I3RC_LDS_TALLIES");
-      LaunchPlan p = plan;
-      if (p.place == GRID_LDS && ldsTalliesEnv && h->ldsTalliesOn) {
-        p.P.ldsGrid |= kLdsGridTrackSums;
-        if (lds_bytes<PhiloxTrackStream>(h, p, false, false) > kLdsLaunchMax) p.P.ldsGrid &= ~kLdsGridTrackSums;
-      }
-      return launch<PhiloxTrackStream>(h, p, A, stream, timeIt);
-    }
+    case EXTRA_LEVELS: return launch<PhiloxLevelStream>(h, L, A, stream, timeIt);
+    case EXTRA_TRACKS: return launch<PhiloxTrackStream>(h, L, A, stream, timeIt);
     case EXTRA_NONE: break;
   }
   return h->fail("internal: no extra tally block is switched on");
 }
+
+// The production instantiation of a stream's kernels for a key, null where there is none.  (A template only for when it is instantiated:
+// behind the launches above.  The kernels of the code object stand in the order in which the launches first name their lists; a plain
+// function that names the lists would be seen first and put them in its own order.)
+template <int = 0>
+const KernelEntry *find_kernel(const StreamKind &s, const KernelKey &key) {
+  const std::vector<KernelEntry> &list = s.replay ? stream_kernels<ReplayStream>() : s.batched ? stream_kernels<PhiloxBatchStream>()
+                                         : s.extra == EXTRA_LEVELS ? stream_kernels<PhiloxLevelStream>()
+                                         : s.extra == EXTRA_TRACKS ? stream_kernels<PhiloxTrackStream>() : stream_kernels<PhiloxStream>();
+  for (const KernelEntry &e : list)
+    if (e.key == key) return &e;
+  return nullptr;
+}
+EnvKnobs env_from_words(const int32_t *w) {
+  if (!w) return EnvKnobs::process();
+  EnvKnobs e;
+  e.columns = w[0] != 0; e.ldsTallies = w[1] != 0; e.tableLds = w[2] != 0; e.plainPlaces = w[3]; e.fusedPlaces = w[4]; e.direct = w[5] != 0; e.cellRecords = w[6] != 0;
+  return e;
+}
 }  // namespace
+
+extern "C" {
+
+/* Host only: the facts of a domain's field (launch_plan.hpp, derive_facts) as words -- binding.FACT_NAMES. */
+int i3rc_hip_problem_facts(int nx, int ny, int nz, int ncomp, const float *xEdges, const float *yEdges, const float *zEdges, const float *totalExt,
+                           const float *cumExt, const float *ssa, const int32_t *pfIndex, const int32_t *env, int32_t *out, int nout) {
+  if (nx < 1 || ny < 1 || nz < 1 || ncomp < 1 || !xEdges || !yEdges || !zEdges || !totalExt || !cumExt || !ssa || !pfIndex || !out) return 2;
+  ProblemFacts f;
+  g_createError = derive_facts(f, env_from_words(env), nx, ny, nz, ncomp, xEdges, yEdges, zEdges, totalExt, cumExt, ssa, pfIndex);
+  if (!g_createError.empty()) return 1;
+  const int32_t v[kFactWords] = {f.nx, f.ny, f.nz, f.ncomp, f.xyRegular, f.zRegular, f.empty, f.absorbing, f.uniformSsa >= 0.f, f.uniformPf, f.cellRecBytes,
+                                 f.colRecords, f.colBase, f.bsx, f.bsy, f.bsz, f.nbx, f.nby, f.nbz, f.clearShift, f.clearNx, f.clearWords,
+                                 *std::max_element(f.maxPfIndex.begin(), f.maxPfIndex.end())};
+  for (int k = 0; k < std::min(nout, kFactWords); ++k) out[k] = v[k];
+  return 0;
+}
+
+/* Host only: what a launch of `kind` would be on a problem of these facts (i3rc_hip_problem_facts), this setup -- binding.SETUP_NAMES:
+ * what the setters and the handle's knobs add -- and these switches of the process (binding.ENV_NAMES; NULL: the process's own).
+ * kind: the stream (0 plain, 1 fused, 2 replay, 3 level tally, 4 track tally), the kind of the source, the batches of a fused launch. */
+int i3rc_hip_plan_launch(const int32_t *facts, const int32_t *setup, const int32_t *env, const int32_t *kind, int32_t *out, int nout,
+                         char *text, int ntext) {
+  if (!facts || !setup || !kind || !out || !text || ntext < 1 || kind[0] < 0 || kind[0] > 4 || facts[3] < 1) return 2;
+  ProblemFacts f;
+  f.nx = facts[0]; f.ny = facts[1]; f.nz = facts[2]; f.ncomp = facts[3]; f.xyRegular = facts[4]; f.zRegular = facts[5]; f.empty = facts[6] != 0;
+  f.absorbing = facts[7] != 0; f.uniformSsa = facts[8] ? 0.5f : -1.f; f.uniformPf = facts[9]; f.cellRecBytes = facts[10];
+  f.colRecords = facts[11] != 0; f.colBase = facts[12] != 0; f.bsx = facts[13]; f.bsy = facts[14]; f.bsz = facts[15]; f.nbx = facts[16];
+  f.nby = facts[17]; f.nbz = facts[18]; f.clearShift = facts[19]; f.clearNx = facts[20]; f.clearWords = facts[21];
+  f.maxPfIndex.assign(f.ncomp, facts[22]);
+  static const float present = 0.f;
+  CompTables t{};
+  f.nDir = setup[0];
+  t.inv = t.invCos = setup[1] ? &present : nullptr; t.fwd = t.fwdOrig = setup[2] ? &present : nullptr; t.nInv = setup[3];
+  f.comp.assign(f.ncomp, t); f.nInvEntries.assign(f.ncomp, setup[4]); f.nFwdEntries.assign(f.ncomp, 0);
+  f.params.useSurfaceBDRF = setup[5]; f.params.useRayTracing = setup[6]; f.nxs = setup[7]; f.nys = setup[8]; f.surfaceSet = setup[9] != 0;
+  f.extra = (ExtraTally)setup[10]; f.kernelVariant = setup[11]; f.gridPlace = setup[12]; f.ldsTalliesOn = setup[13] != 0;
+  const StreamKind s = kind[0] == 2 ? stream_of<ReplayStream>() : kind[0] == 1 ? stream_of<PhiloxBatchStream>()
+                                                                : plain_stream(kind[0] == 3 ? EXTRA_LEVELS : kind[0] == 4 ? EXTRA_TRACKS : EXTRA_NONE);
+  const LaunchDecision d = plan_launch(f, env_from_words(env), {s, kind[1]});
+  const KernelEntry *kern = d.refusal.empty() ? find_kernel(s, d.key) : nullptr;
+  const std::string say = !d.refusal.empty() ? d.refusal : kern ? kern->name : no_kernel_text(s.batched);
+  std::snprintf(text, (size_t)ntext, "%s", say.c_str());
+  if (!kern) return 1;
+  int32_t v[kPlanWords + 3];
+  plan_words(f, d, kind[2], v);
+  v[kPlanWords] = (int32_t)d.estimate; v[kPlanWords + 1] = d.rayQueueCap; v[kPlanWords + 2] = d.threads;
+  for (int k = 0; k < std::min(nout, kPlanWords + 3); ++k) out[k] = v[k];
+  return 0;
+}
+
+}  // extern "C"

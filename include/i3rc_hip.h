@@ -425,6 +425,39 @@ int i3rc_hip_lds_plan(const int32_t *q, int32_t *out);
  *   out[12] = word offset of the start stores */
 int i3rc_hip_lds_plan_words(const int32_t *q, int nq, int32_t *out, int nout);
 
+/* Test hooks, host code only (no device needed): where a launch is decided (csrc/launch_plan.hpp), in two steps.
+ *
+ * i3rc_hip_problem_facts: the facts of a domain's field, from the arrays of i3rc_hip_create -- the very derivation i3rc_hip_create
+ * makes before its first upload.
+ *   env        the switches of the process a launch reads, 7 words: I3RC_COLUMNS, I3RC_LDS_TALLIES, I3RC_TABLE_LDS (0 / 1 each),
+ *              I3RC_TABLE_LDS_PLACES, I3RC_FUSED_TABLE_LDS_PLACES (bit masks), I3RC_DIRECT, I3RC_CELL_RECORDS (0 / 1); NULL: as the
+ *              process has them
+ *   out[0..min(nout, 23) - 1] = nx, ny, nz, ncomp; x / y regular, z regular, optically empty, absorbing, an albedo every cell with
+ *              extinction shares (0 / 1 each), the table entry they share (0: none); bytes of a cell record (0, 8, 16, 32); column
+ *              records, ... over a base profile (0 / 1); the bricks' log2 sizes in x, y, z and their numbers in x, y, z; the clear-air
+ *              map's shift, width and words; the largest table entry any cell names
+ * Returns 0; 1 where i3rc_hip_create would refuse the field (the text: i3rc_hip_last_error(NULL)); 2 on a bad argument.
+ *
+ * i3rc_hip_plan_launch: the decision of a launch (plan_launch) on a problem of these facts.
+ *   facts      the 23 words above
+ *   setup      what the setters and the handle's knobs add, 14 words: nDir; every component has its inverse table, its forward tables
+ *              (0 / 1); steps and entries of component 1's inverse table; useSurfaceBDRF, useRayTracing; the surface grid's nx, ny and
+ *              whether one is set; the extra tally (0 none, 1 level fluxes, 2 actinic flux); the kernel variant (I3RC_KERNEL_*), the
+ *              grid place (I3RC_GRID_*), i3rc_hip_set_lds_tallies (0 / 1)
+ *   env        as above
+ *   kind       3 words: the stream (0 plain, 1 fused, 2 replay, 3 level tally, 4 track tally), the source's kind (i3rc_source::kind),
+ *              the batches of a fused launch
+ *   out[0..min(nout, 16) - 1] = the 13 words of i3rc_hip_last_plan as the launch would record them (the chunk, which needs the device:
+ *              0), then the estimate of a workgroup's LDS the decisions were made with (bytes), the ray queue's capacity, the
+ *              threads of a workgroup
+ *   text       the kernel's name as i3rc_hip_last_kernel_name would report it, or the refusal's text
+ * Returns 0; 1 where the launch would be refused; 2 on a bad argument. */
+int i3rc_hip_problem_facts(int nx, int ny, int nz, int ncomp, const float *xEdges, const float *yEdges, const float *zEdges,
+                           const float *totalExt, const float *cumExt, const float *ssa, const int32_t *pfIndex, const int32_t *env,
+                           int32_t *out, int nout);
+int i3rc_hip_plan_launch(const int32_t *facts, const int32_t *setup, const int32_t *env, const int32_t *kind, int32_t *out, int nout,
+                         char *text, int ntext);
+
 /* Test hook: the raw Philox4x32-10 blocks (out[n][blocksPerPhoton][4]) of photons firstPhoton..+n-1 and the
  * float32 deviates the photon streams derive from them (outf, same shape). */
 int i3rc_hip_philox_blocks(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1, int64_t firstPhoton, int64_t n,

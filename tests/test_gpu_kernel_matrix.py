@@ -16,6 +16,7 @@ import pytest
 import i3rc_monte_carlo_model_amd as M
 from tests import kernel_matrix as K
 from tests.sums import assert_same_sums
+from tests.test_launch_plan_cpu import decide_recipe
 
 pytestmark = pytest.mark.gpu
 
@@ -58,6 +59,11 @@ def check_recipe(recipe):
         else:
             got[nb, n] = [_plain(g, n)]
         assert g.kernel_name() == target, (target, g.kernel_name(), nb, n)
+        # ... and the host-only decision entry, fed the same facts and knobs, reports the plan and the name this launch recorded
+        # (the chunk needs the device: left out)
+        name, plan = decide_recipe(recipe, fused_batches=nb if recipe["fused"] else 0)
+        launched = g.last_plan()
+        assert name == g.kernel_name() and {k: plan[k] for k in launched if k != "chunk"} == {k: v for k, v in launched.items() if k != "chunk"}, (target, name, plan, launched)
     assert all(v[0]["counters"]["scatterings"] > 0 for (nb, n), v in got.items() if n == N_BIG), target
     # the reference: general kernel, linear field, tallies straight to global memory, one plain launch per batch
     g.set_batch_fusion(0)

@@ -98,7 +98,8 @@ def test_lds_budget_boundaries(flag):
     """Each LDS region at the last shape that has it and the first that does not (found by bisection on the plan of 1-photon
     launches): both shapes against the plainest launch of 30 001 photons.  Probed (size k of LDS_CASES): ldsTallies on at 314, off at
     315 (629 / 631 x 3 columns); ldsVolume 261 / 262 layers of 5 x 3; ldsIntensity 84 / 85 (169 / 171 x 3 columns, two directions);
-    ldsGrid 450 / 451 layers of 7 x 5; the inverse table in LDS 307 / 308 layers of 7 x 5.  Each found pair is printed."""
+    ldsGrid 450 / 451 layers of 7 x 5; the inverse table in LDS 193 / 194 layers of 7 x 5 (307 / 308 before the waves' start stores came
+    to lie beside the table).  Each found pair is printed; tests/test_launch_plan_cpu.py asserts the pairs from recorded launches."""
     make, params, lo, hi = LDS_CASES[flag]
     tabs = _hg(0.85)
     last_on, first_off = _edge(lambda k: _make(make(k), tabs, **params), flag, lo, hi)
@@ -405,9 +406,9 @@ def _column(nz, ncomp=1, ssa=0.0, seed=4):
 
 def test_edge_vectors_at_the_lds_hard_limit():
     """The edge vectors of a 1 x 1 column with an irregular z grid at the largest nz a launch accepts (found by bisection on
-    1-photon launches) and one layer more (refused by make_problem's host check with an I3RCError).  At the edge an omega = 0 flux
+    1-photon launches) and one layer more (refused by plan_launch's host check with an I3RCError).  At the edge an omega = 0 flux
     run reproduces Beer-Lambert transmission exp(-tau / mu0), tau in float64, within 4 binomial standard errors.  Probed: 40 443
-    layers accepted, 40 444 refused.  (The refusal is make_problem's, at the launch: i3rc_hip_create takes such a domain.)"""
+    layers accepted, 40 444 refused.  (The refusal is plan_launch's, at the launch: i3rc_hip_create takes such a domain.)"""
     tab = _hg(0.85)
 
     def accepted(nz):
@@ -489,7 +490,7 @@ def test_trace_rays_at_its_lds_limit(oracle):
 
 
 def test_a_launch_beyond_a_compute_units_lds_is_refused_on_the_host():
-    """Column records over a base profile keep the profile in LDS beside the edges.  A deep two-component column that make_problem's
+    """Column records over a base profile keep the profile in LDS beside the edges.  A deep two-component column that plan_launch's
     edge check accepts (22 000 layers: edges and profile 176 KB): on the automatic place it now reads the field linearly and runs;
     with the column records asked for, launch's own check (160 KB - 256) refuses it before anything reaches the device, nothing is
     tallied, and the handle still runs afterwards.  A field of that depth beyond 4 MB reads its bricks instead, and equals the
