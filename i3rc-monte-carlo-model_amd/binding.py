@@ -31,6 +31,7 @@ SYMBOLS = [
     "i3rc_hip_set_level_fluxes", "i3rc_hip_get_level_flux_layout", "i3rc_hip_normalise_level_fluxes",
     "i3rc_hip_set_actinic_flux", "i3rc_hip_get_actinic_flux_layout", "i3rc_hip_normalise_actinic_flux",
     "i3rc_hip_problem_facts", "i3rc_hip_plan_launch",
+    "i3rc_hip_run_batches_diagnostic_moments", "i3rc_hip_get_diagnostic_moments_layout", "i3rc_hip_diagnostic_moments_layout_words",
 ]
 
 
@@ -57,6 +58,24 @@ class TallyLayout(C.Structure):
 class MomentsLayout(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("fluxUp", "fluxDown", "fluxAbsorbed", "volumeAbsorption", "intensity", "absorbedProfile",
                                          "meanFluxUp", "meanFluxDown", "meanFluxAbsorbed", "meanIntensity", "total")]
+
+
+# i3rc_diagnostic_moments_layout; without its first word, the words of i3rc_hip_diagnostic_moments_layout_words in order
+DIAGNOSTIC_MOMENTS_NAMES = ["levelFluxUp", "levelFluxDown", "meanLevelFluxUp", "meanLevelFluxDown", "actinicFlux", "meanActinicFlux", "total"]
+EXTRA_KINDS = {"none": 0, "levels": 1, "tracks": 2}
+
+
+class DiagnosticMomentsLayout(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ["kind"] + DIAGNOSTIC_MOMENTS_NAMES]
+
+
+def diagnostic_moments_layout(kind, nx, ny, nz, nout=len(DIAGNOSTIC_MOMENTS_NAMES)):
+    """i3rc_hip_diagnostic_moments_layout_words: a dict of DIAGNOSTIC_MOMENTS_NAMES for a kind (EXTRA_KINDS, or its number) and a grid.
+    No device needed."""
+    out = (C.c_int64 * max(int(nout), 1))()
+    if load().i3rc_hip_diagnostic_moments_layout_words(int(EXTRA_KINDS.get(kind, kind)), int(nx), int(ny), int(nz), out, int(nout)) != 0:
+        raise I3RCError("i3rc_hip_diagnostic_moments_layout_words: bad arguments")
+    return dict(zip(DIAGNOSTIC_MOMENTS_NAMES, (int(v) for v in out)))
 
 
 # the words of i3rc_hip_last_plan, in order
@@ -205,6 +224,10 @@ def load():
     if hasattr(L, "i3rc_hip_plan_launch"):   # (likewise)
         L.i3rc_hip_problem_facts.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp, ip, ip, ip, C.c_int]
         L.i3rc_hip_plan_launch.argtypes = [ip, ip, ip, ip, ip, C.c_int, C.c_char_p, C.c_int]
+    if hasattr(L, "i3rc_hip_run_batches_diagnostic_moments"):   # (likewise)
+        L.i3rc_hip_run_batches_diagnostic_moments.argtypes = [H, C.c_uint32, C.c_uint32, C.c_int, C.c_int64, C.POINTER(Source), dp, dp, dp, dp, dp]
+        L.i3rc_hip_get_diagnostic_moments_layout.argtypes = [H, C.POINTER(DiagnosticMomentsLayout)]
+        L.i3rc_hip_diagnostic_moments_layout_words.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, lp, C.c_int]
     L.i3rc_hip_device_count.restype = C.c_int
     L.i3rc_hip_version.restype = C.c_char_p
     _lib = L

@@ -135,6 +135,8 @@ struct i3rc_hip_integrator : ProblemFacts {   // (the facts every launch is deci
   // i3rc_hip_run_batches_moments: sums and sums of squares over a loop's batches, accumulated on the device (momArea / momDz: the
   // device copies of areaFrac / layerDepth)
   DevBuf momSum, momSq, momCounters, momArea, momDz;
+  // i3rc_hip_run_batches_diagnostic_moments: the same of the optional diagnostic tally (extra_moments_layout), sized by the kind
+  DevBuf momExtraSum, momExtraSq;
 
   // XCD-aware photon order (launch): the sorted photon numbers and the slab bookkeeping of a launch, per stream (launches
   // on different streams -- i3rc_hip_run_batches -- are in flight together)
@@ -1174,6 +1176,44 @@ __global__ void __launch_bounds__(256) moments_means_kernel(MomentsDev M, const 
   if (q == 0 && threadIdx.x < I3RC_NUM_COUNTERS) unsafeAtomicAdd(counterTotals + threadIdx.x, raw[V.counters + threadIdx.x]);
 }
 
+// ---- ... and of the optional diagnostic tally (i3rc_hip_run_batches_diagnostic_moments) -----------------------------------------------
+// The kind's extra block of every batch, normalised by normalised_extra_value and added up in a moments block of its own
+// (extra_moments_layout): the fields lie there as the block's elements do, the domain means behind them.
+// fields: one thread per element and slice of the batches, as moments_fields_kernel
+__global__ void __launch_bounds__(256) moments_extra_fields_kernel(TallyView V, ExtraTally kind, long long block, const double *blocks, int count,
+                                                                   long long stride, long long nFields, double *sum, double *sumSq) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= nFields) return;
+  const int perSlice = (count + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int b0 = (int)blockIdx.y * perSlice, b1 = min(count, b0 + perSlice);
+  double s1 = 0.0, s2 = 0.0;
+  for (int b = b0; b < b1; ++b) {
+    const double x = (double)normalised_extra_value(V, blocks + (size_t)b * stride, kind, block, e);
+    s1 += x; s2 += x * x;
+  }
+  unsafeAtomicAdd(sum + e, s1);
+  unsafeAtomicAdd(sumSq + e, s2);
+}
+// domain means: one workgroup per (batch, level of levelFluxUp | level of levelFluxDown, or layer); mean q is the mean over the columns
+// of the elements q * ncol ... of the block, and lies at nFields + q
+__global__ void __launch_bounds__(256) moments_extra_means_kernel(TallyView V, ExtraTally kind, long long block, const double *blocks, long long stride,
+                                                                  int nMeans, long long nFields, double *sum, double *sumSq) {
+  const int b = blockIdx.x / nMeans, q = blockIdx.x - b * nMeans;
+  const double *raw = blocks + (size_t)b * stride;
+  const long long ncol = (long long)V.nx * V.ny;
+  double v = 0.0;
+  for (long long k = threadIdx.x; k < ncol; k += 256) v += (double)normalised_extra_value(V, raw, kind, block, q * ncol + k);
+  __shared__ double part[4];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double x = (double)(float)((part[0] + part[1] + part[2] + part[3]) / (double)ncol);
+    unsafeAtomicAdd(sum + nFields + q, x);
+    unsafeAtomicAdd(sumSq + nFields + q, x * x);
+  }
+}
+
 // Do the batches of a driver's loop -- nBatches of nPhotons each -- share one grid, group by group (see FusedSlot)?  The specialised
 // kernels -- the common problem class, production streams --, with or (round 4) without radiance directions: a local-estimate ray
 // carries its batch in its info word (photon_kernel).  One long batch alone, or batches of a size at which a launch's tail no longer
@@ -1360,6 +1400,32 @@ int accumulate_moments(i3rc_hip_integrator *h, hipStream_t stream, const double 
                      (const double *)excess.p, nFields, (double *)h->momSum.p, (double *)h->momSq.p);
   hipLaunchKernelGGL(moments_means_kernel, dim3((unsigned)(count * (3 + h->nz + h->nDir))), dim3(256), 0, stream, M, blocks, stride,
                      (const double *)excess.p, (double *)h->momSum.p, (double *)h->momSq.p, (double *)h->momCounters.p);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// makes the handle's diagnostic moment sums ready (zeroed) for a loop of batches; behind begin_moments (the grid's device copies)
+int begin_extra_moments(i3rc_hip_integrator *h) {
+  const size_t bytes = (size_t)extra_moments_layout(h->extra, h->nx, h->ny, h->nz).total * sizeof(double);
+  if (h->momExtraSum.bytes != bytes || !h->momExtraSum.p) { HIPCHK(h, h->momExtraSum.alloc(bytes)); HIPCHK(h, h->momExtraSq.alloc(bytes)); }
+  HIPCHK(h, hipMemset(h->momExtraSum.p, 0, bytes));
+  HIPCHK(h, hipMemset(h->momExtraSq.p, 0, bytes));
+  return 0;
+}
+
+// The extra blocks of `count` raw tally blocks on the device -> normalised, x and x^2 added to the handle's diagnostic moment sums;
+// asynchronous on `stream`, as accumulate_moments (which serves the ordinary moments of the same blocks)
+int accumulate_extra_moments(i3rc_hip_integrator *h, hipStream_t stream, const double *blocks, int count) {
+  TallyView V = current_view(h);
+  V.areaFrac = (const double *)h->momArea.p; V.dz = (const double *)h->momDz.p;
+  const long long block = extra_block_offset(h->layout.counters), nFields = extra_block_words(h->extra, h->nx, h->ny, h->nz);
+  const int nMeans = (int)extra_moments_means(h->extra, h->nz);
+  const long long fieldBlocks = (nFields + 255) / 256;
+  const int slices = (int)std::max<long long>(1, std::min<long long>({(long long)(count + 7) / 8, (2048 + fieldBlocks - 1) / fieldBlocks, 65535}));
+  hipLaunchKernelGGL(moments_extra_fields_kernel, dim3((unsigned)fieldBlocks, (unsigned)slices), dim3(256), 0, stream, V, h->extra, block, blocks, count,
+                     (long long)h->layout.total, nFields, (double *)h->momExtraSum.p, (double *)h->momExtraSq.p);
+  hipLaunchKernelGGL(moments_extra_means_kernel, dim3((unsigned)(count * nMeans)), dim3(256), 0, stream, V, h->extra, block, blocks,
+                     (long long)h->layout.total, nMeans, nFields, (double *)h->momExtraSum.p, (double *)h->momExtraSq.p);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -1575,6 +1641,67 @@ int i3rc_hip_run_batches_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_
   HIPCHK(h, hipMemcpy(sum, h->momSum.p, (size_t)L.total * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpy(sumSquares, h->momSq.p, (size_t)L.total * sizeof(double), hipMemcpyDeviceToHost));
   if (counters) HIPCHK(h, hipMemcpy(counters, h->momCounters.p, I3RC_NUM_COUNTERS * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int i3rc_hip_diagnostic_moments_layout_words(int kind, int nx, int ny, int nz, int64_t *out, int nout) {
+  if (kind < EXTRA_NONE || kind > EXTRA_TRACKS || nx < 1 || ny < 1 || nz < 1 || !out || nout < 7) return 1;
+  const ExtraMomentsLayout L = extra_moments_layout((ExtraTally)kind, nx, ny, nz);
+  const int64_t v[7] = {L.levelFluxUp, L.levelFluxDown, L.meanLevelFluxUp, L.meanLevelFluxDown, L.actinicFlux, L.meanActinicFlux, L.total};
+  for (int k = 0; k < 7; ++k) out[k] = v[k];
+  return 0;
+}
+
+int i3rc_hip_get_diagnostic_moments_layout(const i3rc_hip_integrator *h, i3rc_diagnostic_moments_layout *layout) {
+  if (!h || !layout) return 1;
+  const ExtraMomentsLayout L = extra_moments_layout(h->extra, h->nx, h->ny, h->nz);
+  layout->kind = (int64_t)h->extra;
+  layout->levelFluxUp = L.levelFluxUp; layout->levelFluxDown = L.levelFluxDown; layout->meanLevelFluxUp = L.meanLevelFluxUp;
+  layout->meanLevelFluxDown = L.meanLevelFluxDown; layout->actinicFlux = L.actinicFlux; layout->meanActinicFlux = L.meanActinicFlux;
+  layout->total = L.total;
+  return 0;
+}
+
+// A driver's batch loop with a diagnostic tally switched on, its statistics gathered on the device: see include/i3rc_hip.h
+int i3rc_hip_run_batches_diagnostic_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1, int nBatches, int64_t nPhotons,
+                                            const i3rc_source *src, double *sum, double *sumSquares, double *counters, double *extraSum,
+                                            double *extraSumSquares) {
+  static const char who[] = "i3rc_hip_run_batches_diagnostic_moments";
+  if (!h) return 1;
+  if (!src || !sum || !sumSquares || !extraSum || !extraSumSquares || nBatches < 1) return h->fail(std::string(who) + ": bad arguments");
+  if (h->extra == EXTRA_NONE)
+    return h->fail(std::string(who) + ": no diagnostic tally is switched on (i3rc_hip_set_level_fluxes or i3rc_hip_set_actinic_flux first; "
+                   "i3rc_hip_run_batches_moments serves a loop without one)");
+  if (src->kind != 0) return h->fail(std::string(who) + ": Directional photon streams only (explicit streams differ from batch to batch)");
+  if (nPhotons <= 0) return h->fail(std::string(who) + ": setIllumination: must ask for non-negative number of photons.");
+  if (extra_tally_refused(h, who, false)) return 1;
+  HIPCHK(h, hipSetDevice(h->device));
+  drop_lookahead(h);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (begin_moments(h) || begin_extra_moments(h)) return 1;
+  // one launch per batch (the general flux kernel under the kind's tag, as i3rc_hip_launch_batch runs it), several in flight, each
+  // batch's block normalised and added up on its slot's stream behind its launch -- never a fused group
+  const int K = std::min(nBatches, 6);
+  if (reset_slots_if_layout_changed(h)) return 1;
+  for (int k = 0; k < K; ++k) { if (ready_slot(h, k)) return 1; h->pipe[k].batch = -1; }
+  int rc = 0;
+  for (int b = 0; b < nBatches && !rc; ++b) {
+    auto &sl = h->pipe[b % K];
+    rc = run_batch_in_slot(h, sl, seed0, seed1 + (uint32_t)b, nPhotons, src, true, false, who) ||
+         accumulate_moments(h, sl.stream, (const double *)sl.tally.p, 1, sl.excess) ||
+         accumulate_extra_moments(h, sl.stream, (const double *)sl.tally.p, 1);
+  }
+  for (int k = 0; k < K; ++k)
+    if (h->pipe[k].stream && hipStreamSynchronize(h->pipe[k].stream) != hipSuccess && !rc) rc = h->fail(std::string(who) + ": waiting for the batches failed");
+  if (rc) return 1;
+  i3rc_moments_layout L;
+  moments_layout(h, L);
+  const size_t extraBytes = (size_t)extra_moments_layout(h->extra, h->nx, h->ny, h->nz).total * sizeof(double);
+  HIPCHK(h, hipMemcpy(sum, h->momSum.p, (size_t)L.total * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(sumSquares, h->momSq.p, (size_t)L.total * sizeof(double), hipMemcpyDeviceToHost));
+  if (counters) HIPCHK(h, hipMemcpy(counters, h->momCounters.p, I3RC_NUM_COUNTERS * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(extraSum, h->momExtraSum.p, extraBytes, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(extraSumSquares, h->momExtraSq.p, extraBytes, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1915,8 +2042,8 @@ int i3rc_hip_normalise_level_fluxes(const i3rc_hip_integrator *h, const double *
   const TallyView &V = h->view;
   const size_t ncol = (size_t)h->nx * h->ny;
   for (size_t e = 0; e < (size_t)(h->nz + 1) * ncol; ++e) {   // (level after level, as the block is laid out)
-    if (levelFluxUp) levelFluxUp[e] = normalised_column_flux(V, t, V.levelUp + e, e % ncol);
-    if (levelFluxDown) levelFluxDown[e] = normalised_column_flux(V, t, V.levelDown + e, e % ncol);
+    if (levelFluxUp) levelFluxUp[e] = normalised_extra_value(V, t, EXTRA_LEVELS, V.levelUp, e);
+    if (levelFluxDown) levelFluxDown[e] = normalised_extra_value(V, t, EXTRA_LEVELS, V.levelDown, e);
   }
   return 0;
 }
@@ -1926,8 +2053,7 @@ int i3rc_hip_normalise_actinic_flux(const i3rc_hip_integrator *h, const double *
   if (h->extra != EXTRA_TRACKS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_actinic_flux: the actinic flux is not switched on");
   const TallyView &V = h->view;
   const size_t ncol = (size_t)h->nx * h->ny;
-  for (int kz = 0; kz < h->nz; ++kz)
-    for (size_t k = 0; k < ncol; ++k) actinicFlux[(size_t)kz * ncol + k] = normalised_actinic_flux(V, t, track_block(h), kz, k);
+  for (size_t e = 0; e < (size_t)h->nz * ncol; ++e) actinicFlux[e] = normalised_extra_value(V, t, EXTRA_TRACKS, track_block(h), e);
   return 0;
 }
 

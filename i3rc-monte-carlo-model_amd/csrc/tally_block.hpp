@@ -94,6 +94,42 @@ I3RC_TALLY_FN float normalised_actinic_flux(const TallyView &V, const double *ra
   return (float)(raw[block + kz * ncol + col] / (photons_per_column(V, raw, col) * V.dz[kz]));
 }
 
+// Element e of the kind's extra block (at `block`) as reportResults hands it out: the level fluxes (e counts through levelFluxUp |
+// levelFluxDown, level after level) per photon of the column, the actinic flux also per unit of the layer's depth.  What
+// i3rc_hip_normalise_level_fluxes / _actinic_flux fill their arrays with and what the diagnostic batch moments add up.
+I3RC_TALLY_FN float normalised_extra_value(const TallyView &V, const double *raw, ExtraTally kind, long long block, long long e) {
+  const long long ncol = (long long)V.nx * V.ny;
+  if (kind == EXTRA_TRACKS) {
+    const int kz = (int)(e / ncol);
+    return normalised_actinic_flux(V, raw, block, kz, e - kz * ncol);
+  }
+  return normalised_column_flux(V, raw, block + e, e % ncol);
+}
+
+// THE DIAGNOSTIC BATCH MOMENTS (i3rc_hip_run_batches_diagnostic_moments): where the sums over a loop's batches of the kind's fields and
+// of their domain means -- float32(sum over the columns / number of columns) per level or layer, a plain column mean on every grid --
+// lie in a block of their own, in float64 words.  EXTRA_NONE: total 0.
+struct ExtraMomentsLayout {
+  long long levelFluxUp, levelFluxDown, meanLevelFluxUp, meanLevelFluxDown;   // EXTRA_LEVELS: [nz + 1][ny][nx] twice, then nz + 1 twice
+  long long actinicFlux, meanActinicFlux;                                    // EXTRA_TRACKS: [nz][ny][nx], then nz
+  long long total;                                                           // (what the kind has not: -1)
+};
+I3RC_TALLY_FN ExtraMomentsLayout extra_moments_layout(ExtraTally kind, int nx, int ny, int nz) {
+  const long long ncol = (long long)nx * ny;
+  ExtraMomentsLayout L = {-1, -1, -1, -1, -1, -1, 0};
+  if (kind == EXTRA_LEVELS) {
+    L.levelFluxUp = 0; L.levelFluxDown = (nz + 1) * ncol;
+    L.meanLevelFluxUp = 2 * (nz + 1) * ncol; L.meanLevelFluxDown = L.meanLevelFluxUp + (nz + 1);
+    L.total = L.meanLevelFluxDown + (nz + 1);
+  } else if (kind == EXTRA_TRACKS) {
+    L.actinicFlux = 0; L.meanActinicFlux = ncol * nz;
+    L.total = L.meanActinicFlux + nz;
+  }
+  return L;
+}
+// ... the fields in front of the means (= extra_block_words: the moments' fields lie as the block's elements do), and the means
+I3RC_TALLY_FN long long extra_moments_means(ExtraTally kind, int nz) { return kind == EXTRA_LEVELS ? 2 * (nz + 1) : (kind == EXTRA_TRACKS ? nz : 0); }
+
 // What component j (0: the surface) adds to the column's radiance in direction d beyond its own sum: its share of the excess of
 // limited contributions, in proportion to the field (:327-347).  excessSums[j * nDir + d] = the sum over the columns of component j's
 // field in direction d; the caller forms it (the host sequentially, moments_excess_kernel in a tree).

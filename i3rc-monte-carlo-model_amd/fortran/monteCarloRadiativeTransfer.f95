@@ -73,6 +73,10 @@ module monteCarloRadiativeTransfer
     ! sums and sums of squares over the batches of the last computeRadiativeTransferBatchMoments (i3rc_moments_layout)
     real(c_double), dimension(:), pointer :: momentSums => null(), momentSquares => null()
     integer :: momentBatches = 0
+    ! ... and, of the last computeRadiativeTransferDiagnosticMoments, those of the diagnostic tally that was on
+    ! (i3rc_diagnostic_moments_layout; diagnosticKind: 1 level fluxes, 2 the actinic flux)
+    real(c_double), dimension(:), pointer :: diagnosticSums => null(), diagnosticSquares => null()
+    integer :: diagnosticKind = 0
   end type integrator
 
   public :: integrator
@@ -82,6 +86,8 @@ module monteCarloRadiativeTransfer
   public :: computeRadiativeTransferBatches, selectBatchResults
   ! ... and the same loop with its statistics -- all a driver keeps of its batches -- gathered on the device
   public :: computeRadiativeTransferBatchMoments, reportBatchMoments, sumBatchMomentsAcrossProcesses
+  ! ... also of the level fluxes or the actinic flux, whichever is switched on
+  public :: computeRadiativeTransferDiagnosticMoments, reportDiagnosticMoments
 contains
   ! ------------------------------------------------------------------------------------------------
   ! Creation
@@ -745,6 +751,7 @@ contains
     if(.not. deviceCall(thisIntegrator, i3rc_hip_get_moments_layout(thisIntegrator%device, layout), &
                         "computeRadiativeTransfer", status)) return
     if(associated(thisIntegrator%momentSums)) deallocate(thisIntegrator%momentSums, thisIntegrator%momentSquares)
+    if(associated(thisIntegrator%diagnosticSums)) deallocate(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares)
     allocate(thisIntegrator%momentSums(layout%total), thisIntegrator%momentSquares(layout%total))
     thisIntegrator%momentBatches = 0
     if(.not. deviceCall(thisIntegrator, i3rc_hip_run_batches_moments(thisIntegrator%device, int(iseed, c_int32_t),          &
@@ -765,30 +772,171 @@ contains
   end subroutine computeRadiativeTransferBatchMoments
 
   ! The batch moments of every process's share of a loop, summed over the processes: ONE all-reduce of ONE packed float64
-  ! buffer (sums | sums of squares | number of batches) -- where the reference's drivers call sumAcrossProcesses ten times on real(4)
+  ! buffer (sums | sums of squares | with diagnostic moments: their sums | sums of squares | number of batches) -- where the reference's drivers call sumAcrossProcesses ten times on real(4)
   ! fields (monteCarloDriver.f95:333-352 over Code/multipleProcesses_mpi.f95:57-131).  Afterwards reportBatchMoments reports
   ! the whole loop on every process.  A collective: every process calls it.
   subroutine sumBatchMomentsAcrossProcesses(thisIntegrator, status)
     type(integrator),   intent(inout) :: thisIntegrator
     type(ErrorMessage), intent(inout) :: status
     real(c_double), dimension(:), allocatable :: packed
-    integer :: n
+    integer :: n, m
 
     if(.not. associated(thisIntegrator%momentSums)) then
       call setStateToFailure(status, "sumBatchMomentsAcrossProcesses: no batch moments have been computed.")
       return
     end if
     n = size(thisIntegrator%momentSums)
-    allocate(packed(2 * n + 1))
+    m = 0   ! (the diagnostic moments of computeRadiativeTransferDiagnosticMoments travel in the same buffer, behind the ordinary ones)
+    if(associated(thisIntegrator%diagnosticSums)) m = size(thisIntegrator%diagnosticSums)
+    allocate(packed(2 * n + 2 * m + 1))
     packed(1:n)         = thisIntegrator%momentSums
     packed(n + 1:2 * n) = thisIntegrator%momentSquares
-    packed(2 * n + 1)   = real(thisIntegrator%momentBatches, c_double)
+    if(m > 0) then
+      packed(2 * n + 1:2 * n + m)         = thisIntegrator%diagnosticSums
+      packed(2 * n + m + 1:2 * n + 2 * m) = thisIntegrator%diagnosticSquares
+    end if
+    packed(2 * n + 2 * m + 1) = real(thisIntegrator%momentBatches, c_double)
     packed = sumAcrossProcesses(packed)
     thisIntegrator%momentSums    = packed(1:n)
     thisIntegrator%momentSquares = packed(n + 1:2 * n)
-    thisIntegrator%momentBatches = nint(packed(2 * n + 1))
+    if(m > 0) then
+      thisIntegrator%diagnosticSums    = packed(2 * n + 1:2 * n + m)
+      thisIntegrator%diagnosticSquares = packed(2 * n + m + 1:2 * n + 2 * m)
+    end if
+    thisIntegrator%momentBatches = nint(packed(2 * n + 2 * m + 1))
     deallocate(packed)
   end subroutine sumBatchMomentsAcrossProcesses
+
+  ! ------------------------------------------------------------------------------------------------
+  ! Not in the reference: computeRadiativeTransferBatchMoments for a loop WITH A DIAGNOSTIC TALLY switched on
+  !   (specifyParameters: computeLevelFluxes or computeActinicFlux; i3rc_hip_run_batches_diagnostic_moments).  Every batch is one
+  !   launch of its own -- the photons computeRadiativeTransfer traces for seed (/ iseed, batch /) with the diagnostic on --, and
+  !   the level fluxes (or the actinic flux) of every batch are normalised and added up on the device beside everything else.
+  !   reportBatchMoments serves the ordinary moments of such a loop as ever, reportDiagnosticMoments the diagnostic ones: the
+  !   fields in reportResults' shapes, and per level (layer) the mean over the columns -- last dimension 1 = sum of x, 2 = sum of
+  !   x**2 over the batches.  The track-length estimator's variance diverges in cells without extinction: the actinic flux's
+  !   standard errors are not to be trusted there.
+  ! ------------------------------------------------------------------------------------------------
+  subroutine computeRadiativeTransferDiagnosticMoments(thisIntegrator, iseed, firstBatch, numBatches, solarMu, solarAzimuth, &
+                                                       numberOfPhotons, status)
+    type(integrator),   intent(inout) :: thisIntegrator
+    integer,            intent(in   ) :: iseed, firstBatch, numBatches, numberOfPhotons
+    real,               intent(in   ) :: solarMu, solarAzimuth
+    type(ErrorMessage), intent(inout) :: status
+    type(i3rc_source)                    :: source
+    type(i3rc_moments_layout)            :: layout
+    type(i3rc_diagnostic_moments_layout) :: extra
+    real(c_double)                       :: counters(I3RC_NUM_COUNTERS)
+
+    if(.not. isReady_Integrator(thisIntegrator)) then
+      call setStateToFailure(status, "computeRadiativeTransfer: problem not completely specified.")
+      return
+    end if
+    if(numBatches < 1 .or. numberOfPhotons < 1) then
+      call setStateToFailure(status, "computeRadiativeTransfer: Didn't process any photons.")
+      return
+    end if
+    call ensureTables(thisIntegrator, status)
+    if(stateIsFailure(status)) return
+    source%kind = 0; source%solarMu = solarMu; source%solarAzimuth = solarAzimuth
+    if(.not. deviceCall(thisIntegrator, i3rc_hip_get_moments_layout(thisIntegrator%device, layout), &
+                        "computeRadiativeTransfer", status)) return
+    if(.not. deviceCall(thisIntegrator, i3rc_hip_get_diagnostic_moments_layout(thisIntegrator%device, extra), &
+                        "computeRadiativeTransfer", status)) return
+    if(associated(thisIntegrator%momentSums)) deallocate(thisIntegrator%momentSums, thisIntegrator%momentSquares)
+    if(associated(thisIntegrator%diagnosticSums)) deallocate(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares)
+    ! (without a diagnostic the library refuses below: one word each, so that the call has arrays to be given)
+    allocate(thisIntegrator%momentSums(layout%total), thisIntegrator%momentSquares(layout%total), &
+             thisIntegrator%diagnosticSums(max(extra%total, 1_c_int64_t)), thisIntegrator%diagnosticSquares(max(extra%total, 1_c_int64_t)))
+    thisIntegrator%momentBatches = 0; thisIntegrator%diagnosticKind = 0
+    if(.not. deviceCall(thisIntegrator, i3rc_hip_run_batches_diagnostic_moments(thisIntegrator%device, int(iseed, c_int32_t), &
+                        int(firstBatch, c_int32_t), int(numBatches, c_int), int(numberOfPhotons, c_int64_t), source,         &
+                        thisIntegrator%momentSums, thisIntegrator%momentSquares, counters,                                   &
+                        thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares), "computeRadiativeTransfer", status)) then
+      deallocate(thisIntegrator%momentSums, thisIntegrator%momentSquares, thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares)
+      return
+    end if
+    thisIntegrator%momentBatches    = numBatches
+    thisIntegrator%diagnosticKind   = int(extra%kind)
+    thisIntegrator%resultsValid     = .false.      ! (no single batch is current after this call: reportResults says so)
+    thisIntegrator%photonsProcessed = counters(1 + I3RC_CNT_PHOTONS)
+    thisIntegrator%photonsDropped   = counters(1 + I3RC_CNT_DROPPED)
+    if(thisIntegrator%photonsProcessed > 0.d0) then
+      call setStateToCompleteSuccess(status, "computeRadiativeTransfer: finished with photons")
+    else
+      call setStateToFailure(status, "computeRadiativeTransfer: Didn't process any photons.")
+    end if
+  end subroutine computeRadiativeTransferDiagnosticMoments
+
+  subroutine reportDiagnosticMoments(thisIntegrator, levelFluxUpStats, levelFluxDownStats, meanLevelFluxUpStats, &
+                                     meanLevelFluxDownStats, actinicFluxStats, meanActinicFluxStats, status)
+    type(integrator),                      intent(in   ) :: thisIntegrator
+    real, dimension(:, :, :, :), optional, intent(  out) :: levelFluxUpStats, levelFluxDownStats           ! (nx, ny, nz + 1, 2)
+    real, dimension(:, :),       optional, intent(  out) :: meanLevelFluxUpStats, meanLevelFluxDownStats   ! (nz + 1, 2)
+    real, dimension(:, :, :, :), optional, intent(  out) :: actinicFluxStats                               ! (nx, ny, nz, 2)
+    real, dimension(:, :),       optional, intent(  out) :: meanActinicFluxStats                           ! (nz, 2)
+    type(ErrorMessage),                    intent(inout) :: status
+    type(i3rc_diagnostic_moments_layout) :: layout
+    integer :: nx, ny, nz
+
+    if(.not. associated(thisIntegrator%diagnosticSums)) then
+      call setStateToFailure(status, "reportDiagnosticMoments: no diagnostic moments have been computed.")
+      return
+    end if
+    if(.not. deviceCall(thisIntegrator, i3rc_hip_get_diagnostic_moments_layout(thisIntegrator%device, layout), &
+                        "reportDiagnosticMoments", status)) return
+    if(layout%kind /= thisIntegrator%diagnosticKind .or. layout%total /= size(thisIntegrator%diagnosticSums)) then
+      call setStateToFailure(status, "reportDiagnosticMoments: the problem has changed since the moments were computed.")
+      return
+    end if
+    nx = size(thisIntegrator%fluxUp, 1); ny = size(thisIntegrator%fluxUp, 2); nz = size(thisIntegrator%volumeAbsorption, 3)
+    if(present(levelFluxUpStats))       call fieldMoments(layout%levelFluxUp,       nz + 1, levelFluxUpStats,   "levelFluxUpStats",   "level flux")
+    if(present(levelFluxDownStats))     call fieldMoments(layout%levelFluxDown,     nz + 1, levelFluxDownStats, "levelFluxDownStats", "level flux")
+    if(present(meanLevelFluxUpStats))   call meanMoments(layout%meanLevelFluxUp,    nz + 1, meanLevelFluxUpStats,   "meanLevelFluxUpStats",   "level flux")
+    if(present(meanLevelFluxDownStats)) call meanMoments(layout%meanLevelFluxDown,  nz + 1, meanLevelFluxDownStats, "meanLevelFluxDownStats", "level flux")
+    if(present(actinicFluxStats))       call fieldMoments(layout%actinicFlux,       nz,     actinicFluxStats,     "actinicFluxStats",     "actinic flux")
+    if(present(meanActinicFluxStats))   call meanMoments(layout%meanActinicFlux,    nz,     meanActinicFluxStats, "meanActinicFluxStats", "actinic flux")
+    if(.not. stateIsFailure(status)) call setStateToSuccess(status)
+  contains
+    ! (a kind that is not the loop's: its offset is -1)
+    subroutine fieldMoments(at, n, to, name, what)
+      integer(c_int64_t),          intent(in ) :: at
+      integer,                     intent(in ) :: n
+      real, dimension(:, :, :, :), intent(out) :: to
+      character(len = *),          intent(in ) :: name, what
+      integer :: i, j, k
+      integer(c_int64_t) :: e
+      if(at < 0) then
+        call setStateToFailure(status, "reportDiagnosticMoments: " // what // " information not available")
+      else if(any(shape(to) /= (/ nx, ny, n, 2 /))) then
+        call setStateToFailure(status, "reportDiagnosticMoments: " // name // " array is the wrong size")
+      else
+        do k = 1, n
+          do j = 1, ny
+            do i = 1, nx
+              e = at + i + nx * ((j - 1) + ny * (k - 1))
+              to(i, j, k, 1) = real(thisIntegrator%diagnosticSums(e))
+              to(i, j, k, 2) = real(thisIntegrator%diagnosticSquares(e))
+            end do
+          end do
+        end do
+      end if
+    end subroutine fieldMoments
+    subroutine meanMoments(at, n, to, name, what)
+      integer(c_int64_t),    intent(in ) :: at
+      integer,               intent(in ) :: n
+      real, dimension(:, :), intent(out) :: to
+      character(len = *),    intent(in ) :: name, what
+      if(at < 0) then
+        call setStateToFailure(status, "reportDiagnosticMoments: " // what // " information not available")
+      else if(any(shape(to) /= (/ n, 2 /))) then
+        call setStateToFailure(status, "reportDiagnosticMoments: " // name // " array is the wrong size")
+      else
+        to(:, 1) = real(thisIntegrator%diagnosticSums   (at + 1:at + n))
+        to(:, 2) = real(thisIntegrator%diagnosticSquares(at + 1:at + n))
+      end if
+    end subroutine meanMoments
+  end subroutine reportDiagnosticMoments
 
   subroutine reportBatchMoments(thisIntegrator, numBatches, meanFluxUpStats, meanFluxDownStats, meanFluxAbsorbedStats,      &
                                 fluxUpStats, fluxDownStats, fluxAbsorbedStats, absorbedProfileStats, volumeAbsorptionStats, &
@@ -1109,6 +1257,7 @@ contains
     if(associated(thisIntegrator%intensityByComponent)) deallocate(thisIntegrator%intensityByComponent)
     if(associated(thisIntegrator%batchTallies))         deallocate(thisIntegrator%batchTallies)
     if(associated(thisIntegrator%momentSums))           deallocate(thisIntegrator%momentSums, thisIntegrator%momentSquares)
+    if(associated(thisIntegrator%diagnosticSums))       deallocate(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares)
     if(associated(thisIntegrator%levelFluxUp))          deallocate(thisIntegrator%levelFluxUp, thisIntegrator%levelFluxDown)
     if(associated(thisIntegrator%actinicFlux))          deallocate(thisIntegrator%actinicFlux)
     thisIntegrator%computeLevelFluxes = .false.; thisIntegrator%computeActinicFlux = .false.

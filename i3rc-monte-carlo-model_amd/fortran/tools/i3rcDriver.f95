@@ -6,6 +6,10 @@
 ! moments over batches (:358-378, including its scaling by solarFlux), and the ASCII result files (:484-604; same
 ! header keys and line formats, which downstream scripts parse).  The unchanged reference driver also links against
 ! the shell (make linkcheck); this one exists so that a tree without the reference can run end to end.
+! Beyond the reference: computeLevelFluxes / computeActinicFlux in /algorithms/ switch one of the shell's diagnostic tallies on -- the
+! upward and downward flux through every layer interface, or every cell's actinic flux by photon track length -- and the run reports
+! it with the standard error over the batches like everything else: the domain means per level (layer) in outputLevelFluxFile /
+! outputActinicFluxFile of /fileNames/, the fields in the netCDF file.  Both off (the default): the driver's files are what they were.
 !   i3rcDriver namelistFile
 program i3rcDriver
   use ErrorMessages,               only: ErrorMessage, stateIsFailure
@@ -17,7 +21,8 @@ program i3rcDriver
   use monteCarloRadiativeTransfer, only: integrator, new_Integrator, specifyParameters, isReady_Integrator, &
                                          finalize_Integrator, computeRadiativeTransfer, reportResults,           &
                                          computeRadiativeTransferBatches, selectBatchResults, &
-                                         computeRadiativeTransferBatchMoments, reportBatchMoments, sumBatchMomentsAcrossProcesses
+                                         computeRadiativeTransferBatchMoments, reportBatchMoments, sumBatchMomentsAcrossProcesses, &
+                                         computeRadiativeTransferDiagnosticMoments, reportDiagnosticMoments
   use UserInterface,               only: printStatus, getOneArgument
   implicit none
 
@@ -35,15 +40,17 @@ program i3rcDriver
   logical :: limitIntensityContributions = .false.
   real    :: maxIntensityContribution = 77.
   logical :: reportVolumeAbsorption = .false., reportAbsorptionProfile = .false.
+  logical :: computeLevelFluxes = .false., computeActinicFlux = .false.   ! (not in the reference: the shell's diagnostic tallies)
   character(len = 256) :: domainFileName = "", outputFluxFile = "", outputRadFile = "", outputAbsProfFile = "", &
-                          outputAbsVolumeFile = "", outputNetcdfFile = ""
+                          outputAbsVolumeFile = "", outputNetcdfFile = "", outputLevelFluxFile = "", outputActinicFluxFile = ""
   namelist /radiativeTransfer/ solarFlux, solarMu, solarAzimuth, surfaceAlbedo, intensityMus, intensityPhis
   namelist /monteCarlo/ numPhotonsPerBatch, numBatches, iseed, nPhaseIntervals
   namelist /algorithms/ useRayTracing, useRussianRoulette, useHybridPhaseFunsForIntenCalcs, hybridPhaseFunWidth, &
                         numOrdersOrigPhaseFunIntenCalcs, useRussianRouletteForIntensity, zetaMin,               &
-                        limitIntensityContributions, maxIntensityContribution
+                        limitIntensityContributions, maxIntensityContribution, computeLevelFluxes, computeActinicFlux
   namelist /output/ reportVolumeAbsorption, reportAbsorptionProfile
-  namelist /fileNames/ domainFileName, outputRadFile, outputFluxFile, outputAbsProfFile, outputAbsVolumeFile, outputNetcdfFile
+  namelist /fileNames/ domainFileName, outputRadFile, outputFluxFile, outputAbsProfFile, outputAbsVolumeFile, outputNetcdfFile, &
+                       outputLevelFluxFile, outputActinicFluxFile
 
   character(len = 256) :: namelistFile
   integer :: nx, ny, nz, nDir, numProcs, thisProc, perProc, batch, firstBatch
@@ -58,6 +65,9 @@ program i3rcDriver
   ! first and second moments over batches, one slab per quantity
   real, allocatable :: mUp(:, :, :), mDown(:, :, :), mAbs(:, :, :), mProfile(:, :), mVolume(:, :, :, :), mRad(:, :, :, :)
   real :: meanUp, meanDown, meanAbs, mMeans(3, 2)
+  ! ... of the diagnostic tally that is switched on: the fields, and the domain means per level (layer)
+  real, allocatable :: mLevelUp(:, :, :, :), mLevelDown(:, :, :, :), mMeanLevelUp(:, :), mMeanLevelDown(:, :), &
+                       mActinic(:, :, :, :), mMeanActinic(:, :)
   type(domain)               :: cloud
   type(ErrorMessage)         :: status
   type(randomNumberSequence) :: randoms
@@ -77,6 +87,8 @@ program i3rcDriver
   nDir = count(abs(intensityMus) > 0.)
   wantRadiance = nDir > 0 .and. (len_trim(outputRadFile) > 0 .or. len_trim(outputNetcdfFile) > 0)
   if(.not. wantRadiance) outputRadFile = ""
+  if(.not. computeLevelFluxes) outputLevelFluxFile = ""
+  if(.not. computeActinicFlux) outputActinicFluxFile = ""
 
   ! -- problem set-up
   call read_Domain(domainFileName, cloud, status);                                call printStatus(status)
@@ -101,6 +113,13 @@ program i3rcDriver
   end if
   call specifyParameters(mc, useRayTracing = useRayTracing, useRussianRoulette = useRussianRoulette, status = status)
   call printStatus(status)
+  ! (one diagnostic at a time, flux runs with ray tracing only: the library says so -- here for the second switch, else at the first launch)
+  if(computeLevelFluxes) then
+    call specifyParameters(mc, computeLevelFluxes = .true., status = status);     call printStatus(status)
+  end if
+  if(computeActinicFlux) then
+    call specifyParameters(mc, computeActinicFlux = .true., status = status);     call printStatus(status)
+  end if
   if(.not. isReady_Integrator(mc)) stop "Integrator is not ready."
 
   allocate(up(nx, ny), down(nx, ny), absorbed(nx, ny), profile(nz), volume(nx, ny, nz))
@@ -143,8 +162,13 @@ program i3rcDriver
   deviceMoments = 1
   call get_environment_variable("I3RC_DRIVER_MOMENTS", envText, status = rc)
   if(rc == 0 .and. len_trim(envText) > 0) read(envText, *, iostat = rc) deviceMoments
-  if(deviceMoments /= 0 .and. inFlight /= 1) then
-    call computeRadiativeTransferBatchMoments(mc, iseed, firstBatch, perProc, solarMu, solarAzimuth, numPhotonsPerBatch, status)
+  if(computeLevelFluxes .or. computeActinicFlux .or. (deviceMoments /= 0 .and. inFlight /= 1)) then
+    if(computeLevelFluxes .or. computeActinicFlux) then
+      ! (a diagnostic's statistics are gathered on the device or not at all: one launch per batch, the batches overlapping)
+      call computeRadiativeTransferDiagnosticMoments(mc, iseed, firstBatch, perProc, solarMu, solarAzimuth, numPhotonsPerBatch, status)
+    else
+      call computeRadiativeTransferBatchMoments(mc, iseed, firstBatch, perProc, solarMu, solarAzimuth, numPhotonsPerBatch, status)
+    end if
     call printStatus(status)
     ! the processes' shares of the loop: ONE all-reduce of the packed float64 moments (where the reference's driver reduces ten
     ! real(4) fields one by one, :333-352) -- what reportBatchMoments hands out below is the whole loop's, on every process
@@ -157,6 +181,17 @@ program i3rcDriver
     call printStatus(status)
     if(wantRadiance) then
       call reportBatchMoments(mc, intensityStats = mRad, status = status)
+      call printStatus(status)
+    end if
+    if(computeLevelFluxes) then
+      allocate(mLevelUp(nx, ny, nz + 1, 2), mLevelDown(nx, ny, nz + 1, 2), mMeanLevelUp(nz + 1, 2), mMeanLevelDown(nz + 1, 2))
+      call reportDiagnosticMoments(mc, levelFluxUpStats = mLevelUp, levelFluxDownStats = mLevelDown, &
+                                   meanLevelFluxUpStats = mMeanLevelUp, meanLevelFluxDownStats = mMeanLevelDown, status = status)
+      call printStatus(status)
+    end if
+    if(computeActinicFlux) then
+      allocate(mActinic(nx, ny, nz, 2), mMeanActinic(nz, 2))
+      call reportDiagnosticMoments(mc, actinicFluxStats = mActinic, meanActinicFluxStats = mMeanActinic, status = status)
       call printStatus(status)
     end if
     perProc = 0   ! (the loop below has nothing left to do)
@@ -210,7 +245,17 @@ program i3rcDriver
     mRad(:, :, :, 2) = sqrt(max(0., mRad(:, :, :, 2) - mRad(:, :, :, 1)**2) / (numBatches - 1))
   end if
 
+  if(computeLevelFluxes) then
+    call reduce2(mMeanLevelUp); call reduce2(mMeanLevelDown); call reduce4(mLevelUp); call reduce4(mLevelDown)
+  end if
+  if(computeActinicFlux) then
+    call reduce2(mMeanActinic); call reduce4(mActinic)
+  end if
+
   if(MasterProc) then
+    if(len_trim(outputLevelFluxFile) > 0) call writeLevelFluxFile
+    if(len_trim(outputActinicFluxFile) > 0) call writeActinicFluxFile
+    if(len_trim(outputLevelFluxFile) + len_trim(outputActinicFluxFile) > 0) print *, "Wrote ASCII profiles of the diagnostic tally"
     if(len_trim(outputFluxFile) > 0)    call writeFluxFile
     if(len_trim(outputAbsProfFile) > 0) call writeProfileFile
     if(len_trim(outputAbsVolumeFile) > 0) call writeVolumeFile
@@ -241,6 +286,18 @@ contains
     m = solarFlux * m / numBatches
     m(:, :, 2) = sqrt(max(0., m(:, :, 2) - m(:, :, 1)**2) / (numBatches - 1))
   end subroutine reduce3
+
+  subroutine reduce2(m)
+    real, intent(inout) :: m(:, :)
+    m = solarFlux * m / numBatches
+    m(:, 2) = sqrt(max(0., m(:, 2) - m(:, 1)**2) / (numBatches - 1))
+  end subroutine reduce2
+
+  subroutine reduce4(m)
+    real, intent(inout) :: m(:, :, :, :)
+    m = solarFlux * m / numBatches
+    m(:, :, :, 2) = sqrt(max(0., m(:, :, :, 2) - m(:, :, :, 1)**2) / (numBatches - 1))
+  end subroutine reduce4
 
   subroutine writeHeader(unit, title, outputType)
     integer,            intent(in) :: unit
@@ -291,6 +348,33 @@ contains
     close(12)
   end subroutine writeProfileFile
 
+  ! domain means of the flux through every layer interface, the surface first
+  subroutine writeLevelFluxFile
+    integer :: k
+    open(unit = 12, file = trim(outputLevelFluxFile), status = "unknown")
+    call writeHeader(12, "Level Flux Profile", "Level Flux Profile")
+    write(12, '(A)') '!   Z          Flux_Up             Flux_Down '
+    write(12, '(A)') '!          Mean     StdErr       Mean     StdErr '
+    do k = 1, nz + 1
+      write(12, '(F7.3,2(1X,2(1X,F9.4)))') zEdges(k), mMeanLevelUp(k, :), mMeanLevelDown(k, :)
+    end do
+    close(12)
+  end subroutine writeLevelFluxFile
+
+  ! domain means of the actinic flux of every layer, in units of the incident flux on a horizontal surface times solarFlux
+  subroutine writeActinicFluxFile
+    integer :: k
+    open(unit = 12, file = trim(outputActinicFluxFile), status = "unknown")
+    call writeHeader(12, "Actinic Flux Profile", "Actinic Flux Profile")
+    write(12, '(A)') '!  StdErr is not to be trusted in cells without extinction: the track-length variance diverges there'
+    write(12, '(A)') '!   Z      Actinic_Flux '
+    write(12, '(A)') '!          Mean     StdErr '
+    do k = 1, nz
+      write(12, '(F7.3,1X,2(1X,F9.4))') 0.5 * (zEdges(k) + zEdges(k + 1)), mMeanActinic(k, :)
+    end do
+    close(12)
+  end subroutine writeActinicFluxFile
+
   subroutine writeVolumeFile
     integer :: i, j, k
     open(unit = 12, file = trim(outputAbsVolumeFile), status = "unknown")
@@ -329,10 +413,10 @@ contains
   ! names as the reference driver's writeResults_netcdf (:609-854), so that scripts reading its files read these.
   subroutine writeNetcdfFile
     use netcdf
-    integer :: xDim, yDim, zDim, dirDim
+    integer :: xDim, yDim, zDim, dirDim, levelDim
     logical :: wantZ
 
-    wantZ = reportAbsorptionProfile .or. reportVolumeAbsorption
+    wantZ = reportAbsorptionProfile .or. reportVolumeAbsorption .or. computeActinicFlux
     rc = nf90_create(trim(outputNetcdfFile), nf90_clobber, nc)
     if(rc /= nf90_NoErr) then
       print *, "Cannot create " // trim(outputNetcdfFile)
@@ -376,6 +460,17 @@ contains
       rc = nf90_def_var(nc, "intensityPhis", nf90_float, dirDim, v)
       call definePair("intensity", (/ xDim, yDim, dirDim /))
     end if
+    if(computeLevelFluxes) then
+      rc = nf90_def_dim(nc, "zLevel", nz + 1, levelDim)
+      rc = nf90_def_var(nc, "zLevel", nf90_float, levelDim, v)
+      call definePair("levelFluxUp", (/ xDim, yDim, levelDim /))
+      call definePair("levelFluxDown", (/ xDim, yDim, levelDim /))
+    end if
+    if(computeActinicFlux) then
+      call definePair("actinicFlux", (/ xDim, yDim, zDim /))
+      ! (the track-length estimator's variance diverges in cells without extinction)
+      rc = nf90_put_att(nc, v, "note", "not to be trusted in cells without extinction")
+    end if
     rc = nf90_enddef(nc)
     if(rc /= nf90_NoErr) print *, "netCDF output: definitions failed ", rc
 
@@ -394,6 +489,14 @@ contains
     if(wantRadiance) then
       call put1("intensityMus", intensityMus(:nDir)); call put1("intensityPhis", intensityPhis(:nDir))
       call put3("intensity", mRad(:, :, :, 1));       call put3("intensity_StdErr", mRad(:, :, :, 2))
+    end if
+    if(computeLevelFluxes) then
+      call put1("zLevel", zEdges)
+      call put3("levelFluxUp", mLevelUp(:, :, :, 1));     call put3("levelFluxUp_StdErr", mLevelUp(:, :, :, 2))
+      call put3("levelFluxDown", mLevelDown(:, :, :, 1)); call put3("levelFluxDown_StdErr", mLevelDown(:, :, :, 2))
+    end if
+    if(computeActinicFlux) then
+      call put3("actinicFlux", mActinic(:, :, :, 1));     call put3("actinicFlux_StdErr", mActinic(:, :, :, 2))
     end if
     rc = nf90_close(nc)
     if(rc /= nf90_NoErr) print *, "netCDF output: close failed ", rc

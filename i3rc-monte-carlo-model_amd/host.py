@@ -483,19 +483,55 @@ class Integrator:
         s.kind, s.solarMu, s.solarAzimuth = 0, solarMu, solarAzimuth
         self._check(self._lib.i3rc_hip_run_batches_moments(self._h, int(seed[0]), int(seed[1]), int(numBatches), int(numberOfPhotons), C.byref(s),
                                                            s1.ctypes.data_as(B.dp), s2.ctypes.data_as(B.dp), cnt.ctypes.data_as(B.dp)), "computeRadiativeTransfer")
-        nd, ncol = len(self.intensityDirections), self.nx * self.ny
+        return self._unpack_moments(lay, s1), self._unpack_moments(lay, s2), {k: float(cnt[i]) for i, k in enumerate(B.COUNTER_NAMES)}
 
-        def unpack(m):
-            out = dict(fluxUp=m[lay.fluxUp:lay.fluxUp + ncol].reshape(self.ny, self.nx), fluxDown=m[lay.fluxDown:lay.fluxDown + ncol].reshape(self.ny, self.nx),
-                       fluxAbsorbed=m[lay.fluxAbsorbed:lay.fluxAbsorbed + ncol].reshape(self.ny, self.nx),
-                       volumeAbsorption=m[lay.volumeAbsorption:lay.volumeAbsorption + ncol * self.nz].reshape(self.nz, self.ny, self.nx),
-                       absorbedProfile=m[lay.absorbedProfile:lay.absorbedProfile + self.nz], meanFluxUp=m[lay.meanFluxUp],
-                       meanFluxDown=m[lay.meanFluxDown], meanFluxAbsorbed=m[lay.meanFluxAbsorbed])
-            if nd:
-                out["intensity"] = m[lay.intensity:lay.intensity + nd * ncol].reshape(nd, self.ny, self.nx)
-                out["meanIntensity"] = m[lay.meanIntensity:lay.meanIntensity + nd]
+    def _unpack_moments(self, lay, m):
+        """a block of batch moments (B.MomentsLayout) as a dict of arrays in reportResults' shapes"""
+        nd, ncol = len(self.intensityDirections), self.nx * self.ny
+        out = dict(fluxUp=m[lay.fluxUp:lay.fluxUp + ncol].reshape(self.ny, self.nx), fluxDown=m[lay.fluxDown:lay.fluxDown + ncol].reshape(self.ny, self.nx),
+                   fluxAbsorbed=m[lay.fluxAbsorbed:lay.fluxAbsorbed + ncol].reshape(self.ny, self.nx),
+                   volumeAbsorption=m[lay.volumeAbsorption:lay.volumeAbsorption + ncol * self.nz].reshape(self.nz, self.ny, self.nx),
+                   absorbedProfile=m[lay.absorbedProfile:lay.absorbedProfile + self.nz], meanFluxUp=m[lay.meanFluxUp],
+                   meanFluxDown=m[lay.meanFluxDown], meanFluxAbsorbed=m[lay.meanFluxAbsorbed])
+        if nd:
+            out["intensity"] = m[lay.intensity:lay.intensity + nd * ncol].reshape(nd, self.ny, self.nx)
+            out["meanIntensity"] = m[lay.meanIntensity:lay.meanIntensity + nd]
+        return out
+
+    def computeRadiativeTransferDiagnosticMoments(self, seed, numBatches, solarMu, solarAzimuth, numberOfPhotons):
+        """computeRadiativeTransferBatchMoments for a loop with a diagnostic tally switched on (specifyParameters: computeLevelFluxes or
+        computeActinicFlux; i3rc_hip_run_batches_diagnostic_moments): batch k is what computeRadiativeTransfer(new_RandomNumberSequence(
+        (seed[0], seed[1] + k)), ...) traces with the diagnostic on.  The two dicts also hold the sums of levelFluxUp, levelFluxDown
+        (nz + 1, ny, nx), meanLevelFluxUp, meanLevelFluxDown (nz + 1) -- or of actinicFlux (nz, ny, nx) and meanActinicFlux (nz): the
+        mean over the columns of every level or layer, per batch.  In cells without extinction the actinic flux's variance diverges
+        (INTEGRATION.md): its standard errors are not to be trusted there."""
+        if not self.isReady_Integrator():
+            raise I3RCError("computeRadiativeTransfer: problem not completely specified.")
+        self._ensure_tables()
+        lay, xlay = B.MomentsLayout(), B.DiagnosticMomentsLayout()
+        self._check(self._lib.i3rc_hip_get_moments_layout(self._h, C.byref(lay)), "computeRadiativeTransfer")
+        self._check(self._lib.i3rc_hip_get_diagnostic_moments_layout(self._h, C.byref(xlay)), "computeRadiativeTransfer")
+        s1, s2, cnt = np.zeros(lay.total, np.float64), np.zeros(lay.total, np.float64), np.zeros(B.NUM_COUNTERS, np.float64)
+        x1, x2 = np.zeros(max(xlay.total, 1), np.float64), np.zeros(max(xlay.total, 1), np.float64)
+        s = B.Source()
+        s.kind, s.solarMu, s.solarAzimuth = 0, solarMu, solarAzimuth
+        self._check(self._lib.i3rc_hip_run_batches_diagnostic_moments(
+            self._h, int(seed[0]), int(seed[1]), int(numBatches), int(numberOfPhotons), C.byref(s), s1.ctypes.data_as(B.dp),
+            s2.ctypes.data_as(B.dp), cnt.ctypes.data_as(B.dp), x1.ctypes.data_as(B.dp), x2.ctypes.data_as(B.dp)), "computeRadiativeTransfer")
+        ncol = self.nx * self.ny
+
+        def unpack(m, x):
+            out = self._unpack_moments(lay, m)
+            if xlay.kind == B.EXTRA_KINDS["levels"]:
+                for k in ("levelFluxUp", "levelFluxDown"):
+                    out[k] = x[getattr(xlay, k):getattr(xlay, k) + (self.nz + 1) * ncol].reshape(self.nz + 1, self.ny, self.nx)
+                for k in ("meanLevelFluxUp", "meanLevelFluxDown"):
+                    out[k] = x[getattr(xlay, k):getattr(xlay, k) + self.nz + 1]
+            else:
+                out["actinicFlux"] = x[xlay.actinicFlux:xlay.actinicFlux + self.nz * ncol].reshape(self.nz, self.ny, self.nx)
+                out["meanActinicFlux"] = x[xlay.meanActinicFlux:xlay.meanActinicFlux + self.nz]
             return out
-        return unpack(s1), unpack(s2), {k: float(cnt[i]) for i, k in enumerate(B.COUNTER_NAMES)}
+        return unpack(s1, x1), unpack(s2, x2), {k: float(cnt[i]) for i, k in enumerate(B.COUNTER_NAMES)}
 
     def set_batch_fusion(self, mode):
         """-1: automatic (default), 0: every batch a launch of its own, 1: fuse a loop's batches into one grid whenever the

@@ -266,6 +266,38 @@ int i3rc_hip_get_moments_layout(const i3rc_hip_integrator *h, i3rc_moments_layou
 int i3rc_hip_run_batches_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1, int nBatches, int64_t nPhotons,
                                  const i3rc_source *src, double *sum, double *sumSquares, double *counters);
 
+/* Layout (in float64 elements) of a block of DIAGNOSTIC batch moments (i3rc_hip_run_batches_diagnostic_moments): the fields of the
+ * optional diagnostic tally that is switched on, in reportResults' shapes, and their domain means -- per level (layer) the plain mean
+ * over the columns, rounded to real(4) per batch as meanFluxUp is, also on irregular grids; so meanLevelFluxUp[nz] is the quantity
+ * meanFluxUp is, and meanLevelFluxDown[0] the one meanFluxDown is.  kind: 0 none (total 0), 1 level fluxes, 2 the actinic flux; the
+ * offsets of what the kind has not are -1. */
+typedef struct i3rc_diagnostic_moments_layout {
+  int64_t kind;
+  int64_t levelFluxUp, levelFluxDown;                    /* (nz+1)*nx*ny each ([nz+1][ny][nx])          */
+  int64_t meanLevelFluxUp, meanLevelFluxDown;            /* nz+1 each                                   */
+  int64_t actinicFlux;                                   /* nx*ny*nz ([nz][ny][nx])                     */
+  int64_t meanActinicFlux;                               /* nz                                          */
+  int64_t total;
+} i3rc_diagnostic_moments_layout;
+int i3rc_hip_get_diagnostic_moments_layout(const i3rc_hip_integrator *h, i3rc_diagnostic_moments_layout *layout);
+/* ... and as host code of its own (no device needed), for a kind and a grid: out[0..6] = levelFluxUp, levelFluxDown, meanLevelFluxUp,
+ * meanLevelFluxDown, actinicFlux, meanActinicFlux, total.  Returns 0; 1 on a kind out of range, a size below 1, a null out or
+ * nout < 7. */
+int i3rc_hip_diagnostic_moments_layout_words(int kind, int nx, int ny, int nz, int64_t *out, int nout);
+
+/* A driver's batch loop WITH A DIAGNOSTIC TALLY SWITCHED ON (i3rc_hip_set_level_fluxes or i3rc_hip_set_actinic_flux), its statistics
+ * gathered on the device.  Batch k = 0 .. nBatches-1 is exactly what i3rc_hip_launch_batch(seed0, seed1 + k, 0, nPhotons) traces while
+ * the diagnostic is on -- the general flux kernel under the kind's tag, cut into launches as ever --, always one launch per batch with
+ * up to 6 batches in flight, never a fused group.  Every batch's block is normalised on the device: sum / sumSquares / counters are
+ * filled as i3rc_hip_run_batches_moments fills them (i3rc_moments_layout), extraSum / extraSumSquares (i3rc_diagnostic_moments_layout)
+ * with x and x*x of the kind's fields as i3rc_hip_normalise_level_fluxes / _actinic_flux give them, and of their domain means, from the
+ * same photons.  Nothing of a batch is copied to the host.  Refused: no diagnostic switched on; radiance directions or max
+ * cross-section (as i3rc_hip_launch_batch refuses them); sources other than Directional.  The track-length estimator's variance
+ * diverges in cells without extinction: the actinic flux's second moments are not to be trusted there.  Synchronous. */
+int i3rc_hip_run_batches_diagnostic_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1, int nBatches, int64_t nPhotons,
+                                            const i3rc_source *src, double *sum, double *sumSquares, double *counters,
+                                            double *extraSum, double *extraSumSquares);
+
 /* computeRadiativeTransfer (:262-398) for ONE batch of a driver's loop -- i3rc_hip_zero_tallies + i3rc_hip_launch_batch(seed0,
  * seed1, 0, nPhotons) + i3rc_hip_fetch_tallies into hostTallies, in a tally buffer and on a stream of the library's own --
  * that LOOKS AHEAD: the reference's drivers call computeRadiativeTransfer once per batch with
