@@ -1091,15 +1091,10 @@ __global__ void __launch_bounds__(256) reduce_counters_kernel(const double *coun
   out[(size_t)b * stride + oCnt + k] = v;
 }
 
-// ---- batch moments on the device (i3rc_hip_run_batches_moments) ---------------------------------------------------------
+// ---- batch moments on the device (i3rc_hip_run_batches_moments, i3rc_hip_run_batches_diagnostic_moments) ----------------
 // A driver only ever wants the first two moments over its batches of what reportResults hands out (monteCarloDriver.f95:
 // 300-321, reduced at :333-352): per batch the raw block is normalised by the rule of tally_block.hpp, which i3rc_hip_normalise follows too (:353-395,
 // float64, rounded to the reference's real(4)) and x, x^2 are added up per element -- the per-batch blocks never leave the device.
-struct MomentsDev {
-  TallyView raw;   // the raw tally block, over the device copies of its two arrays ...
-  // ... and the moments block (i3rc_moments_layout)
-  long long mUp, mDown, mAbs, mVol, mInt, mProfile, mMeanUp, mMeanDown, mMeanAbs, mMeanInt;
-};
 // one normalised field value of a batch; e counts through fluxUp | fluxDown | fluxAbsorbed | volumeAbsorption | intensity
 __device__ __forceinline__ float moments_field_value(const TallyView &V, const double *raw, const double *excessSums, long long e) {
   const long long ncol = (long long)V.nx * V.ny, ncell = ncol * V.nz;
@@ -1117,101 +1112,91 @@ __device__ __forceinline__ float moments_field_value(const TallyView &V, const d
   const int d = (int)(e / ncol);
   return normalised_intensity(V, raw, excessSums, d, e - d * ncol);
 }
+// What a moments pass adds up, handed to its two kernels by value: element e of batch b (`raw`: the batch's block), the number of
+// fields -- they lie in front of the sums in the order e counts them --, the number of domain means, and for mean q its first
+// element and its place in the sums.  V's two arrays are device memory here.
+struct BatchFields {   // what reportResults hands out (i3rc_moments_layout)
+  TallyView V;
+  i3rc_moments_layout L;
+  const double *excessSums;   // moments_excess_kernel's, (ncomp + 1) * nDir per batch
+  __device__ __forceinline__ float value(const double *raw, int b, long long e) const {
+    return moments_field_value(V, raw, excessSums + (size_t)b * ((V.ncomp + 1) * V.nDir), e);
+  }
+  __host__ __device__ __forceinline__ long long fields() const { return L.absorbedProfile; }   // (fluxUp ... intensity: everything in front of the profile)
+  // domain means (:739-742), the absorption profile (:780) and the mean radiances
+  __host__ __device__ __forceinline__ int means() const { return 3 + V.nz + V.nDir; }
+  __device__ __forceinline__ void mean(int q, long long &first, long long &at) const {
+    const long long ncol = (long long)V.nx * V.ny;
+    // (the three places read before one is chosen: a choice among the members' addresses would keep a copy of *this in scratch)
+    const long long flux[3] = {L.meanFluxUp, L.meanFluxDown, L.meanFluxAbsorbed};
+    if (q < 3) { first = q * ncol; at = flux[q]; }
+    else if (q < 3 + V.nz) { first = 3 * ncol + (long long)(q - 3) * ncol; at = L.absorbedProfile + (q - 3); }
+    else { first = 3 * ncol + ncol * V.nz + (long long)(q - 3 - V.nz) * ncol; at = L.meanIntensity + (q - 3 - V.nz); }
+  }
+};
+struct ExtraFields {   // the optional diagnostic tally: the kind's extra block, normalised by normalised_extra_value (extra_moments_layout)
+  TallyView V;
+  ExtraTally kind;
+  __device__ __forceinline__ float value(const double *raw, int, long long e) const { return normalised_extra_value(V, raw, kind, extra_block_offset(V.counters), e); }
+  __host__ __device__ __forceinline__ long long fields() const { return extra_block_words(kind, V.nx, V.ny, V.nz); }
+  // one mean per level of levelFluxUp | level of levelFluxDown, or per layer: over the columns of the elements q * ncol ...
+  __host__ __device__ __forceinline__ int means() const { return (int)extra_moments_means(kind, V.nz); }
+  __device__ __forceinline__ void mean(int q, long long &first, long long &at) const { first = (long long)q * V.nx * V.ny; at = fields() + q; }
+};
+// the sum of v over the 256 threads of a workgroup (what thread 0 returns is used)
+__device__ __forceinline__ double workgroup_sum(double v) {
+  __shared__ double part[4];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return part[0] + part[1] + part[2] + part[3];
+}
 // excessSums[b][(j * nDir + d)] = sum over the columns of intensityByComponent(:, :, d, j) of batch b (one workgroup each)
-__global__ void __launch_bounds__(256) moments_excess_kernel(MomentsDev M, const double *blocks, long long stride, double *excessSums) {
-  const TallyView &V = M.raw;
+__global__ void __launch_bounds__(256) moments_excess_kernel(TallyView V, const double *blocks, long long stride, double *excessSums) {
   const int per = (V.ncomp + 1) * V.nDir, b = blockIdx.x / per, jd = blockIdx.x - b * per;
   const size_t ncol = (size_t)V.nx * V.ny;
   const double *f = blocks + (size_t)b * stride + V.intensityByComponent + (size_t)jd * ncol;
   double v = 0.0;
   for (size_t k = threadIdx.x; k < ncol; k += 256) v += f[k];
-  __shared__ double part[4];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) excessSums[(size_t)b * per + jd] = part[0] + part[1] + part[2] + part[3];
+  v = workgroup_sum(v);
+  if (threadIdx.x == 0) excessSums[(size_t)b * per + jd] = v;
 }
 // fields: one thread per element and SLICE of the group's batches (blockIdx.y; a slice's batches one after the other).  A small domain
 // with many batches -- 700 elements x 1e5 batches of a thousand photons -- would otherwise be a few hundred threads walking 1e5 batches
 // each, longer than the trace itself (round-4 advisor): the launch cuts the batches into as many slices as fill the chip.
-__global__ void __launch_bounds__(256) moments_fields_kernel(MomentsDev M, const double *blocks, int count, long long stride, const double *excessSums,
-                                                             long long nFields, double *sum, double *sumSq) {
+template <class Fields>
+__global__ void __launch_bounds__(256) moments_fields_kernel(Fields F, const double *blocks, int count, long long stride, double *sum, double *sumSq) {
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= nFields) return;
-  const int per = (M.raw.ncomp + 1) * M.raw.nDir;
+  if (e >= F.fields()) return;
   const int perSlice = (count + (int)gridDim.y - 1) / (int)gridDim.y;
   const int b0 = (int)blockIdx.y * perSlice, b1 = min(count, b0 + perSlice);
   double s1 = 0.0, s2 = 0.0;
   for (int b = b0; b < b1; ++b) {
-    const double x = (double)moments_field_value(M.raw, blocks + (size_t)b * stride, excessSums + (size_t)b * per, e);
-    s1 += x; s2 += x * x;
-  }
-  // (fields lie in the moments block in the order e counts them: fluxUp | fluxDown | fluxAbsorbed | volumeAbsorption | intensity)
-  unsafeAtomicAdd(sum + M.mUp + e, s1);
-  unsafeAtomicAdd(sumSq + M.mUp + e, s2);
-}
-// domain means (:739-742), the absorption profile (:780) and the mean radiances: one workgroup per (batch, quantity)
-__global__ void __launch_bounds__(256) moments_means_kernel(MomentsDev M, const double *blocks, long long stride, const double *excessSums,
-                                                            double *sum, double *sumSq, double *counterTotals) {
-  const TallyView &V = M.raw;
-  const int nq = 3 + V.nz + V.nDir, b = blockIdx.x / nq, q = blockIdx.x - b * nq;
-  const double *raw = blocks + (size_t)b * stride;
-  const int per = (V.ncomp + 1) * V.nDir;
-  const long long ncol = (long long)V.nx * V.ny;
-  long long first, at;   // first field element of the quantity (moments_field_value's numbering) and its place in the moments block
-  if (q < 3) { first = q * ncol; at = q == 0 ? M.mMeanUp : (q == 1 ? M.mMeanDown : M.mMeanAbs); }
-  else if (q < 3 + V.nz) { first = 3 * ncol + (long long)(q - 3) * ncol; at = M.mProfile + (q - 3); }
-  else { first = 3 * ncol + ncol * V.nz + (long long)(q - 3 - V.nz) * ncol; at = M.mMeanInt + (q - 3 - V.nz); }
-  double v = 0.0;
-  for (long long k = threadIdx.x; k < ncol; k += 256) v += (double)moments_field_value(V, raw, excessSums + (size_t)b * per, first + k);
-  __shared__ double part[4];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const double x = (double)(float)((part[0] + part[1] + part[2] + part[3]) / (double)ncol);
-    unsafeAtomicAdd(sum + at, x);
-    unsafeAtomicAdd(sumSq + at, x * x);
-  }
-  if (q == 0 && threadIdx.x < I3RC_NUM_COUNTERS) unsafeAtomicAdd(counterTotals + threadIdx.x, raw[V.counters + threadIdx.x]);
-}
-
-// ---- ... and of the optional diagnostic tally (i3rc_hip_run_batches_diagnostic_moments) -----------------------------------------------
-// The kind's extra block of every batch, normalised by normalised_extra_value and added up in a moments block of its own
-// (extra_moments_layout): the fields lie there as the block's elements do, the domain means behind them.
-// fields: one thread per element and slice of the batches, as moments_fields_kernel
-__global__ void __launch_bounds__(256) moments_extra_fields_kernel(TallyView V, ExtraTally kind, long long block, const double *blocks, int count,
-                                                                   long long stride, long long nFields, double *sum, double *sumSq) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= nFields) return;
-  const int perSlice = (count + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int b0 = (int)blockIdx.y * perSlice, b1 = min(count, b0 + perSlice);
-  double s1 = 0.0, s2 = 0.0;
-  for (int b = b0; b < b1; ++b) {
-    const double x = (double)normalised_extra_value(V, blocks + (size_t)b * stride, kind, block, e);
+    const double x = (double)F.value(blocks + (size_t)b * stride, b, e);
     s1 += x; s2 += x * x;
   }
   unsafeAtomicAdd(sum + e, s1);
   unsafeAtomicAdd(sumSq + e, s2);
 }
-// domain means: one workgroup per (batch, level of levelFluxUp | level of levelFluxDown, or layer); mean q is the mean over the columns
-// of the elements q * ncol ... of the block, and lies at nFields + q
-__global__ void __launch_bounds__(256) moments_extra_means_kernel(TallyView V, ExtraTally kind, long long block, const double *blocks, long long stride,
-                                                                  int nMeans, long long nFields, double *sum, double *sumSq) {
-  const int b = blockIdx.x / nMeans, q = blockIdx.x - b * nMeans;
+// domain means: one workgroup per (batch, mean), float32(sum over the columns / number of columns); the workgroup of a batch's first
+// mean also adds the batch's counters to counterTotals (where the caller wants them)
+template <class Fields>
+__global__ void __launch_bounds__(256) moments_means_kernel(Fields F, const double *blocks, long long stride, double *sum, double *sumSq,
+                                                            double *counterTotals) {
+  const int nq = F.means(), b = blockIdx.x / nq, q = blockIdx.x - b * nq;
   const double *raw = blocks + (size_t)b * stride;
-  const long long ncol = (long long)V.nx * V.ny;
+  const long long ncol = (long long)F.V.nx * F.V.ny;
+  long long first, at;
+  F.mean(q, first, at);
   double v = 0.0;
-  for (long long k = threadIdx.x; k < ncol; k += 256) v += (double)normalised_extra_value(V, raw, kind, block, q * ncol + k);
-  __shared__ double part[4];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
+  for (long long k = threadIdx.x; k < ncol; k += 256) v += (double)F.value(raw, b, first + k);
+  v = workgroup_sum(v);
   if (threadIdx.x == 0) {
-    const double x = (double)(float)((part[0] + part[1] + part[2] + part[3]) / (double)ncol);
-    unsafeAtomicAdd(sum + nFields + q, x);
-    unsafeAtomicAdd(sumSq + nFields + q, x * x);
+    const double x = (double)(float)(v / (double)ncol);
+    unsafeAtomicAdd(sum + at, x);
+    unsafeAtomicAdd(sumSq + at, x * x);
   }
+  if (q == 0 && counterTotals && threadIdx.x < I3RC_NUM_COUNTERS) unsafeAtomicAdd(counterTotals + threadIdx.x, raw[F.V.counters + threadIdx.x]);
 }
 
 // Do the batches of a driver's loop -- nBatches of nPhotons each -- share one grid, group by group (see FusedSlot)?  The specialised
@@ -1358,75 +1343,63 @@ void moments_layout(const i3rc_hip_integrator *h, i3rc_moments_layout &L) {
   L.total = o;
 }
 
-// makes the handle's moment sums ready (zeroed) for a loop of batches
+// makes the handle's moment sums ready (zeroed) for a loop of batches -- those of the diagnostic tally too, where one is switched on
 int begin_moments(i3rc_hip_integrator *h) {
   i3rc_moments_layout L;
   moments_layout(h, L);
-  const size_t bytes = (size_t)L.total * sizeof(double);
+  const size_t bytes = (size_t)L.total * sizeof(double), extraBytes = (size_t)extra_moments_layout(h->extra, h->nx, h->ny, h->nz).total * sizeof(double);
   if (h->momSum.bytes != bytes) { HIPCHK(h, h->momSum.alloc(bytes)); HIPCHK(h, h->momSq.alloc(bytes)); }
+  if (h->momExtraSum.bytes != extraBytes) { HIPCHK(h, h->momExtraSum.alloc(extraBytes)); HIPCHK(h, h->momExtraSq.alloc(extraBytes)); }
   if (!h->momCounters.p) HIPCHK(h, h->momCounters.alloc(I3RC_NUM_COUNTERS * sizeof(double)));
   if (!h->momDz.p) {
     HIPCHK(h, h->momDz.upload(h->layerDepth.data(), h->layerDepth.size() * sizeof(double)));
     HIPCHK(h, h->momArea.upload(h->areaFrac.data(), h->areaFrac.size() * sizeof(double)));
   }
-  HIPCHK(h, hipMemset(h->momSum.p, 0, bytes));
-  HIPCHK(h, hipMemset(h->momSq.p, 0, bytes));
-  HIPCHK(h, hipMemset(h->momCounters.p, 0, I3RC_NUM_COUNTERS * sizeof(double)));
+  for (DevBuf *m : {&h->momSum, &h->momSq, &h->momExtraSum, &h->momExtraSq, &h->momCounters})
+    if (m->p) HIPCHK(h, hipMemset(m->p, 0, m->bytes));
   return 0;
+}
+
+// One moments pass: the fields and means F yields of `count` raw blocks on `stream`, x and x^2 added to `sum` / `sumSq`
+template <class Fields>
+void launch_moments(hipStream_t stream, const Fields &F, const double *blocks, int count, long long stride, DevBuf &sum, DevBuf &sumSq, double *counterTotals) {
+  // (slices of the batch range: enough threads for the chip -- 256 CUs x 8 workgroups -- however few the elements are, at least 8 batches a slice)
+  const long long fieldBlocks = (F.fields() + 255) / 256;
+  const int slices = (int)std::max<long long>(1, std::min<long long>({(long long)(count + 7) / 8, (2048 + fieldBlocks - 1) / fieldBlocks, 65535}));
+  hipLaunchKernelGGL(moments_fields_kernel<Fields>, dim3((unsigned)fieldBlocks, (unsigned)slices), dim3(256), 0, stream, F, blocks, count, stride,
+                     (double *)sum.p, (double *)sumSq.p);
+  hipLaunchKernelGGL(moments_means_kernel<Fields>, dim3((unsigned)(count * F.means())), dim3(256), 0, stream, F, blocks, stride, (double *)sum.p,
+                     (double *)sumSq.p, counterTotals);
 }
 
 // `count` raw tally blocks on the device (the handle's layout, counters filled in) -> normalised, x and x^2 added to the
-// handle's moment sums; asynchronous on `stream` (blocks from several streams may be added at the same time: float64 atomics)
+// handle's moment sums, the diagnostic block's (where the layout has one) to those of its own; asynchronous on `stream` (blocks from
+// several streams may be added at the same time: float64 atomics)
 int accumulate_moments(i3rc_hip_integrator *h, hipStream_t stream, const double *blocks, int count, DevBuf &excess) {
-  i3rc_moments_layout L;
-  moments_layout(h, L);
-  MomentsDev M;
-  M.raw = current_view(h);
-  M.raw.areaFrac = (const double *)h->momArea.p; M.raw.dz = (const double *)h->momDz.p;
-  M.mUp = L.fluxUp; M.mDown = L.fluxDown; M.mAbs = L.fluxAbsorbed; M.mVol = L.volumeAbsorption; M.mInt = L.intensity;
-  M.mProfile = L.absorbedProfile; M.mMeanUp = L.meanFluxUp; M.mMeanDown = L.meanFluxDown; M.mMeanAbs = L.meanFluxAbsorbed; M.mMeanInt = L.meanIntensity;
+  BatchFields F;
+  F.V = current_view(h);
+  F.V.areaFrac = (const double *)h->momArea.p; F.V.dz = (const double *)h->momDz.p;
+  moments_layout(h, F.L);
   const long long stride = h->layout.total;
-  const int per = (h->ncomp + 1) * h->nDir;
-  if (M.raw.limitContrib) {
+  if (F.V.limitContrib) {
+    const int per = (h->ncomp + 1) * h->nDir;
     const size_t need = (size_t)count * per * sizeof(double);
     if (excess.bytes < need) HIPCHK(h, excess.alloc(need));
-    hipLaunchKernelGGL(moments_excess_kernel, dim3((unsigned)(count * per)), dim3(256), 0, stream, M, blocks, stride, (double *)excess.p);
+    hipLaunchKernelGGL(moments_excess_kernel, dim3((unsigned)(count * per)), dim3(256), 0, stream, F.V, blocks, stride, (double *)excess.p);
   }
-  const long long nFields = L.absorbedProfile;   // (fluxUp ... intensity: everything in front of the profile)
-  // (slices of the batch range: enough threads for the chip -- 256 CUs x 8 workgroups -- however few the elements are, at least 8 batches a slice)
-  const long long fieldBlocks = (nFields + 255) / 256;
-  const int slices = (int)std::max<long long>(1, std::min<long long>({(long long)(count + 7) / 8, (2048 + fieldBlocks - 1) / fieldBlocks, 65535}));
-  hipLaunchKernelGGL(moments_fields_kernel, dim3((unsigned)fieldBlocks, (unsigned)slices), dim3(256), 0, stream, M, blocks, count, stride,
-                     (const double *)excess.p, nFields, (double *)h->momSum.p, (double *)h->momSq.p);
-  hipLaunchKernelGGL(moments_means_kernel, dim3((unsigned)(count * (3 + h->nz + h->nDir))), dim3(256), 0, stream, M, blocks, stride,
-                     (const double *)excess.p, (double *)h->momSum.p, (double *)h->momSq.p, (double *)h->momCounters.p);
+  F.excessSums = (const double *)excess.p;
+  launch_moments(stream, F, blocks, count, stride, h->momSum, h->momSq, (double *)h->momCounters.p);
+  if (h->extra != EXTRA_NONE) launch_moments(stream, ExtraFields{F.V, h->extra}, blocks, count, stride, h->momExtraSum, h->momExtraSq, nullptr);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
 
-// makes the handle's diagnostic moment sums ready (zeroed) for a loop of batches; behind begin_moments (the grid's device copies)
-int begin_extra_moments(i3rc_hip_integrator *h) {
-  const size_t bytes = (size_t)extra_moments_layout(h->extra, h->nx, h->ny, h->nz).total * sizeof(double);
-  if (h->momExtraSum.bytes != bytes || !h->momExtraSum.p) { HIPCHK(h, h->momExtraSum.alloc(bytes)); HIPCHK(h, h->momExtraSq.alloc(bytes)); }
-  HIPCHK(h, hipMemset(h->momExtraSum.p, 0, bytes));
-  HIPCHK(h, hipMemset(h->momExtraSq.p, 0, bytes));
-  return 0;
-}
-
-// The extra blocks of `count` raw tally blocks on the device -> normalised, x and x^2 added to the handle's diagnostic moment sums;
-// asynchronous on `stream`, as accumulate_moments (which serves the ordinary moments of the same blocks)
-int accumulate_extra_moments(i3rc_hip_integrator *h, hipStream_t stream, const double *blocks, int count) {
-  TallyView V = current_view(h);
-  V.areaFrac = (const double *)h->momArea.p; V.dz = (const double *)h->momDz.p;
-  const long long block = extra_block_offset(h->layout.counters), nFields = extra_block_words(h->extra, h->nx, h->ny, h->nz);
-  const int nMeans = (int)extra_moments_means(h->extra, h->nz);
-  const long long fieldBlocks = (nFields + 255) / 256;
-  const int slices = (int)std::max<long long>(1, std::min<long long>({(long long)(count + 7) / 8, (2048 + fieldBlocks - 1) / fieldBlocks, 65535}));
-  hipLaunchKernelGGL(moments_extra_fields_kernel, dim3((unsigned)fieldBlocks, (unsigned)slices), dim3(256), 0, stream, V, h->extra, block, blocks, count,
-                     (long long)h->layout.total, nFields, (double *)h->momExtraSum.p, (double *)h->momExtraSq.p);
-  hipLaunchKernelGGL(moments_extra_means_kernel, dim3((unsigned)(count * nMeans)), dim3(256), 0, stream, V, h->extra, block, blocks,
-                     (long long)h->layout.total, nMeans, nFields, (double *)h->momExtraSum.p, (double *)h->momExtraSq.p);
-  HIPCHK(h, hipGetLastError());
+// ... and the sums of a finished loop to the caller's arrays (counters, and the diagnostic pair: where the caller wants them)
+int download_moments(i3rc_hip_integrator *h, double *sum, double *sumSquares, double *counters, double *extraSum, double *extraSumSquares) {
+  const std::pair<double *, const DevBuf *> copies[] = {{sum, &h->momSum}, {sumSquares, &h->momSq}, {counters, &h->momCounters},
+                                                         {extraSum, &h->momExtraSum}, {extraSumSquares, &h->momExtraSq}};
+  for (const auto &c : copies)
+    if (c.first) HIPCHK(h, hipMemcpy(c.first, c.second->p, c.second->bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1436,9 +1409,7 @@ int run_batches_fused(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1, in
   const bool moments = hostTallies == nullptr;
   const int G = fused_group_size(h, nBatches, nPhotons, moments);
   const size_t blockBytes = (size_t)h->layout.total * sizeof(double);
-  drop_lookahead(h);
-  HIPCHK(h, hipStreamSynchronize(h->stream));   // whatever the caller had in flight on the handle's stream comes first
-  for (auto &g : h->fused) g.count = 0;
+  for (auto &g : h->fused) g.count = 0;   // (begin_batch_loop has called the look-ahead off, whose groups held them)
   int rc = 0;
   auto collect = [&](i3rc_hip_integrator::FusedSlot &g) -> int {
     if (g.count == 0) return 0;
@@ -1523,10 +1494,10 @@ int launch_batch_parts(i3rc_hip_integrator *h, const Launch &L, const RunArgs &A
   return 0;
 }
 
-// One Directional batch into pipeline slot `sl`: zeroed, traced and (copyBack) copied to the slot's pinned buffer, all asynchronous on
-// the slot's stream.  `who` names the caller in the error texts.
+// One Directional batch into pipeline slot `sl`: zeroed and traced, asynchronous on the slot's stream.  `who` names the caller in the
+// error texts.
 int run_batch_in_slot(i3rc_hip_integrator *h, i3rc_hip_integrator::PipeSlot &sl, uint32_t seed0, uint32_t seed1, int64_t nPhotons,
-                      const i3rc_source *src, bool timeIt, bool copyBack, const char *who) {
+                      const i3rc_source *src, bool timeIt, const char *who) {
   Launch L;
   RunArgs A;
   std::memset(&A, 0, sizeof(A));
@@ -1535,11 +1506,61 @@ int run_batch_in_slot(i3rc_hip_integrator *h, i3rc_hip_integrator::PipeSlot &sl,
   if (prepare_launch(h, plain_stream(h->extra), src, nPhotons, sl.stream, (double *)sl.tally.p, L, A)) return 1;
   const size_t bytes = (size_t)h->layout.total * sizeof(double);
   if (hipMemsetAsync(sl.tally.p, 0, bytes, sl.stream) != hipSuccess) return h->fail(std::string(who) + ": clearing a tally buffer failed");
-  if (launch_batch_parts(h, L, A, sl.stream, timeIt)) return 1;
-  if (copyBack && (hipMemcpyAsync(sl.pinned, sl.tally.p, bytes, hipMemcpyDeviceToHost, sl.stream) != hipSuccess ||
-                   hipEventRecord(sl.done, sl.stream) != hipSuccess))
+  return launch_batch_parts(h, L, A, sl.stream, timeIt);
+}
+// ... and its block on the way into the slot's pinned buffer behind the trace; sl.done tells when it is there
+int copy_back_slot(i3rc_hip_integrator *h, i3rc_hip_integrator::PipeSlot &sl, const char *who) {
+  if (hipMemcpyAsync(sl.pinned, sl.tally.p, (size_t)h->layout.total * sizeof(double), hipMemcpyDeviceToHost, sl.stream) != hipSuccess ||
+      hipEventRecord(sl.done, sl.stream) != hipSuccess)
     return h->fail(std::string(who) + ": copying a batch's tallies back failed");
   return 0;
+}
+
+// What the three calls that run a driver's loop do first, `who` in the error texts: the checks (argsOk: the caller's pointers and
+// batch count), then the handle made ready -- the look-ahead called off (i3rc_hip_compute_batch shares the slots), and whatever the
+// caller had in flight on the handle's stream comes first.  diagnostic: the loop is one WITH a diagnostic tally, which must be on and
+// fit a plain launch (the call then names itself in front of the photon count's text too); any other loop has none.
+int begin_batch_loop(i3rc_hip_integrator *h, const std::string &who, bool argsOk, const i3rc_source *src, int64_t nPhotons, bool diagnostic) {
+  if (!h) return 1;
+  if (!argsOk) return h->fail(who + ": bad arguments");
+  if (diagnostic && h->extra == EXTRA_NONE)
+    return h->fail(who + ": no diagnostic tally is switched on (i3rc_hip_set_level_fluxes or i3rc_hip_set_actinic_flux first; "
+                   "i3rc_hip_run_batches_moments serves a loop without one)");
+  if (src->kind != 0) return h->fail(who + ": Directional photon streams only (explicit streams differ from batch to batch)");
+  if (nPhotons <= 0) return h->fail((diagnostic ? who + ": " : "") + "setIllumination: must ask for non-negative number of photons.");
+  if (extra_tally_refused(h, who.c_str(), !diagnostic)) return 1;
+  HIPCHK(h, hipSetDevice(h->device));
+  drop_lookahead(h);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// A loop's batches one launch each, batch b into slot b % K, up to K in flight (inFlight <= 0: six): behind a batch's trace
+// `queue(slot)` puts the call's own work on the slot's stream, and `finish(slot)` waits for a batch and takes what the call wants of
+// it -- before its slot is used again, and for every slot at the end.  Nothing of the call stays in flight, also after a failure.
+template <class Queue, class Finish>
+int run_batch_pipeline(i3rc_hip_integrator *h, const char *who, uint32_t seed0, uint32_t seed1, int nBatches, int64_t nPhotons, const i3rc_source *src,
+                       int inFlight, Queue &&queue, Finish &&finish) {
+  const int K = std::min(nBatches, inFlight <= 0 ? 6 : std::min(inFlight, (int)i3rc_hip_integrator::kMaxInFlight));
+  if (reset_slots_if_layout_changed(h)) return 1;
+  for (int k = 0; k < K; ++k) {
+    if (ready_slot(h, k)) return 1;
+    h->pipe[k].batch = -1;
+  }
+  int rc = 0;
+  for (int b = 0; b < nBatches && !rc; ++b) {
+    auto &sl = h->pipe[b % K];
+    if (sl.batch >= 0) rc = finish(sl);
+    rc = rc || run_batch_in_slot(h, sl, seed0, seed1 + (uint32_t)b, nPhotons, src, true, who) || queue(sl);
+    if (!rc) sl.batch = b;
+  }
+  for (int k = 0; k < K; ++k) {
+    auto &sl = h->pipe[k];
+    if (!rc && sl.batch >= 0) rc = finish(sl);
+    if (rc) (void)hipStreamSynchronize(sl.stream);
+    sl.batch = -1;
+  }
+  return rc;
 }
 
 }  // namespace
@@ -1565,40 +1586,17 @@ int i3rc_hip_launch_batch(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1
 // The batch loop of a driver (Example-Drivers/monteCarloDriver.f95:283-326) as one call: see include/i3rc_hip.h
 int i3rc_hip_run_batches(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1, int nBatches, int64_t nPhotons,
                          const i3rc_source *src, int inFlight, double *hostTallies) {
-  if (!h) return 1;
-  if (!src || !hostTallies || nBatches < 1) return h->fail("i3rc_hip_run_batches: bad arguments");
-  if (src->kind != 0) return h->fail("i3rc_hip_run_batches: Directional photon streams only (explicit streams differ from batch to batch)");
-  if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
-  if (extra_tally_refused(h, "i3rc_hip_run_batches", true)) return 1;
-  HIPCHK(h, hipSetDevice(h->device));
+  static const char who[] = "i3rc_hip_run_batches";
+  if (begin_batch_loop(h, who, src && hostTallies && nBatches >= 1, src, nPhotons, false)) return 1;
   if (fuse_loop(h, nPhotons, nBatches)) return run_batches_fused(h, seed0, seed1, nBatches, nPhotons, src, hostTallies);
-  const int K = std::min(nBatches, inFlight <= 0 ? 6 : std::min(inFlight, (int)i3rc_hip_integrator::kMaxInFlight));
-  const size_t bytes = (size_t)h->layout.total * sizeof(double);
-  drop_lookahead(h);               // (i3rc_hip_compute_batch shares the slots)
-  if (reset_slots_if_layout_changed(h)) return 1;
-  for (int k = 0; k < K; ++k) {
-    if (ready_slot(h, k)) return 1;
-    h->pipe[k].batch = -1;
-  }
-  HIPCHK(h, hipStreamSynchronize(h->stream));   // whatever the caller had in flight on the handle's stream comes first
-  int rc = 0;
-  auto collect = [&](i3rc_hip_integrator::PipeSlot &sl) -> int {
-    if (sl.batch < 0) return 0;
-    HIPCHK(h, hipEventSynchronize(sl.done));
-    std::memcpy(hostTallies + (size_t)sl.batch * (size_t)h->layout.total, sl.pinned, bytes);
-    sl.batch = -1;
-    return 0;
-  };
-  for (int b = 0; b < nBatches && !rc; ++b) {
-    auto &sl = h->pipe[b % K];
-    if ((rc = collect(sl)) || (rc = run_batch_in_slot(h, sl, seed0, seed1 + (uint32_t)b, nPhotons, src, true, true, "i3rc_hip_run_batches"))) break;
-    sl.batch = b;
-  }
-  for (int k = 0; k < K; ++k) {   // drain (also after a failure: nothing of this call stays in flight)
-    if (rc) { (void)hipStreamSynchronize(h->pipe[k].stream); h->pipe[k].batch = -1; }
-    else rc = collect(h->pipe[k]);
-  }
-  return rc;
+  // every batch's block comes back through its slot's pinned buffer
+  return run_batch_pipeline(
+      h, who, seed0, seed1, nBatches, nPhotons, src, inFlight, [&](i3rc_hip_integrator::PipeSlot &sl) { return copy_back_slot(h, sl, who); },
+      [&](i3rc_hip_integrator::PipeSlot &sl) -> int {
+        HIPCHK(h, hipEventSynchronize(sl.done));
+        std::memcpy(hostTallies + (size_t)sl.batch * (size_t)h->layout.total, sl.pinned, (size_t)h->layout.total * sizeof(double));
+        return 0;
+      });
 }
 
 int i3rc_hip_get_moments_layout(const i3rc_hip_integrator *h, i3rc_moments_layout *layout) {
@@ -1607,41 +1605,30 @@ int i3rc_hip_get_moments_layout(const i3rc_hip_integrator *h, i3rc_moments_layou
   return 0;
 }
 
-// A driver's batch loop with its statistics gathered on the device: see include/i3rc_hip.h
+// A loop's batches with their statistics gathered on the device (the two entry points below; extraSum / extraSumSquares: the
+// diagnostic tally's, nullptr for a loop without one).  Problems whose batches share a grid go there group by group; the others (the
+// general kernels -- a diagnostic tally's among them --, long batches) one launch per batch, each batch's block normalised and added up
+// on its slot's stream behind its trace.
+static int run_batches_moments(i3rc_hip_integrator *h, const char *who, uint32_t seed0, uint32_t seed1, int nBatches, int64_t nPhotons,
+                               const i3rc_source *src, double *sum, double *sumSquares, double *counters, double *extraSum, double *extraSumSquares) {
+  if (begin_moments(h)) return 1;
+  const int rc =
+      h->extra == EXTRA_NONE && fuse_loop(h, nPhotons, nBatches)   // (no fused kernel fills a diagnostic block: extra_tally_refused)
+          ? run_batches_fused(h, seed0, seed1, nBatches, nPhotons, src, nullptr)
+          : run_batch_pipeline(
+                h, who, seed0, seed1, nBatches, nPhotons, src, 0,
+                [&](i3rc_hip_integrator::PipeSlot &sl) { return accumulate_moments(h, sl.stream, (const double *)sl.tally.p, 1, sl.excess); },
+                [&](i3rc_hip_integrator::PipeSlot &sl) {
+                  return hipStreamSynchronize(sl.stream) == hipSuccess ? 0 : h->fail(std::string(who) + ": waiting for the batches failed");
+                });
+  return rc || download_moments(h, sum, sumSquares, counters, extraSum, extraSumSquares);
+}
+
 int i3rc_hip_run_batches_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1, int nBatches, int64_t nPhotons,
                                  const i3rc_source *src, double *sum, double *sumSquares, double *counters) {
-  if (!h) return 1;
-  if (!src || !sum || !sumSquares || nBatches < 1) return h->fail("i3rc_hip_run_batches_moments: bad arguments");
-  if (src->kind != 0) return h->fail("i3rc_hip_run_batches_moments: Directional photon streams only (explicit streams differ from batch to batch)");
-  if (nPhotons <= 0) return h->fail("setIllumination: must ask for non-negative number of photons.");
-  if (extra_tally_refused(h, "i3rc_hip_run_batches_moments", true)) return 1;
-  HIPCHK(h, hipSetDevice(h->device));
-  drop_lookahead(h);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (begin_moments(h)) return 1;
-  int rc = 0;
-  if (fuse_loop(h, nPhotons, nBatches))
-    rc = run_batches_fused(h, seed0, seed1, nBatches, nPhotons, src, nullptr);
-  else {
-    // other problems (the general kernels; long batches): one launch per batch, several in flight as in i3rc_hip_run_batches, each
-    // batch's block normalised and added up on its slot's stream behind its launch
-    const int K = std::min(nBatches, 6);
-    if (reset_slots_if_layout_changed(h)) return 1;
-    for (int k = 0; k < K; ++k) { if (ready_slot(h, k)) return 1; h->pipe[k].batch = -1; }
-    for (int b = 0; b < nBatches && !rc; ++b) {
-      auto &sl = h->pipe[b % K];
-      rc = run_batch_in_slot(h, sl, seed0, seed1 + (uint32_t)b, nPhotons, src, true, false, "i3rc_hip_run_batches_moments") ||
-           accumulate_moments(h, sl.stream, (const double *)sl.tally.p, 1, sl.excess);
-    }
-    for (int k = 0; k < K; ++k) if (h->pipe[k].stream && hipStreamSynchronize(h->pipe[k].stream) != hipSuccess && !rc) rc = h->fail("i3rc_hip_run_batches_moments: waiting for the batches failed");
-  }
-  if (rc) return 1;
-  i3rc_moments_layout L;
-  moments_layout(h, L);
-  HIPCHK(h, hipMemcpy(sum, h->momSum.p, (size_t)L.total * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(h, hipMemcpy(sumSquares, h->momSq.p, (size_t)L.total * sizeof(double), hipMemcpyDeviceToHost));
-  if (counters) HIPCHK(h, hipMemcpy(counters, h->momCounters.p, I3RC_NUM_COUNTERS * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
+  static const char who[] = "i3rc_hip_run_batches_moments";
+  return begin_batch_loop(h, who, src && sum && sumSquares && nBatches >= 1, src, nPhotons, false) ||
+         run_batches_moments(h, who, seed0, seed1, nBatches, nPhotons, src, sum, sumSquares, counters, nullptr, nullptr);
 }
 
 int i3rc_hip_diagnostic_moments_layout_words(int kind, int nx, int ny, int nz, int64_t *out, int nout) {
@@ -1667,42 +1654,8 @@ int i3rc_hip_run_batches_diagnostic_moments(i3rc_hip_integrator *h, uint32_t see
                                             const i3rc_source *src, double *sum, double *sumSquares, double *counters, double *extraSum,
                                             double *extraSumSquares) {
   static const char who[] = "i3rc_hip_run_batches_diagnostic_moments";
-  if (!h) return 1;
-  if (!src || !sum || !sumSquares || !extraSum || !extraSumSquares || nBatches < 1) return h->fail(std::string(who) + ": bad arguments");
-  if (h->extra == EXTRA_NONE)
-    return h->fail(std::string(who) + ": no diagnostic tally is switched on (i3rc_hip_set_level_fluxes or i3rc_hip_set_actinic_flux first; "
-                   "i3rc_hip_run_batches_moments serves a loop without one)");
-  if (src->kind != 0) return h->fail(std::string(who) + ": Directional photon streams only (explicit streams differ from batch to batch)");
-  if (nPhotons <= 0) return h->fail(std::string(who) + ": setIllumination: must ask for non-negative number of photons.");
-  if (extra_tally_refused(h, who, false)) return 1;
-  HIPCHK(h, hipSetDevice(h->device));
-  drop_lookahead(h);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (begin_moments(h) || begin_extra_moments(h)) return 1;
-  // one launch per batch (the general flux kernel under the kind's tag, as i3rc_hip_launch_batch runs it), several in flight, each
-  // batch's block normalised and added up on its slot's stream behind its launch -- never a fused group
-  const int K = std::min(nBatches, 6);
-  if (reset_slots_if_layout_changed(h)) return 1;
-  for (int k = 0; k < K; ++k) { if (ready_slot(h, k)) return 1; h->pipe[k].batch = -1; }
-  int rc = 0;
-  for (int b = 0; b < nBatches && !rc; ++b) {
-    auto &sl = h->pipe[b % K];
-    rc = run_batch_in_slot(h, sl, seed0, seed1 + (uint32_t)b, nPhotons, src, true, false, who) ||
-         accumulate_moments(h, sl.stream, (const double *)sl.tally.p, 1, sl.excess) ||
-         accumulate_extra_moments(h, sl.stream, (const double *)sl.tally.p, 1);
-  }
-  for (int k = 0; k < K; ++k)
-    if (h->pipe[k].stream && hipStreamSynchronize(h->pipe[k].stream) != hipSuccess && !rc) rc = h->fail(std::string(who) + ": waiting for the batches failed");
-  if (rc) return 1;
-  i3rc_moments_layout L;
-  moments_layout(h, L);
-  const size_t extraBytes = (size_t)extra_moments_layout(h->extra, h->nx, h->ny, h->nz).total * sizeof(double);
-  HIPCHK(h, hipMemcpy(sum, h->momSum.p, (size_t)L.total * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(h, hipMemcpy(sumSquares, h->momSq.p, (size_t)L.total * sizeof(double), hipMemcpyDeviceToHost));
-  if (counters) HIPCHK(h, hipMemcpy(counters, h->momCounters.p, I3RC_NUM_COUNTERS * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(h, hipMemcpy(extraSum, h->momExtraSum.p, extraBytes, hipMemcpyDeviceToHost));
-  HIPCHK(h, hipMemcpy(extraSumSquares, h->momExtraSq.p, extraBytes, hipMemcpyDeviceToHost));
-  return 0;
+  return begin_batch_loop(h, who, src && sum && sumSquares && extraSum && extraSumSquares && nBatches >= 1, src, nPhotons, true) ||
+         run_batches_moments(h, who, seed0, seed1, nBatches, nPhotons, src, sum, sumSquares, counters, extraSum, extraSumSquares);
 }
 
 // computeRadiativeTransfer for one batch of a driver's loop, looking ahead: see include/i3rc_hip.h
@@ -1723,7 +1676,8 @@ int i3rc_hip_compute_batch(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed
     return -1;
   };
   auto start = [&](int k, uint32_t s1, bool timed) -> int {   // (batches launched ahead of the caller are not recorded in the ring of timed launches)
-    if (ready_slot(h, k) || run_batch_in_slot(h, h->pipe[k], seed0, s1, nPhotons, src, timed, true, "i3rc_hip_compute_batch")) return 1;
+    static const char who[] = "i3rc_hip_compute_batch";
+    if (ready_slot(h, k) || run_batch_in_slot(h, h->pipe[k], seed0, s1, nPhotons, src, timed, who) || copy_back_slot(h, h->pipe[k], who)) return 1;
     h->pipe[k].batch = 0;   // in use (any value >= 0; i3rc_hip_run_batches keeps a batch number here)
     return 0;
   };

@@ -733,9 +733,23 @@ contains
     integer,            intent(in   ) :: iseed, firstBatch, numBatches, numberOfPhotons
     real,               intent(in   ) :: solarMu, solarAzimuth
     type(ErrorMessage), intent(inout) :: status
-    type(i3rc_source)         :: source
-    type(i3rc_moments_layout) :: layout
-    real(c_double)            :: counters(I3RC_NUM_COUNTERS)
+
+    call computeBatchMoments(thisIntegrator, .false., iseed, firstBatch, numBatches, solarMu, solarAzimuth, numberOfPhotons, status)
+  end subroutine computeRadiativeTransferBatchMoments
+
+  ! What stands behind computeRadiativeTransferBatchMoments and (diagnostic) computeRadiativeTransferDiagnosticMoments
+  subroutine computeBatchMoments(thisIntegrator, diagnostic, iseed, firstBatch, numBatches, solarMu, solarAzimuth, &
+                                 numberOfPhotons, status)
+    type(integrator),   intent(inout) :: thisIntegrator
+    logical,            intent(in   ) :: diagnostic
+    integer,            intent(in   ) :: iseed, firstBatch, numBatches, numberOfPhotons
+    real,               intent(in   ) :: solarMu, solarAzimuth
+    type(ErrorMessage), intent(inout) :: status
+    type(i3rc_source)                    :: source
+    type(i3rc_moments_layout)            :: layout
+    type(i3rc_diagnostic_moments_layout) :: extra
+    real(c_double)                       :: counters(I3RC_NUM_COUNTERS)
+    logical                              :: done
 
     if(.not. isReady_Integrator(thisIntegrator)) then
       call setStateToFailure(status, "computeRadiativeTransfer: problem not completely specified.")
@@ -750,17 +764,34 @@ contains
     source%kind = 0; source%solarMu = solarMu; source%solarAzimuth = solarAzimuth
     if(.not. deviceCall(thisIntegrator, i3rc_hip_get_moments_layout(thisIntegrator%device, layout), &
                         "computeRadiativeTransfer", status)) return
+    extra%kind = 0
+    if(diagnostic) then
+      if(.not. deviceCall(thisIntegrator, i3rc_hip_get_diagnostic_moments_layout(thisIntegrator%device, extra), &
+                          "computeRadiativeTransfer", status)) return
+    end if
     if(associated(thisIntegrator%momentSums)) deallocate(thisIntegrator%momentSums, thisIntegrator%momentSquares)
     if(associated(thisIntegrator%diagnosticSums)) deallocate(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares)
     allocate(thisIntegrator%momentSums(layout%total), thisIntegrator%momentSquares(layout%total))
-    thisIntegrator%momentBatches = 0
-    if(.not. deviceCall(thisIntegrator, i3rc_hip_run_batches_moments(thisIntegrator%device, int(iseed, c_int32_t),          &
+    thisIntegrator%momentBatches = 0; thisIntegrator%diagnosticKind = 0
+    if(diagnostic) then
+      ! (without a diagnostic the library refuses below: one word each, so that the call has arrays to be given)
+      allocate(thisIntegrator%diagnosticSums(max(extra%total, 1_c_int64_t)), thisIntegrator%diagnosticSquares(max(extra%total, 1_c_int64_t)))
+      done = deviceCall(thisIntegrator, i3rc_hip_run_batches_diagnostic_moments(thisIntegrator%device, int(iseed, c_int32_t), &
+                        int(firstBatch, c_int32_t), int(numBatches, c_int), int(numberOfPhotons, c_int64_t), source,         &
+                        thisIntegrator%momentSums, thisIntegrator%momentSquares, counters,                                   &
+                        thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares), "computeRadiativeTransfer", status)
+      if(.not. done) deallocate(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares)
+    else
+      done = deviceCall(thisIntegrator, i3rc_hip_run_batches_moments(thisIntegrator%device, int(iseed, c_int32_t),          &
                         int(firstBatch, c_int32_t), int(numBatches, c_int), int(numberOfPhotons, c_int64_t), source,       &
-                        thisIntegrator%momentSums, thisIntegrator%momentSquares, counters), "computeRadiativeTransfer", status)) then
+                        thisIntegrator%momentSums, thisIntegrator%momentSquares, counters), "computeRadiativeTransfer", status)
+    end if
+    if(.not. done) then
       deallocate(thisIntegrator%momentSums, thisIntegrator%momentSquares)
       return
     end if
     thisIntegrator%momentBatches    = numBatches
+    thisIntegrator%diagnosticKind   = int(extra%kind)
     thisIntegrator%resultsValid     = .false.      ! (no single batch is current after this call: reportResults says so)
     thisIntegrator%photonsProcessed = counters(1 + I3RC_CNT_PHOTONS)
     thisIntegrator%photonsDropped   = counters(1 + I3RC_CNT_DROPPED)
@@ -769,7 +800,7 @@ contains
     else
       call setStateToFailure(status, "computeRadiativeTransfer: Didn't process any photons.")
     end if
-  end subroutine computeRadiativeTransferBatchMoments
+  end subroutine computeBatchMoments
 
   ! The batch moments of every process's share of a loop, summed over the processes: ONE all-reduce of ONE packed float64
   ! buffer (sums | sums of squares | with diagnostic moments: their sums | sums of squares | number of batches) -- where the reference's drivers call sumAcrossProcesses ten times on real(4)
@@ -823,50 +854,40 @@ contains
     integer,            intent(in   ) :: iseed, firstBatch, numBatches, numberOfPhotons
     real,               intent(in   ) :: solarMu, solarAzimuth
     type(ErrorMessage), intent(inout) :: status
-    type(i3rc_source)                    :: source
-    type(i3rc_moments_layout)            :: layout
-    type(i3rc_diagnostic_moments_layout) :: extra
-    real(c_double)                       :: counters(I3RC_NUM_COUNTERS)
 
-    if(.not. isReady_Integrator(thisIntegrator)) then
-      call setStateToFailure(status, "computeRadiativeTransfer: problem not completely specified.")
-      return
-    end if
-    if(numBatches < 1 .or. numberOfPhotons < 1) then
-      call setStateToFailure(status, "computeRadiativeTransfer: Didn't process any photons.")
-      return
-    end if
-    call ensureTables(thisIntegrator, status)
-    if(stateIsFailure(status)) return
-    source%kind = 0; source%solarMu = solarMu; source%solarAzimuth = solarAzimuth
-    if(.not. deviceCall(thisIntegrator, i3rc_hip_get_moments_layout(thisIntegrator%device, layout), &
-                        "computeRadiativeTransfer", status)) return
-    if(.not. deviceCall(thisIntegrator, i3rc_hip_get_diagnostic_moments_layout(thisIntegrator%device, extra), &
-                        "computeRadiativeTransfer", status)) return
-    if(associated(thisIntegrator%momentSums)) deallocate(thisIntegrator%momentSums, thisIntegrator%momentSquares)
-    if(associated(thisIntegrator%diagnosticSums)) deallocate(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares)
-    ! (without a diagnostic the library refuses below: one word each, so that the call has arrays to be given)
-    allocate(thisIntegrator%momentSums(layout%total), thisIntegrator%momentSquares(layout%total), &
-             thisIntegrator%diagnosticSums(max(extra%total, 1_c_int64_t)), thisIntegrator%diagnosticSquares(max(extra%total, 1_c_int64_t)))
-    thisIntegrator%momentBatches = 0; thisIntegrator%diagnosticKind = 0
-    if(.not. deviceCall(thisIntegrator, i3rc_hip_run_batches_diagnostic_moments(thisIntegrator%device, int(iseed, c_int32_t), &
-                        int(firstBatch, c_int32_t), int(numBatches, c_int), int(numberOfPhotons, c_int64_t), source,         &
-                        thisIntegrator%momentSums, thisIntegrator%momentSquares, counters,                                   &
-                        thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares), "computeRadiativeTransfer", status)) then
-      deallocate(thisIntegrator%momentSums, thisIntegrator%momentSquares, thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares)
-      return
-    end if
-    thisIntegrator%momentBatches    = numBatches
-    thisIntegrator%diagnosticKind   = int(extra%kind)
-    thisIntegrator%resultsValid     = .false.      ! (no single batch is current after this call: reportResults says so)
-    thisIntegrator%photonsProcessed = counters(1 + I3RC_CNT_PHOTONS)
-    thisIntegrator%photonsDropped   = counters(1 + I3RC_CNT_DROPPED)
-    if(thisIntegrator%photonsProcessed > 0.d0) then
-      call setStateToCompleteSuccess(status, "computeRadiativeTransfer: finished with photons")
-    else
-      call setStateToFailure(status, "computeRadiativeTransfer: Didn't process any photons.")
-    end if
+    call computeBatchMoments(thisIntegrator, .true., iseed, firstBatch, numBatches, solarMu, solarAzimuth, numberOfPhotons, status)
   end subroutine computeRadiativeTransferDiagnosticMoments
+
+  ! What reportBatchMoments and reportDiagnosticMoments hand out of a pair of moment blocks (sums and sums of squares over the batches),
+  !   from the 0-based word `at` on: a field's words, x fastest, into to(:, :, :, 1:2) -- element by element: a cloud field's volume is
+  !   millions of cells, and array-valued temporaries of that size have no place on a stack -- ...
+  subroutine copyFieldMoments(sums, squares, at, to)
+    real(c_double), dimension(:), intent(in ) :: sums, squares
+    integer(c_int64_t),           intent(in ) :: at
+    real, dimension(:, :, :, :),  intent(out) :: to
+    integer :: i, j, k
+    integer(c_int64_t) :: e
+
+    do k = 1, size(to, 3)
+      do j = 1, size(to, 2)
+        do i = 1, size(to, 1)
+          e = at + i + size(to, 1) * ((j - 1) + size(to, 2) * (k - 1))
+          to(i, j, k, 1) = real(sums(e))
+          to(i, j, k, 2) = real(squares(e))
+        end do
+      end do
+    end do
+  end subroutine copyFieldMoments
+
+  !   ... and one word per level, layer or direction into to(:, 1:2)
+  subroutine copyMeanMoments(sums, squares, at, to)
+    real(c_double), dimension(:), intent(in ) :: sums, squares
+    integer(c_int64_t),           intent(in ) :: at
+    real, dimension(:, :),        intent(out) :: to
+
+    to(:, 1) = real(sums   (at + 1:at + size(to, 1)))
+    to(:, 2) = real(squares(at + 1:at + size(to, 1)))
+  end subroutine copyMeanMoments
 
   subroutine reportDiagnosticMoments(thisIntegrator, levelFluxUpStats, levelFluxDownStats, meanLevelFluxUpStats, &
                                      meanLevelFluxDownStats, actinicFluxStats, meanActinicFluxStats, status)
@@ -904,22 +925,12 @@ contains
       integer,                     intent(in ) :: n
       real, dimension(:, :, :, :), intent(out) :: to
       character(len = *),          intent(in ) :: name, what
-      integer :: i, j, k
-      integer(c_int64_t) :: e
       if(at < 0) then
         call setStateToFailure(status, "reportDiagnosticMoments: " // what // " information not available")
       else if(any(shape(to) /= (/ nx, ny, n, 2 /))) then
         call setStateToFailure(status, "reportDiagnosticMoments: " // name // " array is the wrong size")
       else
-        do k = 1, n
-          do j = 1, ny
-            do i = 1, nx
-              e = at + i + nx * ((j - 1) + ny * (k - 1))
-              to(i, j, k, 1) = real(thisIntegrator%diagnosticSums(e))
-              to(i, j, k, 2) = real(thisIntegrator%diagnosticSquares(e))
-            end do
-          end do
-        end do
+        call copyFieldMoments(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares, at, to)
       end if
     end subroutine fieldMoments
     subroutine meanMoments(at, n, to, name, what)
@@ -932,8 +943,7 @@ contains
       else if(any(shape(to) /= (/ n, 2 /))) then
         call setStateToFailure(status, "reportDiagnosticMoments: " // name // " array is the wrong size")
       else
-        to(:, 1) = real(thisIntegrator%diagnosticSums   (at + 1:at + n))
-        to(:, 2) = real(thisIntegrator%diagnosticSquares(at + 1:at + n))
+        call copyMeanMoments(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares, at, to)
       end if
     end subroutine meanMoments
   end subroutine reportDiagnosticMoments
@@ -951,8 +961,7 @@ contains
     real, dimension(:, :, :, :), optional, intent(  out) :: intensityStats                                  ! (nx, ny, nDir, 2)
     type(ErrorMessage),                    intent(inout) :: status
     type(i3rc_moments_layout) :: layout
-    integer :: nx, ny, nz, nDir, i, j, k
-    integer(c_int64_t) :: at
+    integer :: nx, ny, nz, nDir
 
     if(.not. associated(thisIntegrator%momentSums)) then
       call setStateToFailure(status, "reportBatchMoments: no batch moments have been computed.")
@@ -977,24 +986,14 @@ contains
       if(any(shape(absorbedProfileStats) /= (/ nz, 2 /))) then
         call setStateToFailure(status, "reportBatchMoments: absorbedProfileStats array is the wrong size")
       else
-        absorbedProfileStats(:, 1) = real(thisIntegrator%momentSums   (layout%absorbedProfile + 1:layout%absorbedProfile + nz))
-        absorbedProfileStats(:, 2) = real(thisIntegrator%momentSquares(layout%absorbedProfile + 1:layout%absorbedProfile + nz))
+        call copyMeanMoments(thisIntegrator%momentSums, thisIntegrator%momentSquares, layout%absorbedProfile, absorbedProfileStats)
       end if
     end if
     if(present(volumeAbsorptionStats)) then
       if(any(shape(volumeAbsorptionStats) /= (/ nx, ny, nz, 2 /))) then
         call setStateToFailure(status, "reportBatchMoments: volumeAbsorptionStats array is the wrong size")
       else
-        ! (element by element: a cloud field's volume is millions of cells, and array-valued temporaries of that size have no place on a stack)
-        do k = 1, nz
-          do j = 1, ny
-            do i = 1, nx
-              at = layout%volumeAbsorption + i + nx * ((j - 1) + ny * (k - 1))
-              volumeAbsorptionStats(i, j, k, 1) = real(thisIntegrator%momentSums(at))
-              volumeAbsorptionStats(i, j, k, 2) = real(thisIntegrator%momentSquares(at))
-            end do
-          end do
-        end do
+        call copyFieldMoments(thisIntegrator%momentSums, thisIntegrator%momentSquares, layout%volumeAbsorption, volumeAbsorptionStats)
       end if
     end if
     if(present(meanIntensityStats)) then
@@ -1003,8 +1002,7 @@ contains
       else if(any(shape(meanIntensityStats) /= (/ nDir, 2 /))) then
         call setStateToFailure(status, "reportBatchMoments: requesting mean intensity in the wrong number of directions.")
       else
-        meanIntensityStats(:, 1) = real(thisIntegrator%momentSums   (layout%meanIntensity + 1:layout%meanIntensity + nDir))
-        meanIntensityStats(:, 2) = real(thisIntegrator%momentSquares(layout%meanIntensity + 1:layout%meanIntensity + nDir))
+        call copyMeanMoments(thisIntegrator%momentSums, thisIntegrator%momentSquares, layout%meanIntensity, meanIntensityStats)
       end if
     end if
     if(present(intensityStats)) then
@@ -1013,15 +1011,7 @@ contains
       else if(any(shape(intensityStats) /= (/ nx, ny, nDir, 2 /))) then
         call setStateToFailure(status, "reportBatchMoments: intensity array has wrong dimensions.")
       else
-        do k = 1, nDir
-          do j = 1, ny
-            do i = 1, nx
-              at = layout%intensity + i + nx * ((j - 1) + ny * (k - 1))
-              intensityStats(i, j, k, 1) = real(thisIntegrator%momentSums(at))
-              intensityStats(i, j, k, 2) = real(thisIntegrator%momentSquares(at))
-            end do
-          end do
-        end do
+        call copyFieldMoments(thisIntegrator%momentSums, thisIntegrator%momentSquares, layout%intensity, intensityStats)
       end if
     end if
     if(.not. stateIsFailure(status)) call setStateToSuccess(status)

@@ -27,6 +27,13 @@ r32 = np.float32  # scalar float32 (f32() from the binding makes contiguous ARRA
 DEFAULT_MIN_TABLE_SIZE = 9001  # monteCarloRadiativeTransfer.f95:36-37
 
 
+def _directional(solarMu, solarAzimuth):
+    """the library's record of a Directional photon stream (new_PhotonStream(solarMu, solarAzimuth, ...))"""
+    s = B.Source()
+    s.kind, s.solarMu, s.solarAzimuth = 0, solarMu, solarAzimuth
+    return s
+
+
 # ---------------------------------------------------------------------------------------------------------
 class RandomNumberSequence:
     """new_RandomNumberSequence(seed): on the GPU the seed pair keys the per-photon Philox streams."""
@@ -374,11 +381,11 @@ class Integrator:
         self._ensure_tables()
         if zero:
             self._check(self._lib.i3rc_hip_zero_tallies(self._h), "computeRadiativeTransfer")
-        s = B.Source()
-        s.kind = incomingPhotons.kind
-        if s.kind == 0:
-            s.solarMu, s.solarAzimuth = incomingPhotons.solarMu, incomingPhotons.solarAzimuth
+        if incomingPhotons.kind == 0:
+            s = _directional(incomingPhotons.solarMu, incomingPhotons.solarAzimuth)
         else:
+            s = B.Source()
+            s.kind = incomingPhotons.kind
             s.x, s.y, s.z, s.mu, s.phi = [pf(a) for a in incomingPhotons.arrays]
         if firstPhoton is None:
             firstPhoton = randomNumbers.photonsDrawn
@@ -445,8 +452,7 @@ class Integrator:
             raise I3RCError("computeRadiativeTransfer: Didn't process any photons.")
         self._ensure_tables()
         raw = np.zeros(self.layout().total, np.float64)
-        s = B.Source()
-        s.kind, s.solarMu, s.solarAzimuth = 0, incomingPhotons.solarMu, incomingPhotons.solarAzimuth
+        s = _directional(incomingPhotons.solarMu, incomingPhotons.solarAzimuth)
         self._check(self._lib.i3rc_hip_compute_batch(self._h, randomNumbers.seed[0], randomNumbers.seed[1], incomingPhotons.n,
                                                      C.byref(s), int(lookAhead), raw.ctypes.data_as(B.dp)), "computeRadiativeTransfer")
         randomNumbers.photonsDrawn += incomingPhotons.n
@@ -463,8 +469,7 @@ class Integrator:
         self._ensure_tables()
         lay = self.layout()
         raw = np.zeros((int(numBatches), lay.total), np.float64)
-        s = B.Source()
-        s.kind, s.solarMu, s.solarAzimuth = 0, solarMu, solarAzimuth
+        s = _directional(solarMu, solarAzimuth)
         self._check(self._lib.i3rc_hip_run_batches(self._h, int(seed[0]), int(seed[1]), int(numBatches), int(numberOfPhotons),
                                                    C.byref(s), int(inFlight), raw.ctypes.data_as(B.dp)), "computeRadiativeTransfer")
         return [self.finish(raw[k]) for k in range(int(numBatches))]
@@ -473,30 +478,7 @@ class Integrator:
         """A driver's batch loop with its statistics gathered on the device (i3rc_hip_run_batches_moments): the sums and sums of
         squares over the batches of everything reportResults hands out (monteCarloDriver.f95:300-321), as two dicts of arrays in
         reportResults' shapes, plus the work counters summed over the batches.  No per-batch block comes back to the host."""
-        if not self.isReady_Integrator():
-            raise I3RCError("computeRadiativeTransfer: problem not completely specified.")
-        self._ensure_tables()
-        lay = B.MomentsLayout()
-        self._check(self._lib.i3rc_hip_get_moments_layout(self._h, C.byref(lay)), "computeRadiativeTransfer")
-        s1, s2, cnt = np.zeros(lay.total, np.float64), np.zeros(lay.total, np.float64), np.zeros(B.NUM_COUNTERS, np.float64)
-        s = B.Source()
-        s.kind, s.solarMu, s.solarAzimuth = 0, solarMu, solarAzimuth
-        self._check(self._lib.i3rc_hip_run_batches_moments(self._h, int(seed[0]), int(seed[1]), int(numBatches), int(numberOfPhotons), C.byref(s),
-                                                           s1.ctypes.data_as(B.dp), s2.ctypes.data_as(B.dp), cnt.ctypes.data_as(B.dp)), "computeRadiativeTransfer")
-        return self._unpack_moments(lay, s1), self._unpack_moments(lay, s2), {k: float(cnt[i]) for i, k in enumerate(B.COUNTER_NAMES)}
-
-    def _unpack_moments(self, lay, m):
-        """a block of batch moments (B.MomentsLayout) as a dict of arrays in reportResults' shapes"""
-        nd, ncol = len(self.intensityDirections), self.nx * self.ny
-        out = dict(fluxUp=m[lay.fluxUp:lay.fluxUp + ncol].reshape(self.ny, self.nx), fluxDown=m[lay.fluxDown:lay.fluxDown + ncol].reshape(self.ny, self.nx),
-                   fluxAbsorbed=m[lay.fluxAbsorbed:lay.fluxAbsorbed + ncol].reshape(self.ny, self.nx),
-                   volumeAbsorption=m[lay.volumeAbsorption:lay.volumeAbsorption + ncol * self.nz].reshape(self.nz, self.ny, self.nx),
-                   absorbedProfile=m[lay.absorbedProfile:lay.absorbedProfile + self.nz], meanFluxUp=m[lay.meanFluxUp],
-                   meanFluxDown=m[lay.meanFluxDown], meanFluxAbsorbed=m[lay.meanFluxAbsorbed])
-        if nd:
-            out["intensity"] = m[lay.intensity:lay.intensity + nd * ncol].reshape(nd, self.ny, self.nx)
-            out["meanIntensity"] = m[lay.meanIntensity:lay.meanIntensity + nd]
-        return out
+        return self._batch_moments(False, seed, numBatches, solarMu, solarAzimuth, numberOfPhotons)
 
     def computeRadiativeTransferDiagnosticMoments(self, seed, numBatches, solarMu, solarAzimuth, numberOfPhotons):
         """computeRadiativeTransferBatchMoments for a loop with a diagnostic tally switched on (specifyParameters: computeLevelFluxes or
@@ -505,33 +487,45 @@ class Integrator:
         (nz + 1, ny, nx), meanLevelFluxUp, meanLevelFluxDown (nz + 1) -- or of actinicFlux (nz, ny, nx) and meanActinicFlux (nz): the
         mean over the columns of every level or layer, per batch.  In cells without extinction the actinic flux's variance diverges
         (INTEGRATION.md): its standard errors are not to be trusted there."""
+        return self._batch_moments(True, seed, numBatches, solarMu, solarAzimuth, numberOfPhotons)
+
+    def _batch_moments(self, diagnostic, seed, numBatches, solarMu, solarAzimuth, numberOfPhotons):
+        """either moments call of the library: (sums, sums of squares, counters), the diagnostic tally's sums in the same two dicts"""
         if not self.isReady_Integrator():
             raise I3RCError("computeRadiativeTransfer: problem not completely specified.")
         self._ensure_tables()
         lay, xlay = B.MomentsLayout(), B.DiagnosticMomentsLayout()
         self._check(self._lib.i3rc_hip_get_moments_layout(self._h, C.byref(lay)), "computeRadiativeTransfer")
-        self._check(self._lib.i3rc_hip_get_diagnostic_moments_layout(self._h, C.byref(xlay)), "computeRadiativeTransfer")
-        s1, s2, cnt = np.zeros(lay.total, np.float64), np.zeros(lay.total, np.float64), np.zeros(B.NUM_COUNTERS, np.float64)
-        x1, x2 = np.zeros(max(xlay.total, 1), np.float64), np.zeros(max(xlay.total, 1), np.float64)
-        s = B.Source()
-        s.kind, s.solarMu, s.solarAzimuth = 0, solarMu, solarAzimuth
-        self._check(self._lib.i3rc_hip_run_batches_diagnostic_moments(
-            self._h, int(seed[0]), int(seed[1]), int(numBatches), int(numberOfPhotons), C.byref(s), s1.ctypes.data_as(B.dp),
-            s2.ctypes.data_as(B.dp), cnt.ctypes.data_as(B.dp), x1.ctypes.data_as(B.dp), x2.ctypes.data_as(B.dp)), "computeRadiativeTransfer")
-        ncol = self.nx * self.ny
+        bufs = [np.zeros(lay.total, np.float64), np.zeros(lay.total, np.float64), np.zeros(B.NUM_COUNTERS, np.float64)]
+        call = self._lib.i3rc_hip_run_batches_moments
+        if diagnostic:
+            self._check(self._lib.i3rc_hip_get_diagnostic_moments_layout(self._h, C.byref(xlay)), "computeRadiativeTransfer")
+            bufs += [np.zeros(max(xlay.total, 1), np.float64), np.zeros(max(xlay.total, 1), np.float64)]
+            call = self._lib.i3rc_hip_run_batches_diagnostic_moments
+        self._check(call(self._h, int(seed[0]), int(seed[1]), int(numBatches), int(numberOfPhotons), C.byref(_directional(solarMu, solarAzimuth)),
+                         *[b.ctypes.data_as(B.dp) for b in bufs]), "computeRadiativeTransfer")
+        s1, s2, cnt = bufs[:3]
+        x1, x2 = bufs[3:] or (None, None)
+        return (self._unpack_moments(lay, s1, xlay, x1), self._unpack_moments(lay, s2, xlay, x2),
+                {k: float(cnt[i]) for i, k in enumerate(B.COUNTER_NAMES)})
 
-        def unpack(m, x):
-            out = self._unpack_moments(lay, m)
-            if xlay.kind == B.EXTRA_KINDS["levels"]:
-                for k in ("levelFluxUp", "levelFluxDown"):
-                    out[k] = x[getattr(xlay, k):getattr(xlay, k) + (self.nz + 1) * ncol].reshape(self.nz + 1, self.ny, self.nx)
-                for k in ("meanLevelFluxUp", "meanLevelFluxDown"):
-                    out[k] = x[getattr(xlay, k):getattr(xlay, k) + self.nz + 1]
-            else:
-                out["actinicFlux"] = x[xlay.actinicFlux:xlay.actinicFlux + self.nz * ncol].reshape(self.nz, self.ny, self.nx)
-                out["meanActinicFlux"] = x[xlay.meanActinicFlux:xlay.meanActinicFlux + self.nz]
-            return out
-        return unpack(s1, x1), unpack(s2, x2), {k: float(cnt[i]) for i, k in enumerate(B.COUNTER_NAMES)}
+    def _unpack_moments(self, lay, m, xlay, x):
+        """a block of batch moments (B.MomentsLayout), and with a diagnostic tally the block of its moments (B.DiagnosticMomentsLayout: what the
+        loop's kind has not lies at -1), as a dict of arrays in reportResults' shapes"""
+        nd, ncol = len(self.intensityDirections), self.nx * self.ny
+
+        def part(block, at, *shape):
+            return block[at:at + int(np.prod(shape))].reshape(shape)
+        out = {k: part(m, getattr(lay, k), self.ny, self.nx) for k in ("fluxUp", "fluxDown", "fluxAbsorbed")}
+        out.update(volumeAbsorption=part(m, lay.volumeAbsorption, self.nz, self.ny, self.nx), absorbedProfile=part(m, lay.absorbedProfile, self.nz),
+                   meanFluxUp=m[lay.meanFluxUp], meanFluxDown=m[lay.meanFluxDown], meanFluxAbsorbed=m[lay.meanFluxAbsorbed])
+        if nd:
+            out.update(intensity=part(m, lay.intensity, nd, self.ny, self.nx), meanIntensity=part(m, lay.meanIntensity, nd))
+        for k, mean, levels in (("levelFluxUp", "meanLevelFluxUp", self.nz + 1), ("levelFluxDown", "meanLevelFluxDown", self.nz + 1),
+                                ("actinicFlux", "meanActinicFlux", self.nz)):
+            if x is not None and getattr(xlay, k) >= 0:
+                out[k], out[mean] = part(x, getattr(xlay, k), levels, self.ny, self.nx), part(x, getattr(xlay, mean), levels)
+        return out
 
     def set_batch_fusion(self, mode):
         """-1: automatic (default), 0: every batch a launch of its own, 1: fuse a loop's batches into one grid whenever the

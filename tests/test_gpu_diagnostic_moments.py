@@ -1,6 +1,6 @@
 """Batch statistics of the optional diagnostic tally on the device (i3rc_hip_run_batches_diagnostic_moments, through the mirror's
 computeRadiativeTransferDiagnosticMoments): the level fluxes and the actinic flux of a loop's batches, normalised and added up -- x and
-x^2, per element and per domain mean -- by moments_extra_fields_kernel / moments_extra_means_kernel behind every batch's launch.
+x^2, per element and per domain mean -- by moments_fields_kernel / moments_means_kernel over ExtraFields behind every batch's launch.
 
   the loop is its batches   s1, s2 against the same batches run one by one (computeRadiativeTransfer + reportResults, float64 sums on
                             the host), ordinary moments included, once per place of the extinction field and kind

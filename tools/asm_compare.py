@@ -19,7 +19,9 @@ def kernels(path):
         if text.startswith(".Lfunc_end"):   # (the kernel descriptor, .amdhsa_kernel ... .end_amdhsa_kernel, lies before it: part of the body)
             out[name], name = body, None
         elif text and not re.match(r"\.(loc|file|cfi_\w+)\b", text):
-            body.append(text)
+            # (a block label carries the number of its function in the file, .LBB<function>_<block>: kernels added or removed in front of
+            # this one renumber it and change nothing else)
+            body.append(re.sub(r"\.LBB\d+_", ".LBB_", text))
     return out
 
 
