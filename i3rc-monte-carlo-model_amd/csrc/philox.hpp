@@ -76,8 +76,14 @@ __host__ __device__ inline float u32_to_unit_float(uint32_t u) {
 //   spare()   Russian roulette
 // so that no run-time cursor has to be consulted for them.  Whatever else an event needs (component choice, the
 // max-cross-section test, a retry) comes from next(), a cursor over further blocks of the same photon.  The
-// local-estimate rays of an event draw from blocks of their own: same photon and block number, direction + 1 in the
-// fourth counter word (kernels.hpp, ray mode).  Which word serves which purpose is this code's own convention: the production streams are not the
+// local-estimate rays of an event draw from blocks of their own: same photon and key, direction + 1 in the fourth counter
+// word, and as block number the photon's block counter as the event LEAVES it (event_block(), read after part C of the
+// event phase: kernels.hpp, make_ray and the ring's record).  That is the event's own block number unless the event's
+// next() -- the component choice of a several-components domain, a reflection's retry -- had to refill: a refill takes
+// the photon's next block number, and the event's rays then carry the refill's number, not the event's.  Every kernel
+// reads it at the same point, so they agree; and no two blocks collide either way -- the photon's own blocks have 0 in
+// the fourth word, and two events of a photon never leave the counter at the same number.  Word 0 of a ray's block is its
+// free path, word 1 its roulette deviate.  Which word serves which purpose is this code's own convention: the production streams are not the
 // reference's Mersenne Twister sequence anyway, and every production kernel follows the same convention (tests
 // compare them photon by photon).  The replay stream hands out the reference's deviates in the reference's order.
 // BATCHED (fused multi-batch launches, kernels.hpp): the lanes of a wave carry photons of DIFFERENT batches of a driver's

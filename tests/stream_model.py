@@ -20,20 +20,33 @@ What the model follows (the line it restates in brackets):
   * radiance, plain local estimate: w P(theta) / (4 pi |mu_d|) exp(-tau) per event and direction, the surface's w / pi exp(-tau), into
     the column in which the RAY leaves the domain [service phase: `(sr.iy - 1) * nx + (sr.ix - 1)`]; hybrid tables for orders up
     to numOrdersOrig; the contribution limit [make_ray, service phase];
-  * counters, and the deviates consumed one by one (I3RC_CNT_RNG_DRAWS).
+  * the local estimate's own roulette (rr_intensity, Iwabuchi's; zeta_min): a ray's block is philox(photon_lo, photon_hi, the photon's
+    block counter as the event leaves it, direction + 1; the photon's key) -- word 0 its free path tauFree = -log(max(tiny, u0)), word 1
+    its roulette deviate r2, two deviates a ray whether it is traced or not [philox.hpp, the comment above PhiloxStreamT; make_ray].
+    pi norm <= zetaMin, a SMALL contribution: won = r2 zetaMin <= pi norm is decided before any trace; a lost ray adds nothing and counts
+    as skipped (I3RC_CNT_RAYS_SKIPPED); a won one adds w zetaMin / pi if the top lies within tauFree, else 0.  A LARGE one: tauMax =
+    -log(zetaMin / (pi norm)); the top within tauMax: the plain estimate; a first leg that leaves through the bottom: 0; else a second
+    leg from where the first one arrives, target tauFree: w zetaMin / pi if it leaves through the top, else 0.  A downward direction
+    never counts: its entries are exactly 0 (Result.exact_zero).  The contribution limit applies to whichever value results [make_ray,
+    service phase];
+  * counters, and the deviates consumed one by one (I3RC_CNT_RNG_DRAWS); I3RC_CNT_TRACER_CALLS: one per trace of a photon, per traced
+    ray and per second leg.
 The optical path is analytic: with C(z) the extinction integrated from the bottom, a path of optical depth tau along direction
 cosine dz ends where C changes by tau |dz|.  The tracer itself is pinned bit for bit elsewhere (tests/test_gpu_parity.py).
 
-Out of scope (the replay pin and the oracle tests cover them): max cross-section, the local estimate's own roulette (Iwabuchi) --
-and with it the local-estimate ray's Philox block, which is drawn for nothing else --, gridded surfaces, explicit photon sources,
-horizontally varying fields.
+Out of scope (the replay pin and the oracle tests cover them): max cross-section, gridded surfaces, explicit photon sources,
+horizontally varying fields, zetaMin = 0, a reflection's retry (a deviate of exactly 0: asserted not to occur), the diagnostic tallies.
 
 MARGINS AND BOUNDS.  Every discrete decision records its margin and the model's own bound on the float32 error of the compared
 quantity; a photon is FRAGILE when some margin is below 4 bounds.  The decisions: top / bottom / which layer (one comparison of
 optical depths), the component compare (both sides are float32 values the kernel holds too: bound 0), the roulette compares
 (w < 0.5, spare >= w), the column of an event, an exit or a ray's exit, the sign of the direction's z-cosine in next_direct (its
-frame changes hands there) and the contribution limit.  The table intervals are no such decisions here: the inverse table's k comes
-from a float32 product the model forms bit for bit, and the forward table's interpolation is continuous across k -- a neighbouring
+frame changes hands there) and the contribution limit; with the local estimate's roulette also pi norm against zetaMin (bound: pi e_norm
++ 3 eps of the product), r2 zetaMin against pi norm (+ 1 eps), the optical depth to the top against tauFree (e_tau + 2 ulp for fast_log)
+and against tauMax (e_tau + 2 ulp + 1 ulp for fast_div + 3 eps + e_norm / norm), the second leg's remaining depth against tauFree (all
+of these, + the arrival point's rounding) -- each only where its outcome reaches a tally or a counter, and a ray's column only where
+the ray counts.  The capped value w zetaMin (1 / pi) is formed with the float32 constant: the weight's bound + 3 eps.  The table
+intervals are no such decisions here: the inverse table's k comes from a float32 product the model forms bit for bit, and the forward table's interpolation is continuous across k -- a neighbouring
 interval is within what P at theta +- e_theta already allows.  The bound is first order and summed along
 the photon's events from what the code states: hardware sin / cos 1e-7 absolute, fast_log 2 ulp, v_rcp / v_sqrt / v_exp 1 ulp, one
 rounding (2^-24 relative) per float32 operation otherwise, one ulp for the scattering cosine wherever refined_rcp(n) one ulp off the
@@ -112,6 +125,8 @@ class Problem:
     hybrid: bool = False
     orders_orig: int = 0
     max_contrib: float = None       # the contribution limit; None: off
+    rr_intensity: bool = False      # the local estimate's own roulette (useRussianRouletteForIntensity)
+    zeta_min: float = 0.3           # ... and its bound (the library's default)
 
     def __post_init__(self):
         self.xe, self.ye, self.ze = (np.asarray(a, f32) for a in (self.xe, self.ye, self.ze))
@@ -136,6 +151,8 @@ class Result:
     counters: dict
     per_photon: dict                # fate (0 top, 1 surface, 2 roulette / absorbed), order, weight, fragile, counts, deposits
     caps: dict = field(default_factory=dict)
+    branches: dict = field(default_factory=dict)   # rays of the local estimate's roulette by what became of them (BRANCHES)
+    exact_zero: dict = field(default_factory=dict)  # per tally: entries nothing can reach, whatever a fragile photon does (a downward direction's, with the roulette)
 
     @property
     def fragile_share(self):
@@ -143,11 +160,18 @@ class Result:
 
 
 VARIANTS = ("swap first second", "azimuth from first", "table interval k + 1")
+# ... and of the local estimate's roulette (rr_intensity): each one a mistake the kernels could make in make_ray or the service phase
+RAY_VARIANTS = ("ray block ignores the direction", "ray counter word d", "r2 from word 0", "ray key without the batch", "ray block without the high word",
+                "second leg from the event", "downward direction counts")
+# what a ray of the roulette can do (Result.branches counts the rays of each)
+BRANCHES = ("small lost", "small won counted", "small won ended inside", "large first leg", "large through the bottom",
+            "second leg counted", "second leg ended inside", "surface small", "surface large", "capped above the limit")
 
 
-def run(P, seed, first_photon, n, variant=None, drop_high_word=False):
-    """n photons first_photon .. first_photon + n - 1 of the key `seed`"""
-    assert variant is None or variant in VARIANTS, variant
+def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0):
+    """n photons first_photon .. first_photon + n - 1 of the key (seed[0], seed[1] + batch): batch `batch` of a fused launch whose
+    first batch has the key `seed`"""
+    assert variant is None or variant in VARIANTS + RAY_VARIANTS, variant
     nx, ny, nz, ncomp = len(P.xe) - 1, len(P.ye) - 1, len(P.ze) - 1, P.ext.shape[0]
     xe, ye, ze = P.xe.astype(f64), P.ye.astype(f64), P.ze.astype(f64)
     x0, y0, Lx, Ly = xe[0], ye[0], xe[-1] - xe[0], ye[-1] - ye[0]
@@ -164,14 +188,18 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False):
     nd = P.ndir
     black = not (f32(P.albedo) > TINY) and nd == 0
     alb = float(f32(P.albedo))
-    k0, k1 = np.uint64(seed[0] & 0xFFFFFFFF), np.uint64(seed[1] & 0xFFFFFFFF)
+    k0, k1 = np.uint64(seed[0] & 0xFFFFFFFF), np.uint64((seed[1] + batch) & 0xFFFFFFFF)
+    k1_ray = np.uint64(seed[1] & 0xFFFFFFFF) if variant == "ray key without the batch" else k1   # (a ray's key is its photon's)
+    zeta = float(f32(P.zeta_min))
+    inv_pi32 = float(f32(1.0) / PI32)   # the float32 constant 1 / pi of the capped value
+    branches = {k: 0 for k in BRANCHES}
     pid = np.uint64(first_photon) + np.arange(n, dtype=np.uint64)
     lo, hi = pid & _MASK, (np.zeros(n, np.uint64) if drop_high_word else pid >> _S32)
 
     T = dict(fluxUp=np.zeros((ny, nx)), fluxDown=np.zeros((ny, nx)), volumeAbsorption=np.zeros((nz, ny, nx)),
              intensity=np.zeros((ncomp + 1, max(nd, 1), ny, nx)), intensityExcess=np.zeros((ncomp + 1, max(nd, 1))))
     Bd = {k: np.zeros_like(v) for k, v in T.items()}
-    cnt = {k: np.zeros(n, np.int64) for k in ("scatterings", "surfaceHits", "exitsTop", "roulette", "rngDraws")}
+    cnt = {k: np.zeros(n, np.int64) for k in ("scatterings", "surfaceHits", "exitsTop", "roulette", "rngDraws", "raysSkipped", "tracerCalls")}
     dep = {k: np.zeros(n) for k in ("fluxUp", "fluxDown", "volumeAbsorption", "intensity")}
     fragile, why = np.zeros(n, bool), {}
     fate, order, wfin = np.full(n, -1), np.zeros(n, np.int64), np.zeros(n)
@@ -222,7 +250,8 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False):
             exy = e_h + max(abs(u[0]), abs(u[1])) * ds
             crossed = column(idx, px + u[0] * s, py + u[1] * s, None, None)[4]
             steps = (nz - lay if up else lay + 1) + crossed + 1
-            _, _, ci, cj, _ = column(idx, px + u[0] * s, py + u[1] * s, exy + steps * EPS * (xs + 2 * dxmax), "ray column")
+            _, _, ci, cj, _ = column(idx, px + u[0] * s, py + u[1] * s, None, None)
+            e_col = exy + steps * EPS * (xs + 2 * dxmax)
             e_tau = (e_c + extmax * (crossed + 1) * EPS * (zs + 2 * dzmax)) / abs(u[2]) + 3 * EPS * steps * tauB
             if comp is None:
                 norm, e_norm = np.full(len(idx), 1.0 / np.pi), np.zeros(len(idx))
@@ -250,10 +279,67 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False):
             att = np.exp(-tauB)
             con = wgt * norm * att
             e_con = con * (e_w + 4 * EPS + 3 * ULP + 2 * EPS * tauB + np.expm1(e_tau)) + wgt * e_norm * att
+            counted = np.ones(len(idx), bool)      # does the ray reach a tally at all?  (its column is a decision only then)
+            capped = np.zeros(len(idx), bool)
+            if not P.rr_intensity:
+                cnt["tracerCalls"][idx] += 1
+            else:
+                # the ray's own block: same photon, the photon's block counter as the event leaves it (a component deviate that refilled
+                # next() has moved it on: philox.hpp), the direction number + 1 in the fourth word; key as the photon's
+                d4 = {"ray block ignores the direction": 1, "ray counter word d": d}.get(variant, d + 1)
+                hi_ray = np.zeros(len(idx), np.uint64) if variant == "ray block without the high word" else hi[idx]
+                q = philox(lo[idx], hi_ray, blk[idx] - 1, d4, k0, k1_ray)
+                u0, r2 = unit(q[0]), unit(q[0] if variant == "r2 from word 0" else q[1])
+                cnt["rngDraws"][idx] += 2
+                tau_free = -np.log(np.maximum(TINY, u0))
+                e_tf = 2 * ULP * tau_free
+                reaches = up or variant == "downward direction counts"   # only an exit through the top counts
+                pn = np.pi * norm
+                e_pn = np.pi * e_norm + 3 * EPS * pn                   # (the product's rounding, pi's and -- the surface -- 1 / pi's)
+                decide(idx, np.abs(pn - zeta), e_pn, "ray: small or large")
+                small = pn <= zeta
+                # small contribution: the roulette is decided before any trace; a lost ray is not traced
+                decide(idx[small], np.abs(r2 * zeta - pn)[small], (e_pn + EPS * r2 * zeta)[small], "ray: won")
+                won = small & (r2 * zeta <= pn)
+                lost = small & ~won
+                cnt["raysSkipped"][idx[lost]] += 1
+                cnt["tracerCalls"][idx[~lost]] += 1
+                if reaches:
+                    decide(idx[won], np.abs(tauB - tau_free)[won], (e_tau + e_tf)[won], "ray: free path")
+                won_top = won & (tauB <= tau_free) & reaches
+                # large contribution: a first leg up to tauMax, a second one from where that arrives up to the free path
+                large = ~small
+                tau_max = -np.log(zeta / np.maximum(TINY, pn))
+                e_tm = 2 * ULP * np.abs(tau_max) + ULP + 3 * EPS + e_norm / np.maximum(norm, TINY)
+                decide(idx[large], np.abs(tauB - tau_max)[large], (e_tau + e_tm)[large], "ray: tauMax")
+                first = large & (tauB <= tau_max)
+                second = large & ~first
+                cnt["tracerCalls"][idx[second]] += 1
+                rem = tauB if variant == "second leg from the event" else tauB - tau_max
+                e_rem = e_tau + e_tm + e_tf + 4 * EPS * zs * extmax / abs(u[2])   # (+ the arrival point's own rounding)
+                if reaches:
+                    decide(idx[second], np.abs(rem - tau_free)[second], e_rem[second], "ray: second leg")
+                second_top = second & (rem <= tau_free) & reaches
+                direct = first & reaches
+                capped = won_top | second_top
+                counted = direct | capped
+                cap_val = wgt * zeta * inv_pi32
+                con = np.where(direct, con, np.where(capped, cap_val, 0.0))
+                e_con = np.where(direct, e_con, np.where(capped, cap_val * (e_w + 3 * EPS), 0.0))
+                for k, m in (("small lost", lost), ("small won counted", won_top), ("small won ended inside", won & ~won_top & up),
+                             ("large first leg", direct), ("large through the bottom", first & (not up)), ("second leg counted", second_top),
+                             ("second leg ended inside", second & ~second_top & up), ("surface small", small & (comp is None)),
+                             ("surface large", large & (comp is None))):
+                    branches[k] += int(np.sum(m))
+            sel = np.nonzero(counted)[0]
+            if P.rr_intensity:
+                e_col = e_col + 4 * EPS * (xs + 2 * dxmax)   # (a second leg starts from a rounded arrival point)
+            column(idx[sel], (px + u[0] * s)[sel], (py + u[1] * s)[sel], e_col[sel], "ray column")
             if P.max_contrib is not None:
                 mc = float(f32(P.max_contrib))
                 decide(idx, np.abs(con - mc), e_con, "contribution limit")
                 over = con > mc
+                branches["capped above the limit"] += int(np.sum(over & capped))
                 np.add.at(T["intensityExcess"], (cidx[over], d), con[over] - mc)
                 np.add.at(Bd["intensityExcess"], (cidx[over], d), e_con[over])
                 e_con = np.where(over, 0.0, e_con)
@@ -289,6 +375,7 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False):
         idx = np.nonzero(alive)[0]
         dz = dvec[2, idx]
         assert np.all(dz != 0.0)
+        cnt["tracerCalls"][idx] += 1          # (one trace of the photon itself; the rays' are counted where they start)
         adz = np.abs(dz)
         up = dz > 0
         Cz = np.interp(z[idx], ze, cumz)
@@ -474,10 +561,17 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False):
         cmax = max(max(float(t.max()) for t in P.fwd + P.fwd_orig) / (4 * np.pi * float(np.abs(P.dirs[:, 2]).min())), 1 / np.pi)
         if P.max_contrib is not None:
             cmax = min(cmax, float(P.max_contrib))
+        if P.rr_intensity:
+            cmax = max(cmax, zeta / np.pi)
         caps["intensity"] = dep["intensity"] + (order + 1) * cmax
         caps["intensityExcess"] = caps["intensity"]
     per = dict(fate=fate, order=order, weight=wfin, fragile=fragile, why=why, **{"n_" + k: v for k, v in cnt.items()})
-    return Result(n, T, Bd, counters, per, caps)
+    exact_zero = {}
+    if nd and P.rr_intensity:   # only an exit through the top counts: no float32 decision stands between a downward direction and 0
+        for k in ("intensity", "intensityExcess"):
+            exact_zero[k] = np.zeros(T[k].shape, bool)
+            exact_zero[k][:, P.dirs[:, 2] < 0] = True
+    return Result(n, T, Bd, counters, per, caps, branches, exact_zero)
 
 
 def _rowwise(rows, theta):
@@ -493,16 +587,17 @@ def _rowwise(rows, theta):
     return np.where(inside, (1.0 - fr) * rows[i, kk - 1] + fr * rows[i, kk], rows[i, nf - 1]), pos
 
 
-def clean_range(model):
-    """(first, count) of the longest run of consecutive photons of a run none of which is fragile: launched on its own, that range
-    must give the model's counters exactly and its tallies within the float32 bound alone"""
-    edges = np.concatenate([[-1], np.nonzero(model.per_photon["fragile"])[0], [model.n]])
+def clean_range(model, start=0):
+    """(first, count) of the longest run of consecutive photons of a run (from its photon `start` on) none of which is fragile: launched
+    on its own, that range must give the model's counters exactly and its tallies within the float32 bound alone"""
+    frag = np.nonzero(model.per_photon["fragile"])[0]
+    edges = np.concatenate([[start - 1], frag[frag >= start], [model.n]])
     k = int(np.argmax(np.diff(edges)))
     return int(edges[k] + 1), int(edges[k + 1] - edges[k] - 1)
 
 
 COUNTERS_EXACT = ("photons", "dropped")
-COUNTERS_FRAGILE = ("scatterings", "surfaceHits", "exitsTop", "roulette", "rngDraws")
+COUNTERS_FRAGILE = ("scatterings", "surfaceHits", "exitsTop", "roulette", "rngDraws", "raysSkipped", "tracerCalls")
 
 
 def compare_counters(models, counters, names=COUNTERS_EXACT + COUNTERS_FRAGILE):
@@ -525,6 +620,9 @@ def compare(model, tallies, counters, counter_names=COUNTERS_EXACT + COUNTERS_FR
         got = np.asarray(tallies[k], f64).reshape(want.shape)
         slack = float(model.caps[k][frag].sum())
         tol = model.bounds[k] + slack
+        if k in model.exact_zero:
+            assert not want[model.exact_zero[k]].any()
+            tol = np.where(model.exact_zero[k], 0.0, tol)
         diff = np.abs(got - want)
         with np.errstate(divide="ignore", invalid="ignore"):
             ratio = np.where(diff > 0, diff / np.where(tol > 0, tol, TINY), 0.0)
@@ -580,6 +678,22 @@ def _cases():
                                         [(0.85, 0.6), (0.0,)], _layers(8, 6.0), albedo=0.3, mus=[1.0, 0.8, -0.7], phis=[0.0, 120.0, 250.0], n=10_000)
     C["h hybrid"] = _case(e8, on * f32(0.95), on * 1, [(0.95,)], _layers(8, 6.0), albedo=0.3, mus=[0.9], phis=[10.0], hybrid=1, n=10_000)
     C["h limit"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), albedo=0.3, mus=[0.9, 0.4], phis=[10.0, 200.0], limit=0.5, n=10_000)
+    # ... and with the local estimate's own roulette (make_ray's tail, the service phase's stages): the same media and directions
+    rr = dict(albedo=0.3, rr_intensity=True, n=10_000)
+    C["r one up"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), mus=[0.8], phis=[30.0], **rr)
+    C["r one down"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), mus=[-0.6], phis=[200.0], **rr)
+    C["r three"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), mus=[1.0, 0.7, -0.8], phis=[0.0, 120.0, 250.0], **rr)
+    C["r three two components"] = _case([e8, gas], [on * f32(0.98), np.full(8, f32(0.6))], [on * np.array([1, 0, 2, 1, 0, 0, 2, 1]), np.ones(8)],
+                                        [(0.85, 0.6), (0.0,)], _layers(8, 6.0), mus=[1.0, 0.8, -0.7], phis=[0.0, 120.0, 250.0], **rr)
+    C["r hybrid"] = _case(e8, on * f32(0.95), on * 1, [(0.95,)], _layers(8, 6.0), mus=[0.9], phis=[10.0], hybrid=1, **rr)
+    # (a limit below zetaMin / pi = 0.095: capped values of the heavier photons exceed it, and so does every large contribution)
+    C["r limit"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), mus=[0.9, 0.4], phis=[10.0, 200.0], limit=0.08, **rr)
+    # (zetaMin above 1: the surface's pi norm = 1 is a small contribution)
+    C["r zeta"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), mus=[0.6, -0.9], phis=[40.0, 300.0], zeta_min=1.5, **rr)
+    # (columns a hundred times as wide: hardly a photon or a ray comes within its own error of a column's side, so the WHOLE case allows
+    # next to nothing beyond the float32 bound -- the case on which the controls of tests/test_stream_model_cpu.py are seen on a whole case)
+    C["r wide"] = _case(e8, on * f32(0.95), on * 1, [(0.85,)], _layers(8, 6.0), xe=f32(100.0) * _XE, ye=f32(100.0) * _YE,
+                        mus=[1.0, 0.4, -0.8], phis=[0.0, 120.0, 250.0], limit=0.08, **rr)
     return C
 
 
@@ -587,6 +701,10 @@ CASES = _cases()
 SUN = (0.7, 25.0)
 SEED = (23, 4)
 FRAGILE_CAP = 0.005
+# A fused launch hands out every batch's photons from 0 on, so its run without a fragile photon has to begin there: with this key the
+# first FUSED_CLEAN_N photons of batches 0, 1 and 2 (key (seed0, seed1 + batch)) of `r one up` and `r three` hold none -- the first ones
+# are photons 765, 787 and 1335 (found by running the model over first key words 1 .. 120; asserted in tests/test_stream_model_cpu.py)
+FUSED_CLEAN_SEED, FUSED_CLEAN_N, FUSED_CLEAN_CASES = (3, 4), 750, ("r one up", "r three")
 
 
 def problem(case, inverse, forward=None, forward_orig=None, dirs=None):
@@ -594,7 +712,8 @@ def problem(case, inverse, forward=None, forward_orig=None, dirs=None):
     p = case["params"]
     return Problem(case["xe"], case["ye"], case["ze"], case["ext"], case["ssa"], case["pfi"], inverse, mu0=SUN[0], azimuth=SUN[1],
                    albedo=p["albedo"], roulette=p.get("roulette", True), dirs=dirs, fwd=forward, fwd_orig=forward_orig,
-                   hybrid=bool(p.get("hybrid")), orders_orig=int(p.get("hybrid", 0)), max_contrib=p.get("limit"))
+                   hybrid=bool(p.get("hybrid")), orders_orig=int(p.get("hybrid", 0)), max_contrib=p.get("limit"),
+                   rr_intensity=bool(p.get("rr_intensity", False)), zeta_min=p.get("zeta_min", 0.3))
 
 
 def case_directions(case):
@@ -620,6 +739,14 @@ FRAGILE_SHARES = {
     'h three two components': 0.0047,
     'h hybrid': 0.0032,
     'h limit': 0.0031,
+    'r one up': 0.0021,
+    'r one down': 0.0014,
+    'r three': 0.0023,
+    'r three two components': 0.0023,
+    'r hybrid': 0.0024,
+    'r limit': 0.0021,
+    'r zeta': 0.0015,
+    'r wide': 0.001,
 }
 
 if __name__ == "__main__":
@@ -628,3 +755,6 @@ if __name__ == "__main__":
     for name in CASES:
         r = model_for(name)
         print(f"{name:26s} n {r.n:6d} fragile {r.fragile_share:.5f} {r.per_photon['why']} mean order {r.per_photon['order'].mean():.2f}")
+        if CASES[name]["params"].get("rr_intensity"):
+            first, count = clean_range(r)
+            print(f"{'':26s} rays {r.branches}\n{'':26s} clean run {first} + {count}: {model_for(name, first=first, n=count).branches}")

@@ -8,9 +8,15 @@ both shown without a GPU:
   * the share of fragile photons of every shared case, asserted below 0.5 % (a condition on the inputs);
   * energy: up + absorbed + (1 - albedo) down = 1 per photon without roulette;
   * the controls: a model that swaps first() and second(), takes the azimuth from first(), interpolates the inverse table one
-    interval on, or drops the high word of the photon number must FAIL the comparison the GPU module makes, at the shared cases' sizes.
-    (The fourth control the issue names -- a ray block that ignores the direction number -- has nothing to act on: that block is drawn
-    only by the local estimate's own roulette, which the model leaves to the replay and oracle tests.)"""
+    interval on, or drops the high word of the photon number must FAIL the comparison the GPU module makes, at the shared cases' sizes;
+  * the local estimate's own roulette (the `r ...` cases): the model with it against the solver and the oracle (a downward direction
+    exactly 0 on both sides); every branch a ray can take holds 200 rays over the cases and 20 inside their runs without a fragile
+    photon; and its controls -- a ray block that ignores the direction number, d instead of d + 1 in the fourth counter word, r2 from
+    word 0, a fused ray key without the batch, a second leg restarted at the event, a downward direction that counts -- FAIL the
+    comparison on the run without fragile photons, and on a whole case where one can see them at all (RAY_CONTROLS says which, and why
+    a mere re-draw of the rays' deviates is a thousandth of what a whole case allows its fragile photons).  A fused launch starts at
+    photon 0: the key S.FUSED_CLEAN_SEED, whose three batches begin with 750 photons none of them fragile, is where the key without
+    the batch fails for fused launches; a ray block without the photon's high word fails on the clean window beyond 2^32."""
 import functools
 
 import numpy as np
@@ -48,8 +54,8 @@ def case_problem(name):
 
 
 @functools.lru_cache(maxsize=None)
-def model_for(name, seed=S.SEED, first=0, n=None, variant=None, drop=False):
-    return S.run(case_problem(name), seed, first, n or S.CASES[name]["n"], variant=variant, drop_high_word=drop)
+def model_for(name, seed=S.SEED, first=0, n=None, variant=None, drop=False, batch=0):
+    return S.run(case_problem(name), seed, first, n or S.CASES[name]["n"], variant=variant, drop_high_word=drop, batch=batch)
 
 
 # ---- Philox ----------------------------------------------------------------------------------------------------------------------
@@ -77,14 +83,14 @@ def test_deviate_mapping_reaches_both_ends():
 
 
 # ---- against the solver ---------------------------------------------------------------------------------------------------------
-def _slab(tau, omega, albedo, moments, dirs=None, n_table=10001):
+def _slab(tau, omega, albedo, moments, dirs=None, n_table=10001, rr_intensity=False):
     from tools import cases
 
     d = cases.plane_parallel(optical_depth=tau, ssa=omega, nx=2, ny=2, nlayers=3)
     t = M.PhaseFunctionTable([M.henyey_greenstein(0.85, moments)])
     fwd = [t.forward_table(n_table)] if dirs is not None else None
     return S.Problem(d["xe"], d["ye"], d["ze"], d["ext"][:, 0, 0], d["ssa"][:, 0, 0], d["pf"][:, 0, 0], [t.inverse_table(n_table)],
-                     mu0=0.5, azimuth=0.0, albedo=albedo, roulette=True, dirs=dirs, fwd=fwd)
+                     mu0=0.5, azimuth=0.0, albedo=albedo, roulette=True, dirs=dirs, fwd=fwd, rr_intensity=rr_intensity)
 
 
 def _means(results, key, axes):
@@ -108,20 +114,33 @@ def test_model_fluxes_against_adding_doubling(tau, omega, albedo):
         assert abs(got - want[key]) <= 4.0 * se + SOLVER, (key, tau, omega, albedo, got, want[key], se)
 
 
-@pytest.mark.parametrize("tau,omega,albedo", [(1.0, 1.0, 0.0), (10.0, 0.9, 0.5), (0.1, 1.0, 0.5)])
-def test_model_radiances_against_adding_doubling(tau, omega, albedo):
+def _radiances_against_adding_doubling(tau, omega, albedo, rr_intensity):
     from tests.plane_parallel_solver import solve
     from tests.test_plane_parallel import G, MOMENTS_RADIANCE, MU0, VIEW_MUS, VIEW_PHIS
 
     n, nb = (60_000 if tau < 5 else 20_000), 10
     dirs = np.array([S.direction(m, p) for m, p in zip(VIEW_MUS, VIEW_PHIS)])
-    P = _slab(tau, omega, albedo, MOMENTS_RADIANCE, dirs)
+    P = _slab(tau, omega, albedo, MOMENTS_RADIANCE, dirs, rr_intensity=rr_intensity)
     rs = [S.run(P, (10, b), 0, n) for b in range(1, nb + 1)]
     want = solve(tau, omega, G, MU0, albedo=albedo, radiance_mus=VIEW_MUS, radiance_dphis_deg=VIEW_PHIS)
     per = np.array([r.tallies["intensity"].sum(axis=(0, 2, 3)) / r.n for r in rs])   # (mean over columns of sum / photons per column)
     got, se = per.mean(0), per.std(0, ddof=1) / np.sqrt(nb)
     for k in range(len(VIEW_MUS)):
         assert abs(got[k] - want["intensity"][k]) <= 4.0 * se[k] + SOLVER, (k, tau, omega, albedo, got[k], want["intensity"][k], se[k])
+
+
+RADIANCE_SLABS = [(1.0, 1.0, 0.0), (10.0, 0.9, 0.5), (0.1, 1.0, 0.5)]
+
+
+@pytest.mark.parametrize("tau,omega,albedo", RADIANCE_SLABS)
+def test_model_radiances_against_adding_doubling(tau, omega, albedo):
+    _radiances_against_adding_doubling(tau, omega, albedo, False)
+
+
+@pytest.mark.parametrize("tau,omega,albedo", RADIANCE_SLABS)
+def test_model_radiances_with_the_roulette_against_adding_doubling(tau, omega, albedo):
+    """the local estimate's roulette is unbiased: the solver's answer is the same, the rule is the same"""
+    _radiances_against_adding_doubling(tau, omega, albedo, True)
 
 
 # ---- against the oracle ---------------------------------------------------------------------------------------------------------
@@ -151,6 +170,37 @@ def test_model_against_the_oracle_two_components_surface_radiance():
         assert abs(a.mean() - m.mean()) <= 4.0 * se, (key, a.mean(), m.mean(), se)
 
 
+def test_model_against_the_oracle_with_the_roulette_up_and_down():
+    """the same with the local estimate's roulette on both sides, an upward and a downward direction: the downward one's field is
+    exactly 0 on both sides (only an exit through the top counts), the upward one's agrees within the two samples' errors"""
+    from oracle import pyoracle as O
+
+    O.build()
+    name = "r three two components"
+    c, P = S.CASES[name], case_problem(name)
+    nz, ny, nx = len(c["ze"]) - 1, len(c["ye"]) - 1, len(c["xe"]) - 1
+    full = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a)[:, :, None, None], a.shape + (ny, nx)))   # noqa: E731
+    o = O.Integrator(c["xe"], c["ye"], c["ze"], full(c["ext"]).astype(np.float32), full(c["ssa"]).astype(np.float32),
+                     full(c["pfi"]).astype(np.int32), P.inv, P.fwd, P.fwd_orig)
+    p = c["params"]
+    assert p["mus"][1] > 0 > p["mus"][2]
+    o.specify(surfaceAlbedo=p["albedo"], intensityMus=p["mus"][1:], intensityPhis=p["phis"][1:], useRRForIntensity=1, zetaMin=P.zeta_min)
+    P.dirs = P.dirs[1:]
+    n, nb = 20_000, 10
+    ors, ms = [], []
+    for b in range(1, nb + 1):
+        rng = O.RandomNumberSequence([10, b])
+        ors.append(o.compute(rng, *O.photons_directional(rng, *S.SUN, n)))
+        ms.append(S.run(P, (10, b), 0, n))
+    assert all(not r["intensity"][1].any() for r in ors) and all(not r.tallies["intensity"][:, 1].any() for r in ms)
+    assert sum(r.branches["second leg counted"] for r in ms) > 1000 and sum(r.branches["small won counted"] for r in ms) > 1000
+    for key in ("fluxUp", "fluxDown", "fluxAbsorbed", "intensity"):
+        a = np.array([(r[key][0] if key == "intensity" else r[key]).astype(np.float64).mean() for r in ors])
+        m = np.array([(r.tallies[key][:, 0].sum(0) if key == "intensity" else r.tallies[key]).sum() / r.n for r in ms])
+        se = np.sqrt(a.var(ddof=1) / nb + m.var(ddof=1) / nb)
+        assert a.mean() > 0 and abs(a.mean() - m.mean()) <= 4.0 * se, (key, a.mean(), m.mean(), se)
+
+
 # ---- the inputs: few fragile photons --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(S.CASES))
 def test_fragile_share_of_the_shared_cases(name):
@@ -161,7 +211,7 @@ def test_fragile_share_of_the_shared_cases(name):
 
 
 @pytest.mark.parametrize("first", [2 ** 32 - 700, 2 ** 33 + 5])
-@pytest.mark.parametrize("name", ["a common", "h three"])
+@pytest.mark.parametrize("name", ["a common", "h three", "r one up", "r three"])
 def test_fragile_share_across_two_to_the_32(name, first):
     assert model_for(name, first=first, n=1500).fragile_share <= S.FRAGILE_CAP
 
@@ -214,8 +264,128 @@ def test_the_next_table_interval_fails_the_comparison(name):
     assert _fails(clean_model(name), clean_model(name, S.VARIANTS[2])), name
 
 
-@pytest.mark.parametrize("name", ["a common", "h three"])
+@pytest.mark.parametrize("name", ["a common", "h three", "r three"])
 @pytest.mark.parametrize("first", [2 ** 32 - 700, 2 ** 33 + 5])
 def test_a_dropped_high_word_fails_the_comparison(name, first):
     base = model_for(name, first=first, n=1500)
     assert _fails(base, model_for(name, first=first, n=1500, drop=True)), (name, first)
+
+
+# ---- the local estimate's own roulette ------------------------------------------------------------------------------------------
+RR_CASES = [k for k, c in S.CASES.items() if c["params"].get("rr_intensity")]
+
+
+def test_the_roulette_cases_are_the_ones_asked_for():
+    p = {k: S.CASES[k]["params"] for k in RR_CASES}
+    nd = sorted(len(q["mus"]) for q in p.values())
+    assert nd.count(1) >= 3 and nd.count(3) >= 2 and all(S.CASES[k]["n"] == 10_000 for k in RR_CASES)
+    assert any(len(q["mus"]) == 1 and q["mus"][0] < 0 for q in p.values()) and any(q.get("hybrid") == 1 for q in p.values())
+    assert any(len(S.CASES[k]["gs"]) == 2 and len(q["mus"]) == 3 and min(q["mus"]) < 0 for k, q in p.items())
+    assert any("limit" in q and len(q["mus"]) == 2 and 0.4 in q["mus"] for q in p.values())
+    assert any(q.get("zeta_min", 0.3) >= 1.0 for q in p.values()) and all(q.get("rr_intensity") is None for k, q in
+                                                                         ((k, c["params"]) for k, c in S.CASES.items() if k not in RR_CASES))
+
+
+def test_every_branch_of_the_roulette_is_taken():
+    """over the roulette's cases together every branch holds at least 200 rays, and at least 20 inside the cases' longest runs without a
+    fragile photon -- where nothing but the float32 bound is allowed (a surface event is small only with zetaMin >= 1, large otherwise:
+    `each stage it can take`)"""
+    whole = {b: sum(model_for(k).branches[b] for k in RR_CASES) for b in S.BRANCHES}
+    clean = {b: sum(clean_model(k).branches[b] for k in RR_CASES) for b in S.BRANCHES}
+    assert min(whole.values()) >= 200, whole
+    assert min(clean.values()) >= 20, clean
+    # (the rays the model skips are the ones it counts as lost, and a flux case or a case without the roulette skips none)
+    assert all(model_for(k).counters["raysSkipped"] == model_for(k).branches["small lost"] > 0 for k in RR_CASES)
+    assert all(model_for(k).counters["raysSkipped"] == 0 for k in S.CASES if k not in RR_CASES)
+
+
+def test_tracer_calls_without_the_roulette_are_the_photons_traces_and_one_per_ray():
+    for name in ("a common", "h three"):
+        c = model_for(name).counters
+        nd = len(S.CASES[name]["params"].get("mus", ()))
+        rays = nd * (c["scatterings"] + c["surfaceHits"])   # (every event makes its rays: the albedo is above 0)
+        assert c["tracerCalls"] == c["scatterings"] + c["surfaceHits"] + c["exitsTop"] + rays
+
+
+# (variant, case, is it seen on the WHOLE case too?)  On a whole case a fragile photon may carry up to the largest contribution there is
+# per ray into any entry, and the counters may differ by the fragile photons' own counts.  A control that only RE-DRAWS the rays' deviates
+# -- the fourth counter word d instead of d + 1, a key without the batch: the same distribution from other blocks -- changes the counters
+# by a fluctuation of some sqrt(rays), which at 10^4 photons is about what the fragile photons' own counts allow (measured: `r wide` missed
+# the word d by 64 skipped rays against 80 allowed; the key without the batch 14178 against 14097, 46813 against 46783 skipped rays, inside
+# the allowance), and the tally entries by about a THOUSANDTH of the whole case's tolerance (measured: 0.001 to 0.002 of it; `r wide`
+# 0.3 to 0.37): a whole case cannot see a re-draw.  The run without fragile photons, where the float32 bound alone is allowed, sees every
+# one of them, on every case -- the device runs that range of every case, and a fused launch, which always starts at photon 0, runs
+# S.FUSED_CLEAN_N photons a batch of a key for which the three batches hold no fragile photon (below).  The other controls change WHAT is
+# computed and are seen on the whole case `r wide` as well, whose wide columns and contribution limit leave the fragile photons little
+# to carry; a downward direction that counts is seen on every whole case (those entries are exactly 0).
+RAY_CONTROLS = [("ray block ignores the direction", "r wide", True), ("ray block ignores the direction", "r three", False),
+                ("ray block ignores the direction", "r three two components", False),
+                ("ray counter word d", "r one up", False), ("ray counter word d", "r three", False), ("ray counter word d", "r wide", False),
+                ("r2 from word 0", "r wide", True), ("r2 from word 0", "r zeta", True), ("r2 from word 0", "r one up", False),
+                ("second leg from the event", "r wide", True), ("second leg from the event", "r one up", False),
+                ("second leg from the event", "r limit", False), ("second leg from the event", "r three two components", False),
+                ("downward direction counts", "r one down", True), ("downward direction counts", "r three", True),
+                ("downward direction counts", "r three two components", True), ("downward direction counts", "r zeta", True),
+                ("downward direction counts", "r wide", True)]
+
+
+@pytest.mark.parametrize("variant,name,whole", RAY_CONTROLS)
+def test_a_mistake_in_the_rays_roulette_fails_the_comparison(variant, name, whole):
+    """a ray block that ignores the direction number, or has d instead of d + 1 in its fourth counter word (direction 0: the event's own
+    block), r2 from the free path's word, a second leg restarted at the event, a downward direction that counts: each fails the
+    comparison the GPU module makes on the case's run without fragile photons, and on the whole case where RAY_CONTROLS says so"""
+    base = model_for(name)
+    assert S.compare(base, base.tallies, base.counters)[0] == []
+    assert _fails(clean_model(name), clean_model(name, variant)), (name, variant)
+    if whole:
+        assert _fails(base, model_for(name, variant=variant)), (name, variant)
+
+
+@pytest.mark.parametrize("name", ["r one up", "r three", "r wide"])
+def test_a_ray_key_without_the_batch_fails_the_comparison(name):
+    """fused launches: batch b's rays keyed as batch 0's (every batch would reuse the same ray deviates).  A re-draw: seen on the run
+    without fragile photons (see RAY_CONTROLS)"""
+    variant = "ray key without the batch"
+    for b in (1, 2):
+        base = model_for(name, batch=b)
+        assert base.counters == model_for(name, seed=(S.SEED[0], S.SEED[1] + b)).counters   # (batch b of a fused launch: the key's second word + b)
+        first, count = S.clean_range(base)
+        assert count >= 500
+        assert _fails(model_for(name, first=first, n=count, batch=b), model_for(name, first=first, n=count, variant=variant, batch=b)), (name, b)
+    assert not _fails(model_for(name), model_for(name, variant=variant))   # (batch 0: nothing to tell apart)
+
+
+@pytest.mark.parametrize("name", S.FUSED_CLEAN_CASES)
+def test_fused_batches_without_a_fragile_photon_see_the_ray_key(name):
+    """what the GPU module's fused launch without fragile photons compares: batches 0, 1, 2 of S.FUSED_CLEAN_SEED, photons from 0, none of
+    them fragile -- and on exactly those runs a ray key without the batch (a ring record whose batch word is lost does the same) fails"""
+    for b in range(3):
+        base = model_for(name, seed=S.FUSED_CLEAN_SEED, n=S.FUSED_CLEAN_N, batch=b)
+        assert not base.per_photon["fragile"].any(), (name, b, np.nonzero(base.per_photon["fragile"])[0])
+        assert min(base.branches[k] for k in ("small lost", "small won counted", "large first leg", "second leg counted")) >= 20, base.branches
+        alone = model_for(name, seed=(S.FUSED_CLEAN_SEED[0], S.FUSED_CLEAN_SEED[1] + b), n=S.FUSED_CLEAN_N)
+        assert base.counters == alone.counters and all(np.array_equal(base.tallies[k], alone.tallies[k]) for k in base.tallies)
+        other = model_for(name, seed=S.FUSED_CLEAN_SEED, n=S.FUSED_CLEAN_N, batch=b, variant="ray key without the batch")
+        assert _fails(base, other) == (b > 0), (name, b)
+        if b > 0:   # (... by the tallies alone, which is what the device is held to per batch: its ray counters go over the group)
+            assert S.compare(base, other.tallies, other.counters, S.COUNTERS_EXACT)[0] != [], (name, b)
+
+
+def beyond_two_to_the_32(name, first, n=1500):
+    """(first photon, count) of the longest run without a fragile photon among the photons of first .. first + n - 1 whose number has a
+    high word"""
+    base = model_for(name, first=first, n=n)
+    at, count = S.clean_range(base, start=max(0, 2 ** 32 - first))
+    return first + at, count
+
+
+@pytest.mark.parametrize("first", [2 ** 32 - 700, 2 ** 33 + 5])
+@pytest.mark.parametrize("name", ["r one up", "r three"])
+def test_a_ray_block_without_the_high_word_fails_the_comparison(name, first):
+    """the ray's block alone keyed without the photon number's high word (the ring record's word, make_ray's second argument): a re-draw of
+    the rays' deviates, seen on the run without fragile photons beyond 2^32 that the GPU module launches"""
+    at, count = beyond_two_to_the_32(name, first)
+    assert at >= 2 ** 32 and count >= 150, (at, count)   # (some hundreds of rays of every kind)
+    clean = model_for(name, first=at, n=count)
+    assert not clean.per_photon["fragile"].any()
+    assert _fails(clean, model_for(name, first=at, n=count, variant="ray block without the high word")), (name, first)
