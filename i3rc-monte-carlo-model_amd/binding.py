@@ -30,6 +30,7 @@ SYMBOLS = [
     "i3rc_hip_set_batch_fusion", "i3rc_hip_select_grid_place", "i3rc_hip_has_column_records", "i3rc_hip_column_records", "i3rc_hip_column_records_base", "i3rc_hip_lds_plan", "i3rc_hip_lds_plan_words", "i3rc_hip_set_lds_tallies", "i3rc_hip_last_kernel_name", "i3rc_hip_last_plan", "i3rc_hip_timed_launch_count", "i3rc_hip_philox_blocks", "i3rc_hip_arith_check", "i3rc_hip_find_index", "i3rc_hip_surface_reflectance", "i3rc_hip_device_count", "i3rc_hip_version",
     "i3rc_hip_set_level_fluxes", "i3rc_hip_get_level_flux_layout", "i3rc_hip_normalise_level_fluxes",
     "i3rc_hip_set_actinic_flux", "i3rc_hip_get_actinic_flux_layout", "i3rc_hip_normalise_actinic_flux",
+    "i3rc_hip_set_path_lengths", "i3rc_hip_get_path_length_layout", "i3rc_hip_normalise_path_lengths",
     "i3rc_hip_problem_facts", "i3rc_hip_plan_launch",
     "i3rc_hip_run_batches_diagnostic_moments", "i3rc_hip_get_diagnostic_moments_layout", "i3rc_hip_diagnostic_moments_layout_words",
 ]
@@ -62,7 +63,7 @@ class MomentsLayout(C.Structure):
 
 # i3rc_diagnostic_moments_layout; without its first word, the words of i3rc_hip_diagnostic_moments_layout_words in order
 DIAGNOSTIC_MOMENTS_NAMES = ["levelFluxUp", "levelFluxDown", "meanLevelFluxUp", "meanLevelFluxDown", "actinicFlux", "meanActinicFlux", "total"]
-EXTRA_KINDS = {"none": 0, "levels": 1, "tracks": 2}
+EXTRA_KINDS = {"none": 0, "levels": 1, "tracks": 2, "paths": 3}   # (csrc/tally_block.hpp, ExtraTally; path lengths have no batch moments)
 
 
 class DiagnosticMomentsLayout(C.Structure):
@@ -92,7 +93,7 @@ SETUP_NAMES = ["nDir", "inverseTables", "forwardTables", "inverseSteps", "invers
                "surfaceNy", "surfaceSet", "extra", "kernelVariant", "gridPlace", "ldsTalliesOn"]
 ENV_DEFAULTS = {"I3RC_COLUMNS": 1, "I3RC_LDS_TALLIES": 1, "I3RC_TABLE_LDS": 1, "I3RC_TABLE_LDS_PLACES": 11, "I3RC_FUSED_TABLE_LDS_PLACES": 11,
                 "I3RC_DIRECT": 1, "I3RC_CELL_RECORDS": 1}
-STREAM_KINDS = {"plain": 0, "fused": 1, "replay": 2, "level": 3, "track": 4}
+STREAM_KINDS = {"plain": 0, "fused": 1, "replay": 2, "level": 3, "track": 4, "path": 5}
 PLAN_EXTRA_NAMES = ["ldsEstimate", "rayQueueCap", "threads"]
 
 
@@ -221,6 +222,10 @@ def load():
         L.i3rc_hip_set_actinic_flux.argtypes = [H, C.c_int]
         L.i3rc_hip_get_actinic_flux_layout.argtypes = [H, lp, lp]
         L.i3rc_hip_normalise_actinic_flux.argtypes = [H, dp, fp]
+    if hasattr(L, "i3rc_hip_set_path_lengths"):   # (likewise)
+        L.i3rc_hip_set_path_lengths.argtypes = [H, C.c_int]
+        L.i3rc_hip_get_path_length_layout.argtypes = [H, lp, lp, lp, lp, lp]
+        L.i3rc_hip_normalise_path_lengths.argtypes = [H, dp, fp, fp, fp, fp]
     if hasattr(L, "i3rc_hip_plan_launch"):   # (likewise)
         L.i3rc_hip_problem_facts.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp, ip, ip, ip, C.c_int]
         L.i3rc_hip_plan_launch.argtypes = [ip, ip, ip, ip, ip, C.c_int, C.c_char_p, C.c_int]

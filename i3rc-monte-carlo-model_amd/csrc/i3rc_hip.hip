@@ -225,9 +225,10 @@ struct ExtraWords { const char *setter, *noun, *are, *need, *them, *their, *poss
 static const ExtraWords kExtraWords[] = {
     {},
     {"i3rc_hip_set_level_fluxes", "level fluxes", "are", "need", "them", "their", "the level fluxes'"},
-    {"i3rc_hip_set_actinic_flux", "the actinic flux", "is", "needs", "it", "its", "the actinic flux's"}};
+    {"i3rc_hip_set_actinic_flux", "the actinic flux", "is", "needs", "it", "its", "the actinic flux's"},
+    {"i3rc_hip_set_path_lengths", "path lengths", "are", "need", "them", "their", "the path lengths'"}};
 
-// Switches one kind of the optional diagnostic tally on or off (i3rc_hip_set_level_fluxes, i3rc_hip_set_actinic_flux).
+// Switches one kind of the optional diagnostic tally on or off (i3rc_hip_set_level_fluxes, i3rc_hip_set_actinic_flux, i3rc_hip_set_path_lengths).
 static int set_extra_tally(i3rc_hip_integrator *h, ExtraTally kind, bool on) {
   if (!h) return 1;
   drop_lookahead(h);
@@ -592,6 +593,18 @@ int i3rc_hip_get_actinic_flux_layout(const i3rc_hip_integrator *h, int64_t *offs
   return 0;
 }
 
+int i3rc_hip_set_path_lengths(i3rc_hip_integrator *h, int on) { return set_extra_tally(h, EXTRA_PATHS, on != 0); }
+
+int i3rc_hip_get_path_length_layout(const i3rc_hip_integrator *h, int64_t *up1, int64_t *up2, int64_t *down1, int64_t *down2, int64_t *total) {
+  if (!h) return 1;
+  if (up1) *up1 = h->view.pathUp1;
+  if (up2) *up2 = h->view.pathUp2;
+  if (down1) *down1 = h->view.pathDown1;
+  if (down2) *down2 = h->view.pathDown2;
+  if (total) *total = h->layout.total;
+  return 0;
+}
+
 /* Tunables for experiments (not part of the reference API): event-phase ballot threshold, blocks per CU. */
 int i3rc_hip_set_tuning(i3rc_hip_integrator *h, int evThreshold, int blocksPerCU) {
   if (!h) return 1;
@@ -894,6 +907,7 @@ template <class Rng>
 constexpr const char *rng_name() {
   if constexpr (Rng::kExtra == EXTRA_LEVELS) return "PhiloxLevelStream";
   else if constexpr (Rng::kExtra == EXTRA_TRACKS) return "PhiloxTrackStream";
+  else if constexpr (Rng::kExtra == EXTRA_PATHS) return "PhiloxPathStream";
   else if constexpr (Rng::kReplay) return "ReplayStream";
   else if constexpr (Rng::kBatched) return "PhiloxBatchStream";
   else return "PhiloxStream";
@@ -955,6 +969,11 @@ const std::vector<KernelEntry> &stream_kernels() {
 // An extra tally block is filled by the general flux kernel of a plain launch, traced: what a launch must be while one is switched on.
 // Called before a launch touches anything; `who` names the entry point in the error text, `batches` says that it runs a loop of
 // batches (fused or announced), which no such kernel serves.
+// (path lengths have no batch statistics: the diagnostic moments' layout has no slot for them)
+std::string no_path_moments_text() {
+  return "path lengths have no batch statistics; the diagnostic moments' layout has no slot for them (switch them off, or call "
+         "i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)";
+}
 int extra_tally_refused(i3rc_hip_integrator *h, const char *who, bool batches) {
   if (h->extra == EXTRA_NONE) return 0;
   const ExtraWords &w = kExtraWords[h->extra];
@@ -1526,6 +1545,7 @@ int begin_batch_loop(i3rc_hip_integrator *h, const std::string &who, bool argsOk
   if (diagnostic && h->extra == EXTRA_NONE)
     return h->fail(who + ": no diagnostic tally is switched on (i3rc_hip_set_level_fluxes or i3rc_hip_set_actinic_flux first; "
                    "i3rc_hip_run_batches_moments serves a loop without one)");
+  if (diagnostic && h->extra == EXTRA_PATHS) return h->fail(who + ": " + no_path_moments_text());
   if (src->kind != 0) return h->fail(who + ": Directional photon streams only (explicit streams differ from batch to batch)");
   if (nPhotons <= 0) return h->fail((diagnostic ? who + ": " : "") + "setIllumination: must ask for non-negative number of photons.");
   if (extra_tally_refused(h, who.c_str(), !diagnostic)) return 1;
@@ -1641,6 +1661,7 @@ int i3rc_hip_diagnostic_moments_layout_words(int kind, int nx, int ny, int nz, i
 
 int i3rc_hip_get_diagnostic_moments_layout(const i3rc_hip_integrator *h, i3rc_diagnostic_moments_layout *layout) {
   if (!h || !layout) return 1;
+  if (h->extra == EXTRA_PATHS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_get_diagnostic_moments_layout: " + no_path_moments_text());
   const ExtraMomentsLayout L = extra_moments_layout(h->extra, h->nx, h->ny, h->nz);
   layout->kind = (int64_t)h->extra;
   layout->levelFluxUp = L.levelFluxUp; layout->levelFluxDown = L.levelFluxDown; layout->meanLevelFluxUp = L.meanLevelFluxUp;
@@ -1774,7 +1795,11 @@ int i3rc_hip_run_replay(i3rc_hip_integrator *h, int64_t nPhotons, const i3rc_sou
                         int32_t *fateOrder, int32_t *drawsUsed) {
   if (!h) return 1;
   if (!src || !randoms || !drawStart || nPhotons <= 0) return h->fail("i3rc_hip_run_replay: bad arguments");
-  if (h->extra == EXTRA_TRACKS) return h->fail("i3rc_hip_run_replay: the actinic flux is tallied by the production stream's kernels only; the replay build has no such kernel (switch it off)");
+  if (h->extra == EXTRA_TRACKS || h->extra == EXTRA_PATHS) {
+    const ExtraWords &w = kExtraWords[h->extra];
+    return h->fail(std::string("i3rc_hip_run_replay: ") + w.noun + " " + w.are + " tallied by the production stream's kernels only; the replay build has no such kernel (switch " +
+                   w.them + " off)");
+  }
   HIPCHK(h, hipSetDevice(h->device));
   Launch L;
   RunArgs A;
@@ -2002,6 +2027,18 @@ int i3rc_hip_normalise_level_fluxes(const i3rc_hip_integrator *h, const double *
   return 0;
 }
 
+int i3rc_hip_normalise_path_lengths(const i3rc_hip_integrator *h, const double *t, float *pathLengthUp, float *pathLengthSquaredUp, float *pathLengthDown,
+                                    float *pathLengthSquaredDown) {
+  if (!h || !t) return 1;
+  if (h->extra != EXTRA_PATHS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_path_lengths: path lengths are not switched on");
+  const TallyView &V = h->view;
+  const size_t ncol = (size_t)h->nx * h->ny;
+  float *const out[4] = {pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown};   // (as the block is laid out)
+  for (int f = 0; f < 4; ++f)
+    for (size_t k = 0; out[f] && k < ncol; ++k) out[f][k] = normalised_extra_value(V, t, EXTRA_PATHS, V.pathUp1, (long long)(f * ncol + k));
+  return 0;
+}
+
 int i3rc_hip_normalise_actinic_flux(const i3rc_hip_integrator *h, const double *t, float *actinicFlux) {
   if (!h || !t || !actinicFlux) return 1;
   if (h->extra != EXTRA_TRACKS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_actinic_flux: the actinic flux is not switched on");
@@ -2016,11 +2053,12 @@ int i3rc_hip_normalise_actinic_flux(const i3rc_hip_integrator *h, const double *
 namespace {
 // The launch of the general flux kernel under the tag of the handle's extra tally block, through the one path every plain launch
 // takes (defined last, so that these kernels are instantiated behind every other kernel of the library: the level kernels, then the
-// track kernels).
+// track kernels, then the path kernels).
 int launch_extra(i3rc_hip_integrator *h, const Launch &L, const RunArgs &A, hipStream_t stream, bool timeIt) {
   switch (h->extra) {
     case EXTRA_LEVELS: return launch<PhiloxLevelStream>(h, L, A, stream, timeIt);
     case EXTRA_TRACKS: return launch<PhiloxTrackStream>(h, L, A, stream, timeIt);
+    case EXTRA_PATHS: return launch<PhiloxPathStream>(h, L, A, stream, timeIt);
     case EXTRA_NONE: break;
   }
   return h->fail("internal: no extra tally block is switched on");
@@ -2033,7 +2071,8 @@ template <int = 0>
 const KernelEntry *find_kernel(const StreamKind &s, const KernelKey &key) {
   const std::vector<KernelEntry> &list = s.replay ? stream_kernels<ReplayStream>() : s.batched ? stream_kernels<PhiloxBatchStream>()
                                          : s.extra == EXTRA_LEVELS ? stream_kernels<PhiloxLevelStream>()
-                                         : s.extra == EXTRA_TRACKS ? stream_kernels<PhiloxTrackStream>() : stream_kernels<PhiloxStream>();
+                                         : s.extra == EXTRA_TRACKS ? stream_kernels<PhiloxTrackStream>()
+                                         : s.extra == EXTRA_PATHS ? stream_kernels<PhiloxPathStream>() : stream_kernels<PhiloxStream>();
   for (const KernelEntry &e : list)
     if (e.key == key) return &e;
   return nullptr;
@@ -2064,10 +2103,10 @@ int i3rc_hip_problem_facts(int nx, int ny, int nz, int ncomp, const float *xEdge
 
 /* Host only: what a launch of `kind` would be on a problem of these facts (i3rc_hip_problem_facts), this setup -- binding.SETUP_NAMES:
  * what the setters and the handle's knobs add -- and these switches of the process (binding.ENV_NAMES; NULL: the process's own).
- * kind: the stream (0 plain, 1 fused, 2 replay, 3 level tally, 4 track tally), the kind of the source, the batches of a fused launch. */
+ * kind: the stream (0 plain, 1 fused, 2 replay, 3 level tally, 4 track tally, 5 path tally), the kind of the source, the batches of a fused launch. */
 int i3rc_hip_plan_launch(const int32_t *facts, const int32_t *setup, const int32_t *env, const int32_t *kind, int32_t *out, int nout,
                          char *text, int ntext) {
-  if (!facts || !setup || !kind || !out || !text || ntext < 1 || kind[0] < 0 || kind[0] > 4 || facts[3] < 1) return 2;
+  if (!facts || !setup || !kind || !out || !text || ntext < 1 || kind[0] < 0 || kind[0] > 5 || facts[3] < 1) return 2;
   ProblemFacts f;
   f.nx = facts[0]; f.ny = facts[1]; f.nz = facts[2]; f.ncomp = facts[3]; f.xyRegular = facts[4]; f.zRegular = facts[5]; f.empty = facts[6] != 0;
   f.absorbing = facts[7] != 0; f.uniformSsa = facts[8] ? 0.5f : -1.f; f.uniformPf = facts[9]; f.cellRecBytes = facts[10];
@@ -2082,7 +2121,7 @@ int i3rc_hip_plan_launch(const int32_t *facts, const int32_t *setup, const int32
   f.params.useSurfaceBDRF = setup[5]; f.params.useRayTracing = setup[6]; f.nxs = setup[7]; f.nys = setup[8]; f.surfaceSet = setup[9] != 0;
   f.extra = (ExtraTally)setup[10]; f.kernelVariant = setup[11]; f.gridPlace = setup[12]; f.ldsTalliesOn = setup[13] != 0;
   const StreamKind s = kind[0] == 2 ? stream_of<ReplayStream>() : kind[0] == 1 ? stream_of<PhiloxBatchStream>()
-                                                                : plain_stream(kind[0] == 3 ? EXTRA_LEVELS : kind[0] == 4 ? EXTRA_TRACKS : EXTRA_NONE);
+                                                                : plain_stream(kind[0] == 3 ? EXTRA_LEVELS : kind[0] == 4 ? EXTRA_TRACKS : kind[0] == 5 ? EXTRA_PATHS : EXTRA_NONE);
   const LaunchDecision d = plan_launch(f, env_from_words(env), {s, kind[1]});
   const KernelEntry *kern = d.refusal.empty() ? find_kernel(s, d.key) : nullptr;
   const std::string say = !d.refusal.empty() ? d.refusal : kern ? kern->name : no_kernel_text(s.batched);

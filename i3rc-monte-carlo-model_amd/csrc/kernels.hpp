@@ -283,6 +283,20 @@ __device__ __forceinline__ void track_add(lds_f64 *sums, double *block, int cell
   else add_global(block + at, v);
 }
 
+// PATH LENGTHS of reflected and transmitted light (EXTRA_PATHS, PhiloxPathStream): per column the sums of w L and w L^2 over the photons
+// that fluxUp and fluxDown count there -- w the weight the flux tally adds at that place (a surface arrival's: before the reflection), L
+// the photon's geometric path since its start -- as four float64 fields [ny][nx]: pathUp1 | pathUp2 | pathDown1 | pathDown2.  L is a
+// float64 register of the lane, the sum of exactly the pieces the actinic flux tallies, each float32 piece converted and added: every
+// voxel step that is no tracer error (trace_step_lazy, LENGTH) and the part finish_arrival forms for an arriving step.  It is 0 for a
+// new photon and carries on through a surface reflection; a photon the tracer drops tallies nothing.  The products are formed in
+// float64 and added with float64 atomics in global memory -- two per photon ending, two more per reflection: no LDS carve-up changes.
+__device__ __forceinline__ void path_add(double *block, int ncol, bool up, int col, float weight, double length) {
+  const double wl = (double)weight * length;
+  double *const at = block + (up ? 0 : 2 * (size_t)ncol) + min((unsigned)col, (unsigned)(ncol - 1));   // (never outside the block, whatever the indices)
+  add_global(at, wl);
+  add_global(at + ncol, wl * length);
+}
+
 // Wave-private reservoir of photon indices: one returning atomic per `chunk` photons instead of one per respawn
 // round (the returning atomic costs microseconds; every wave would pay it in ~97 % of its event phases).  The two
 // bounds are wave-uniform and held in scalar registers (readfirstlane tells the compiler so).
@@ -545,6 +559,9 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   static_assert(!LEVELS || (GENERAL && !INTENSITY && !TBL && !DIRECT && !MULTI), "level fluxes: the general flux kernel");
   static_assert(!TRACK || (GENERAL && !INTENSITY && !TBL && !DIRECT && !MULTI && !STORE && !BATCHED && !REPLAY && !LEVELS),
                 "track lengths: the general flux kernel, no start store, not batched");
+  constexpr bool PATH = Rng::kExtra == EXTRA_PATHS;   // path-length moments (PhiloxPathStream): tallied by the general flux kernel only
+  static_assert(!PATH || (GENERAL && !INTENSITY && !TBL && !DIRECT && !MULTI && !STORE && !BATCHED && !REPLAY),
+                "path lengths: the general flux kernel, no start store, not batched");
   static_assert(!MULTI || (!GENERAL && !TBL && !Rng::kReplay && (INTENSITY || BATCHED)), "MULTI: the widened class -- radiance kernels, and the fused flux kernels (plain flux launches of the class run the general flux kernel)");
   // Work counters of a fused launch.  Flux kernels: exact per batch, gathered per lane (below).  Radiance kernels have no
   // vector register to spare for that: their counters stay per WAVE and are handed to the batch whose photons the wave was
@@ -580,6 +597,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   int order = 0;
   int st = ST_NEW;
   int izFrom = 1;                     // LEVELS: the layer the photon's current segment began in
+  double pathLen = 0.0;               // PATH: the photon's geometric path since its start (path_add)
   // Absorption where the tally goes to global memory: what a photon's CONSECUTIVE scatterings in one cell add to it leaves as one
   // atomic -- when the next scattering lies in another cell, or the photon ends (so that a fused launch's lane never holds a sum of
   // another batch's block).  In clouds whose cells are optically thick (an LES field: 55 m cells, free paths of 10 m) a photon is
@@ -1091,6 +1109,12 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           finish_arrival<true>(r, &part);
           track_add(trackSums, extra_block(tally.base(), Pe.oCnt), cell_index(Pe, r.ix, r.iy, r.iz), Pe.nx * Pe.ny * Pe.nz, w, part);
         }
+      } else if constexpr (PATH) {   // ... or the last piece of the photon's path so far
+        if (wantEvent && st == ST_EVENT && arrival_pending(r)) {
+          float part = 0.0f;
+          finish_arrival<true>(r, &part);
+          pathLen += (double)part;
+        }
       } else
       if (wantEvent && st == ST_EVENT && arrival_pending(r)) finish_arrival(r);
       // ... and one that has left the grid gets its height (finish_exit).  (The general kernels do that where the step ends: here it
@@ -1134,6 +1158,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           }
           const int c2 = (r.iy - 1) * Pe.nx + (r.ix - 1);
           tally.boundary(atTop, c2, w);
+          if constexpr (PATH) path_add(extra_block(tally.base(), Pe.oCnt), Pe.nx * Pe.ny, atTop, c2, w, pathLen);
           if (REPLAY) { fateCol = c2; fateW = w; }
         }
         if (REPLAY) {
@@ -1324,6 +1349,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           order = 0;
           if (REPLAY) { fate = -1; fateCol = -1; fateW = 0.0f; }
           w = 1.0f;
+          if constexpr (PATH) pathLen = 0.0;
           r.x = Pe.x0 + px * (Pe.xMax - Pe.x0);
           r.y = Pe.y0 + py * (Pe.yMax - Pe.y0);
           r.z = Pe.z0 + pz * (Pe.zMax - Pe.z0);
@@ -1359,6 +1385,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
             r.z = surfaceZ;
             const int c2 = (r.iy - 1) * Pe.nx + (r.ix - 1);
             tally.down(c2, w);
+            if constexpr (PATH) path_add(extra_block(tally.base(), Pe.oCnt), Pe.nx * Pe.ny, false, c2, w, pathLen);   // (the weight before the reflection, the path up to here)
             if (REPLAY) { fateCol = c2; fateW = w; }
             float mu = exact_sqrt(rng.first());
             while (!(fabsf(mu) > 2.0f * kTiny)) mu = exact_sqrt((GENERAL || MULTI) ? rng.next() : rng.fresh());   // :546-549
@@ -1593,6 +1620,10 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           float len = 0.0f;
           s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, true, CHAIN>(P, L, r, true, &len);
           if (s == STEP_CONTINUE || s == STEP_EXIT) track_add(trackSums, extra_block(P.tally, P.oCnt), cell, P.nx * P.ny * P.nz, w, len);
+        } else if constexpr (PATH) {   // the same piece, added to the photon's path
+          float len = 0.0f;
+          s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, true, CHAIN>(P, L, r, true, &len);
+          if (s == STEP_CONTINUE || s == STEP_EXIT) pathLen += (double)len;
         } else
         s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, false, CHAIN>(P, L, r, true);   // (an arrival is finished by the event phase)
         if (GENERAL && s == STEP_EXIT) finish_exit(P, r);

@@ -217,7 +217,7 @@ inline bool direct_rays(const ProblemFacts &f, const EnvKnobs &env) {
   return env.direct && f.nDir == 1 && f.kernelVariant != I3RC_KERNEL_RING && !kNestedBuild;
 }
 
-// its stream -- what the Rng template argument of photon_kernel carries: plain (all false), fused, replay, level tally, track tally -- ...
+// its stream -- what the Rng template argument of photon_kernel carries: plain (all false), fused, replay, level tally, track tally, path tally -- ...
 struct StreamKind {
   bool replay, batched;
   ExtraTally extra;
@@ -226,7 +226,10 @@ struct StreamKind {
 template <class Rng>
 constexpr StreamKind stream_of() { return {Rng::kReplay, Rng::kBatched, Rng::kExtra, &has_start_store<Rng>}; }
 inline StreamKind plain_stream(ExtraTally extra) {   // (of a plain launch: the production stream, or the one that also fills the extra tally block)
-  return extra == EXTRA_LEVELS ? stream_of<PhiloxLevelStream>() : extra == EXTRA_TRACKS ? stream_of<PhiloxTrackStream>() : stream_of<PhiloxStream>();
+  return extra == EXTRA_LEVELS   ? stream_of<PhiloxLevelStream>()
+         : extra == EXTRA_TRACKS ? stream_of<PhiloxTrackStream>()
+         : extra == EXTRA_PATHS  ? stream_of<PhiloxPathStream>()
+                                 : stream_of<PhiloxStream>();
 }
 // ... and the kind of its source (i3rc_source::kind, RunArgs::srcKind)
 struct LaunchKind { StreamKind stream; int srcKind; };

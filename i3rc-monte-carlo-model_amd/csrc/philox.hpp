@@ -186,6 +186,7 @@ struct PhiloxBatchStream : PhiloxStreamT<true> {};
 // names begin with neither "PhiloxStream" nor "PhiloxBatchStream": the kernel audits count kernels by those prefixes.)
 struct PhiloxLevelStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_LEVELS; };
 struct PhiloxTrackStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_TRACKS; };
+struct PhiloxPathStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_PATHS; };
 
 // Test stream: deviates come from a buffer (the reference's MT19937 floats); see i3rc_hip_run_replay.
 struct ReplayStream {

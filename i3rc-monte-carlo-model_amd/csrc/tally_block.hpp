@@ -18,6 +18,7 @@ namespace i3rc {
 struct TallyView {
   // offsets in float64 elements (tally_layout below; the level block lies behind the counters, -1 while it is switched off)
   long long fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, intensityByComponent, intensityExcess, counters, levelUp, levelDown;
+  long long pathUp1, pathUp2, pathDown1, pathDown2;   // the path-length block's four fields, [ny][nx] each (-1 unless the block is EXTRA_PATHS)
   int nx, ny, nz, ncomp, nDir, xyRegular;
   int limitContrib;         // the excess of limited radiance contributions is redistributed (:327-347)
   const double *areaFrac;   // [nx * ny] column area / domain area (:358-366; read on irregular grids only)
@@ -30,18 +31,20 @@ struct TallyView {
 enum ExtraTally {
   EXTRA_NONE,
   EXTRA_LEVELS,   // levelFluxUp | levelFluxDown, [nz + 1][ny][nx] each (i3rc_hip_set_level_fluxes)
-  EXTRA_TRACKS    // the actinic flux's track-length sums, [nz][ny][nx] (i3rc_hip_set_actinic_flux)
+  EXTRA_TRACKS,   // the actinic flux's track-length sums, [nz][ny][nx] (i3rc_hip_set_actinic_flux)
+  EXTRA_PATHS     // pathUp1 | pathUp2 | pathDown1 | pathDown2, [ny][nx] each: the sums of w L and w L^2 over the photons that fluxUp / fluxDown count,
+                  // L the geometric path since the photon's start (i3rc_hip_set_path_lengths)
 };
 I3RC_TALLY_FN long long extra_block_offset(long long countersOffset) { return countersOffset + I3RC_NUM_COUNTERS; }
 // ... and its length in float64 words
 I3RC_TALLY_FN long long extra_block_words(ExtraTally kind, int nx, int ny, int nz) {
   const long long ncol = (long long)nx * ny;
-  return kind == EXTRA_LEVELS ? 2 * (nz + 1) * ncol : (kind == EXTRA_TRACKS ? ncol * nz : 0);
+  return kind == EXTRA_LEVELS ? 2 * (nz + 1) * ncol : (kind == EXTRA_TRACKS ? ncol * nz : (kind == EXTRA_PATHS ? 4 * ncol : 0));
 }
 
 // The packed tally buffer of a grid: the fields of i3rc_tally_layout one behind the other, then the extra block, so that switching it
-// moves no other offset.  Fills L, and V's offsets and sizes (levelUp / levelDown: -1 unless the block is EXTRA_LEVELS); returns the
-// extra block's offset, -1 without one.
+// moves no other offset.  Fills L, and V's offsets and sizes (levelUp / levelDown: -1 unless the block is EXTRA_LEVELS; pathUp1 ...
+// pathDown2: -1 unless it is EXTRA_PATHS); returns the extra block's offset, -1 without one.
 inline long long tally_layout(int nx, int ny, int nz, int ncomp, int nDir, ExtraTally extra, i3rc_tally_layout &L, TallyView &V) {
   const long long ncol = (long long)nx * ny;
   long long o = 0;
@@ -58,6 +61,10 @@ inline long long tally_layout(int nx, int ny, int nz, int ncomp, int nDir, Extra
   V.intensityByComponent = L.intensityByComponent; V.intensityExcess = L.intensityExcess; V.counters = L.counters;
   V.levelUp = extra == EXTRA_LEVELS ? block : -1;
   V.levelDown = extra == EXTRA_LEVELS ? block + (nz + 1) * ncol : -1;
+  V.pathUp1 = extra == EXTRA_PATHS ? block : -1;
+  V.pathUp2 = extra == EXTRA_PATHS ? block + ncol : -1;
+  V.pathDown1 = extra == EXTRA_PATHS ? block + 2 * ncol : -1;
+  V.pathDown2 = extra == EXTRA_PATHS ? block + 3 * ncol : -1;
   V.nx = nx; V.ny = ny; V.nz = nz; V.ncomp = ncomp; V.nDir = nDir;
   return block;
 }
@@ -95,8 +102,9 @@ I3RC_TALLY_FN float normalised_actinic_flux(const TallyView &V, const double *ra
 }
 
 // Element e of the kind's extra block (at `block`) as reportResults hands it out: the level fluxes (e counts through levelFluxUp |
-// levelFluxDown, level after level) per photon of the column, the actinic flux also per unit of the layer's depth.  What
-// i3rc_hip_normalise_level_fluxes / _actinic_flux fill their arrays with and what the diagnostic batch moments add up.
+// levelFluxDown, level after level) and the path-length sums (e counts through pathUp1 | pathUp2 | pathDown1 | pathDown2) per photon of
+// the column, as fluxUp; the actinic flux also per unit of the layer's depth.  What i3rc_hip_normalise_level_fluxes / _actinic_flux /
+// _path_lengths fill their arrays with and what the diagnostic batch moments add up.
 I3RC_TALLY_FN float normalised_extra_value(const TallyView &V, const double *raw, ExtraTally kind, long long block, long long e) {
   const long long ncol = (long long)V.nx * V.ny;
   if (kind == EXTRA_TRACKS) {

@@ -233,6 +233,20 @@ module i3rcHipInterface
       type(c_ptr), value         :: actinicFlux                  ! (nx, ny, nz)
       integer(c_int)             :: rc
     end function
+    function i3rc_hip_set_path_lengths(h, on) bind(C, name = "i3rc_hip_set_path_lengths") result(rc)
+      import
+      type(c_ptr), value    :: h
+      integer(c_int), value :: on
+      integer(c_int)        :: rc
+    end function
+    function i3rc_hip_normalise_path_lengths(h, host, pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown) &
+             bind(C, name = "i3rc_hip_normalise_path_lengths") result(rc)
+      import
+      type(c_ptr), value         :: h
+      real(c_double), intent(in) :: host(*)
+      type(c_ptr), value         :: pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown   ! (nx, ny) each
+      integer(c_int)             :: rc
+    end function
     function i3rc_hip_device_count() bind(C, name = "i3rc_hip_device_count") result(n)
       import
       integer(c_int) :: n

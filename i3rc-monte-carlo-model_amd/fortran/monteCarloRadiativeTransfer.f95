@@ -63,6 +63,11 @@ module monteCarloRadiativeTransfer
     ! in units of the incident flux on a horizontal surface (not in the reference)
     logical :: computeActinicFlux = .false.
     real, dimension(:, :, :),    pointer :: actinicFlux => null()
+    ! ... and, with specifyParameters(computePathLengths = .true.), the first two moments of the geometric path length of the reflected
+    ! and the transmitted light (nx, ny, 4): pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown, in units of
+    ! length (squared) x incident flux (not in the reference)
+    logical :: computePathLengths = .false.
+    real, dimension(:, :, :),    pointer :: pathLengths => null()
     double precision :: photonsProcessed = 0.d0, photonsDropped = 0.d0
     ! raw tallies of the batches of the last computeRadiativeTransferBatches (one column per batch)
     real(c_double), dimension(:, :), pointer :: batchTallies => null()
@@ -169,7 +174,7 @@ contains
                                useHybridPhaseFunsForIntenCalcs, hybridPhaseFunWidth,   &
                                numOrdersOrigPhaseFunIntenCalcs,                        &
                                limitIntensityContributions, maxIntensityContribution,  &
-                               status, computeLevelFluxes, computeActinicFlux)
+                               status, computeLevelFluxes, computeActinicFlux, computePathLengths)
     type(integrator),                   intent(inout) :: thisIntegrator
     real,                     optional, intent(in   ) :: surfaceAlbedo
     type(surfaceDescription), optional, intent(in   ) :: surfaceBDRF
@@ -188,6 +193,8 @@ contains
     logical,                  optional, intent(in   ) :: computeLevelFluxes
     ! (likewise: the actinic flux of every cell, see reportResults)
     logical,                  optional, intent(in   ) :: computeActinicFlux
+    ! (likewise: the path-length moments of reflected and transmitted light, see reportResults)
+    logical,                  optional, intent(in   ) :: computePathLengths
     integer :: i, nDir, nx, ny, nc
     real, dimension(:),    pointer :: xs, ys
     real, dimension(:, :), pointer :: albedoGrid
@@ -354,6 +361,16 @@ contains
         thisIntegrator%actinicFlux = 0.
       end if
       thisIntegrator%computeActinicFlux = computeActinicFlux
+    end if
+    if(present(computePathLengths)) then
+      if(.not. deviceCall(thisIntegrator, i3rc_hip_set_path_lengths(thisIntegrator%device, merge(1, 0, computePathLengths)), &
+                          "specifyParameters", status)) return
+      if(associated(thisIntegrator%pathLengths)) deallocate(thisIntegrator%pathLengths)
+      if(computePathLengths) then
+        allocate(thisIntegrator%pathLengths(size(thisIntegrator%totalExt, 1), size(thisIntegrator%totalExt, 2), 4))
+        thisIntegrator%pathLengths = 0.
+      end if
+      thisIntegrator%computePathLengths = computePathLengths
     end if
     call setStateToSuccess(status)
   end subroutine specifyParameters
@@ -598,6 +615,12 @@ contains
     if(thisIntegrator%computeActinicFlux) then
       ok = deviceCall(thisIntegrator, i3rc_hip_normalise_actinic_flux(thisIntegrator%device, raw,                           &
                       c_loc(thisIntegrator%actinicFlux(1, 1, 1))), caller, status)
+      if(.not. ok) return
+    end if
+    if(thisIntegrator%computePathLengths) then
+      ok = deviceCall(thisIntegrator, i3rc_hip_normalise_path_lengths(thisIntegrator%device, raw,                           &
+                      c_loc(thisIntegrator%pathLengths(1, 1, 1)), c_loc(thisIntegrator%pathLengths(1, 1, 2)),                &
+                      c_loc(thisIntegrator%pathLengths(1, 1, 3)), c_loc(thisIntegrator%pathLengths(1, 1, 4))), caller, status)
       if(.not. ok) return
     end if
     thisIntegrator%photonsProcessed = raw(layout%counters + 1 + I3RC_CNT_PHOTONS)
@@ -1045,7 +1068,7 @@ contains
   ! ------------------------------------------------------------------------------------------------
   subroutine reportResults(thisIntegrator, meanFluxUp, meanFluxDown, meanFluxAbsorbed, fluxUp, fluxDown, fluxAbsorbed, &
                            absorbedProfile, volumeAbsorption, meanIntensity, intensity, status, levelFluxUp, levelFluxDown, &
-                           actinicFlux)
+                           actinicFlux, pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown)
     type(integrator),                   intent(in   ) :: thisIntegrator
     real,                     optional, intent(  out) :: meanFluxUp, meanFluxDown, meanFluxAbsorbed
     real, dimension(:, :),    optional, intent(  out) :: fluxUp, fluxDown, fluxAbsorbed
@@ -1058,6 +1081,9 @@ contains
     real, dimension(:, :, :), optional, intent(  out) :: levelFluxUp, levelFluxDown
     ! (likewise) (nx, ny, nz): the cell's mean actinic flux in units of the incident flux on a horizontal surface
     real, dimension(:, :, :), optional, intent(  out) :: actinicFlux
+    ! (likewise) (nx, ny): the sums of w L and w L**2 over the photons fluxUp / fluxDown count, L the geometric path since the photon's
+    ! start, normalised as fluxUp is: pathLengthUp / fluxUp is the mean path of a column's reflected light
+    real, dimension(:, :),    optional, intent(  out) :: pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown
     integer :: nColumns, d
 
     if(.not. associated(thisIntegrator%fluxUp)) then
@@ -1139,8 +1165,22 @@ contains
         actinicFlux = thisIntegrator%actinicFlux
       end if
     end if
+    if(present(pathLengthUp))          call copyPathField(1, pathLengthUp,          "pathLengthUp")
+    if(present(pathLengthSquaredUp))   call copyPathField(2, pathLengthSquaredUp,   "pathLengthSquaredUp")
+    if(present(pathLengthDown))        call copyPathField(3, pathLengthDown,        "pathLengthDown")
+    if(present(pathLengthSquaredDown)) call copyPathField(4, pathLengthSquaredDown, "pathLengthSquaredDown")
     if(.not. stateIsFailure(status)) call setStateToSuccess(status)
   contains
+    subroutine copyPathField(which, to, name)
+      integer,               intent(in ) :: which
+      real, dimension(:, :), intent(out) :: to
+      character(len = *),    intent(in ) :: name
+      if(.not. associated(thisIntegrator%pathLengths)) then
+        call setStateToFailure(status, "reportResults: path length information not available")
+      else
+        call copyField(thisIntegrator%pathLengths(:, :, which), to, name)
+      end if
+    end subroutine copyPathField
     subroutine copyField(from, to, name)
       real, dimension(:, :), intent(in ) :: from
       real, dimension(:, :), intent(out) :: to
@@ -1215,6 +1255,13 @@ contains
         copy%computeActinicFlux = .true.
       end if
     end if
+    if(original%computePathLengths) then
+      if(deviceCall(copy, i3rc_hip_set_path_lengths(copy%device, 1), "copy_Integrator", status)) then
+        allocate(copy%pathLengths(nx, ny, 4))
+        copy%pathLengths = original%pathLengths
+        copy%computePathLengths = .true.
+      end if
+    end if
   end function copy_Integrator
 
   subroutine finalize_Integrator(thisIntegrator)
@@ -1250,7 +1297,8 @@ contains
     if(associated(thisIntegrator%diagnosticSums))       deallocate(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares)
     if(associated(thisIntegrator%levelFluxUp))          deallocate(thisIntegrator%levelFluxUp, thisIntegrator%levelFluxDown)
     if(associated(thisIntegrator%actinicFlux))          deallocate(thisIntegrator%actinicFlux)
-    thisIntegrator%computeLevelFluxes = .false.; thisIntegrator%computeActinicFlux = .false.
+    if(associated(thisIntegrator%pathLengths))          deallocate(thisIntegrator%pathLengths)
+    thisIntegrator%computeLevelFluxes = .false.; thisIntegrator%computeActinicFlux = .false.; thisIntegrator%computePathLengths = .false.
     thisIntegrator%readyToCompute = .false.; thisIntegrator%computeIntensity = .false.
     thisIntegrator%useSurfaceBDRF = .false.
   end subroutine finalize_Integrator

@@ -174,6 +174,10 @@ class Domain:
 
 
 # ---------------------------------------------------------------------------------------------------------
+# the four results of the path-length tally, in the order of its block (i3rc_hip_normalise_path_lengths)
+PATH_LENGTH_NAMES = ("pathLengthUp", "pathLengthSquaredUp", "pathLengthDown", "pathLengthSquaredDown")
+
+
 class Integrator:
     """type(integrator): owns a device-resident copy of the problem (new_Integrator :162-254)."""
 
@@ -181,7 +185,7 @@ class Integrator:
                    "intensityPhis", "computeIntensity", "useRayTracing", "useRussianRoulette",
                    "useRussianRouletteForIntensity", "zetaMin", "useHybridPhaseFunsForIntenCalcs",
                    "hybridPhaseFunWidth", "numOrdersOrigPhaseFunIntenCalcs", "limitIntensityContributions",
-                   "maxIntensityContribution", "computeLevelFluxes", "computeActinicFlux")
+                   "maxIntensityContribution", "computeLevelFluxes", "computeActinicFlux", "computePathLengths")
 
     def __init__(self, atmosphere, device=0):
         self._h = C.c_void_p()
@@ -212,6 +216,7 @@ class Integrator:
         self.computeIntensity = False
         self.computeLevelFluxes = False
         self.computeActinicFlux = False
+        self.computePathLengths = False
         self._inv_size = [0] * self.ncomp
         self._fwd_size = [0] * self.ncomp
         self._fwd_stale = True
@@ -323,6 +328,19 @@ class Integrator:
             self.computeActinicFlux = bool(kw["computeActinicFlux"])
             self._results = None             # (the tally layout has changed)
 
+        if "computePathLengths" in kw:
+            # the first two moments of the path length of reflected and transmitted light (i3rc_hip_set_path_lengths): not in the reference
+            self._check(self._lib.i3rc_hip_set_path_lengths(self._h, int(bool(kw["computePathLengths"]))), "specifyParameters")
+            self.computePathLengths = bool(kw["computePathLengths"])
+            self._results = None             # (the tally layout has changed)
+
+    def path_length_layout(self):
+        """(offsets of pathUp1, pathUp2, pathDown1, pathDown2, total) of the packed tally buffer, in float64 elements; the offsets are
+        -1 while path lengths are off (i3rc_hip_get_path_length_layout)."""
+        v = [C.c_int64(0) for _ in range(5)]
+        self._check(self._lib.i3rc_hip_get_path_length_layout(self._h, *[C.byref(x) for x in v]), "path_length_layout")
+        return tuple(x.value for x in v)
+
     def actinic_flux_layout(self):
         """(offset of the track-length block, total) of the packed tally buffer, in float64 elements; the offset is -1 while the
         actinic flux is off (i3rc_hip_get_actinic_flux_layout)."""
@@ -428,6 +446,11 @@ class Integrator:
         if self.computeActinicFlux:
             res["actinicFlux"] = np.zeros((self.nz, self.ny, self.nx), np.float32)
             self._check(self._lib.i3rc_hip_normalise_actinic_flux(self._h, raw.ctypes.data_as(B.dp), pf(res["actinicFlux"])),
+                        "computeRadiativeTransfer")
+        if self.computePathLengths:
+            for k in PATH_LENGTH_NAMES:
+                res[k] = np.zeros((self.ny, self.nx), np.float32)
+            self._check(self._lib.i3rc_hip_normalise_path_lengths(self._h, raw.ctypes.data_as(B.dp), *[pf(res[k]) for k in PATH_LENGTH_NAMES]),
                         "computeRadiativeTransfer")
         cnt = raw[lay.counters:lay.counters + B.NUM_COUNTERS]
         res["counters"] = {k: float(cnt[i]) for i, k in enumerate(B.COUNTER_NAMES)}
@@ -561,9 +584,14 @@ class Integrator:
         return ms
 
     # -- reportResults :711-826
-    def reportResults(self, levelFluxUp=False, levelFluxDown=False, actinicFlux=False):
+    def reportResults(self, levelFluxUp=False, levelFluxDown=False, actinicFlux=False, pathLengthUp=False, pathLengthSquaredUp=False,
+                      pathLengthDown=False, pathLengthSquaredDown=False):
         """levelFluxUp / levelFluxDown = True ask for the level fluxes, (nz + 1, ny, nx) each, level k at zPosition[k] (the shell's optional
-        arguments of the same names): an error unless specifyParameters(computeLevelFluxes=True) came before the computation."""
+        arguments of the same names): an error unless specifyParameters(computeLevelFluxes=True) came before the computation.
+        pathLengthUp / pathLengthSquaredUp / pathLengthDown / pathLengthSquaredDown = True ask for the path-length moments of the
+        reflected and the transmitted light, the shell's (nx, ny) arrays in fluxUp's own shape here, in units of length (squared) x
+        incident flux: pathLengthUp / fluxUp is the mean path of a column's reflected light.  An error unless
+        specifyParameters(computePathLengths=True) came before the computation."""
         r = self._results
         if r is None:
             raise I3RCError("reportResults: no results available")
@@ -571,6 +599,9 @@ class Integrator:
             raise I3RCError("reportResults: level fluxes weren't computed (specifyParameters: computeLevelFluxes)")
         if actinicFlux and "actinicFlux" not in r:   # (actinicFlux = True: the cell-mean actinic flux, (nz, ny, nx); the shell's error text)
             raise I3RCError("reportResults: actinic flux information not available")
+        paths = [k for k, asked in zip(PATH_LENGTH_NAMES, (pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown)) if asked]
+        if paths and "pathLengthUp" not in r:
+            raise I3RCError("reportResults: path length information not available")
         ncol = r32(self.nx * self.ny)
         out = dict(meanFluxUp=r["fluxUp"].sum(dtype=np.float32) / ncol, meanFluxDown=r["fluxDown"].sum(dtype=np.float32) / ncol,
                    meanFluxAbsorbed=r["fluxAbsorbed"].sum(dtype=np.float32) / ncol,
@@ -586,6 +617,8 @@ class Integrator:
             out["levelFluxDown"] = r["levelFluxDown"]
         if actinicFlux:
             out["actinicFlux"] = r["actinicFlux"]
+        for k in paths:
+            out[k] = r[k]
         return out
 
     # -- test hooks

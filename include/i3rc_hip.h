@@ -195,6 +195,41 @@ int i3rc_hip_get_actinic_flux_layout(const i3rc_hip_integrator *h, int64_t *offs
  * volumeAbsorption in a cell is sum_j ext_j (1 - omega_j) times it.  Fails while the feature is off. */
 int i3rc_hip_normalise_actinic_flux(const i3rc_hip_integrator *h, const double *hostTallies, float *actinicFlux);
 
+/* PATH LENGTHS of reflected and transmitted light (not in the reference): with on != 0, plain flux launches (i3rc_hip_launch_batch,
+ * i3rc_hip_compute_batch, launches split over photon ranges) also tally the first two moments of the photons' geometric path length,
+ * per column: four arrays [ny][nx] of float64 raw sums,
+ *   pathUp1, pathUp2       where fluxUp is tallied (exit through the top, the tracer's own column):          w L and w L^2,
+ *   pathDown1, pathDown2   where fluxDown is tallied (every arrival at the surface, black or reflecting):    w L and w L^2.
+ * w is exactly the weight the flux tally adds at that place -- for a surface arrival the weight before the reflection --, L the
+ * photon's geometric path since its start, in the domain's length unit: the sum of the pieces the actinic flux tallies (every voxel
+ * step that is no tracer error at its full float32 length, and the part up to the arrival of the step in which the photon reaches its
+ * optical depth), each converted to float64 and added in a float64 register of the lane.  L is 0 for a new photon and carries on
+ * through a surface reflection: a second arrival at the surface tallies the cumulative path.  A photon the tracer drops tallies
+ * nothing.  The products (double)w * L and that times L are formed in float64.  So sum(pathUp1) / sum(fluxUp) of the raw sums is the
+ * mean path <L> of the reflected light, sum(pathUp2) / sum(fluxUp) its <L^2>: what the equivalence theorem needs to turn one
+ * conservative run into the reflectance of a band with gaseous absorption, R(k) = R(0) <exp(-k L)>.
+ * The four arrays form a block of 4 nx ny float64 words BEHIND the counters of the packed tally buffer -- where the level fluxes' or
+ * the actinic flux's block would lie: the three features are never on together, and each setter refuses while another is on.  No
+ * offset of i3rc_tally_layout moves; layout.total grows by 4 nx ny while the feature is on and is what it was once it is off again
+ * (zeroing, fetching, binding and an all-reduce of the packed buffer cover the block).  Switching reallocates the handle's own buffer
+ * (cleared); with a caller-bound buffer in use it is refused.  Off by default: nothing changes then.
+ * While the feature is on, a launch runs photon_kernel<PhiloxPathStream, false, true, GRID> -- the general flux kernel's photons,
+ * counter for counter -- and is refused, before anything is touched, when radiance directions are set (nDir > 0) or max cross-section
+ * is in use (useRayTracing = 0); i3rc_hip_run_batches, i3rc_hip_run_batches_moments, i3rc_hip_expect_batches, i3rc_hip_run_replay,
+ * i3rc_hip_run_batches_diagnostic_moments and i3rc_hip_get_diagnostic_moments_layout are refused (the diagnostic moments' layout has no
+ * slot for this kind: it has no batch statistics); i3rc_hip_compute_batch does not look ahead.  Through layers WITHOUT extinction over a
+ * reflecting surface the estimate of <L> has infinite variance and <L^2> diverges logarithmically (a Lambertian reflection into mu
+ * crosses such a layer on a path of dz / mu); extinction in every cell removes the problem. */
+int i3rc_hip_set_path_lengths(i3rc_hip_integrator *h, int on);
+/* Offsets (float64 elements) of pathUp1, pathUp2, pathDown1 and pathDown2 in the packed buffer, -1 each while the feature is off, and
+ * the buffer's total (= layout.total).  Any of the five may be NULL. */
+int i3rc_hip_get_path_length_layout(const i3rc_hip_integrator *h, int64_t *up1, int64_t *up2, int64_t *down1, int64_t *down2, int64_t *total);
+/* fluxUp's normalisation (i3rc_hip_normalise: per column, divided by the photons per column, float64 rounded to float32) of a host
+ * copy of the packed tallies: the four arrays [ny][nx], in units of length x incident flux, so that pathLengthUp / fluxUp is the mean
+ * path of a column's reflected light.  Any output may be NULL.  Fails while the feature is off. */
+int i3rc_hip_normalise_path_lengths(const i3rc_hip_integrator *h, const double *hostTallies, float *pathLengthUp, float *pathLengthSquaredUp,
+                                    float *pathLengthDown, float *pathLengthSquaredDown);
+
 /* ---- the hot path ---------------------------------------------------------------------------------- */
 
 /* computeRT (:400-707) for one batch of nPhotons, ASYNCHRONOUS on the handle's stream; tallies accumulate.
@@ -474,10 +509,10 @@ int i3rc_hip_lds_plan_words(const int32_t *q, int nq, int32_t *out, int nout);
  *   facts      the 23 words above
  *   setup      what the setters and the handle's knobs add, 14 words: nDir; every component has its inverse table, its forward tables
  *              (0 / 1); steps and entries of component 1's inverse table; useSurfaceBDRF, useRayTracing; the surface grid's nx, ny and
- *              whether one is set; the extra tally (0 none, 1 level fluxes, 2 actinic flux); the kernel variant (I3RC_KERNEL_*), the
+ *              whether one is set; the extra tally (0 none, 1 level fluxes, 2 actinic flux, 3 path lengths); the kernel variant (I3RC_KERNEL_*), the
  *              grid place (I3RC_GRID_*), i3rc_hip_set_lds_tallies (0 / 1)
  *   env        as above
- *   kind       3 words: the stream (0 plain, 1 fused, 2 replay, 3 level tally, 4 track tally), the source's kind (i3rc_source::kind),
+ *   kind       3 words: the stream (0 plain, 1 fused, 2 replay, 3 level tally, 4 track tally, 5 path tally), the source's kind (i3rc_source::kind),
  *              the batches of a fused launch
  *   out[0..min(nout, 16) - 1] = the 13 words of i3rc_hip_last_plan as the launch would record them (the chunk, which needs the device:
  *              0), then the estimate of a workgroup's LDS the decisions were made with (bytes), the ray queue's capacity, the
