@@ -31,6 +31,7 @@ SYMBOLS = [
     "i3rc_hip_set_level_fluxes", "i3rc_hip_get_level_flux_layout", "i3rc_hip_normalise_level_fluxes",
     "i3rc_hip_set_actinic_flux", "i3rc_hip_get_actinic_flux_layout", "i3rc_hip_normalise_actinic_flux",
     "i3rc_hip_set_path_lengths", "i3rc_hip_get_path_length_layout", "i3rc_hip_normalise_path_lengths",
+    "i3rc_hip_set_path_histogram", "i3rc_hip_get_path_histogram_layout", "i3rc_hip_normalise_path_histogram",
     "i3rc_hip_problem_facts", "i3rc_hip_plan_launch",
     "i3rc_hip_run_batches_diagnostic_moments", "i3rc_hip_get_diagnostic_moments_layout", "i3rc_hip_diagnostic_moments_layout_words",
 ]
@@ -63,7 +64,8 @@ class MomentsLayout(C.Structure):
 
 # i3rc_diagnostic_moments_layout; without its first word, the words of i3rc_hip_diagnostic_moments_layout_words in order
 DIAGNOSTIC_MOMENTS_NAMES = ["levelFluxUp", "levelFluxDown", "meanLevelFluxUp", "meanLevelFluxDown", "actinicFlux", "meanActinicFlux", "total"]
-EXTRA_KINDS = {"none": 0, "levels": 1, "tracks": 2, "paths": 3}   # (csrc/tally_block.hpp, ExtraTally; path lengths have no batch moments)
+EXTRA_KINDS = {"none": 0, "levels": 1, "tracks": 2, "paths": 3, "bins": 4}   # (csrc/tally_block.hpp, ExtraTally; path lengths and the path histogram have no batch moments)
+MAX_PATH_BINS = 1024   # (csrc/tally_block.hpp, kMaxPathBins)
 
 
 class DiagnosticMomentsLayout(C.Structure):
@@ -82,6 +84,9 @@ def diagnostic_moments_layout(kind, nx, ny, nz, nout=len(DIAGNOSTIC_MOMENTS_NAME
 # the words of i3rc_hip_last_plan, in order
 PLAN_NAMES = ["ldsGrid", "ldsTallies", "ldsVolume", "ldsIntensity", "tableInLds", "ldsBytes", "absorbing", "cellRecordBytes",
               "fusedBatches", "place", "startStoreBytes", "chunk", "ldsTrackSums"]
+# ... and the fourteenth, which the call hands out where it is asked for: the path histogram's sums and edges in LDS (1), or its block
+# added to in global memory (0)
+PLAN_BIN_NAME = "ldsPathBins"
 
 
 # the words of i3rc_hip_problem_facts, in order ...
@@ -93,7 +98,7 @@ SETUP_NAMES = ["nDir", "inverseTables", "forwardTables", "inverseSteps", "invers
                "surfaceNy", "surfaceSet", "extra", "kernelVariant", "gridPlace", "ldsTalliesOn"]
 ENV_DEFAULTS = {"I3RC_COLUMNS": 1, "I3RC_LDS_TALLIES": 1, "I3RC_TABLE_LDS": 1, "I3RC_TABLE_LDS_PLACES": 11, "I3RC_FUSED_TABLE_LDS_PLACES": 11,
                 "I3RC_DIRECT": 1, "I3RC_CELL_RECORDS": 1}
-STREAM_KINDS = {"plain": 0, "fused": 1, "replay": 2, "level": 3, "track": 4, "path": 5}
+STREAM_KINDS = {"plain": 0, "fused": 1, "replay": 2, "level": 3, "track": 4, "path": 5, "bins": 6}
 PLAN_EXTRA_NAMES = ["ldsEstimate", "rayQueueCap", "threads"]
 
 
@@ -118,17 +123,21 @@ def problem_facts(nx, ny, nz, ncomp, xe, ye, ze, total, cum, ssa, pfi, env=None)
     return dict(zip(FACT_NAMES, (int(v) for v in out)))
 
 
-def plan_launch(facts, setup, stream="plain", source=0, fused_batches=0, env=None):
+def plan_launch(facts, setup, stream="plain", source=0, fused_batches=0, env=None, path_bins=0):
     """i3rc_hip_plan_launch: (kernel name, dict of PLAN_NAMES + PLAN_EXTRA_NAMES), or (refusal text, None).  facts: a dict of FACT_NAMES;
-    setup: a dict of SETUP_NAMES.  No device needed."""
-    n = len(PLAN_NAMES) + len(PLAN_EXTRA_NAMES)
+    setup: a dict of SETUP_NAMES.  stream "bins" (the path histogram): path_bins its bins, and PLAN_BIN_NAME one more word of the dict.
+    No device needed."""
+    bins = stream == "bins"
+    n = len(PLAN_NAMES) + len(PLAN_EXTRA_NAMES) + int(bins)
     out, text = (C.c_int32 * n)(), C.create_string_buffer(512)
     rc = load().i3rc_hip_plan_launch((C.c_int32 * len(FACT_NAMES))(*[int(facts[k]) for k in FACT_NAMES]),
                                      (C.c_int32 * len(SETUP_NAMES))(*[int(setup[k]) for k in SETUP_NAMES]), _env_words(env),
-                                     (C.c_int32 * 3)(STREAM_KINDS[stream], int(source), int(fused_batches)), out, n, text, len(text))
+                                     (C.c_int32 * 4)(STREAM_KINDS[stream], int(source), int(fused_batches), int(path_bins)), out, n, text,
+                                     len(text))
     if rc == 2:
         raise I3RCError("i3rc_hip_plan_launch: bad arguments")
-    return text.value.decode(), (dict(zip(PLAN_NAMES + PLAN_EXTRA_NAMES, (int(v) for v in out))) if rc == 0 else None)
+    names = PLAN_NAMES + PLAN_EXTRA_NAMES + ([PLAN_BIN_NAME] if bins else [])
+    return text.value.decode(), (dict(zip(names, (int(v) for v in out))) if rc == 0 else None)
 
 
 class I3RCError(RuntimeError):
@@ -226,6 +235,10 @@ def load():
         L.i3rc_hip_set_path_lengths.argtypes = [H, C.c_int]
         L.i3rc_hip_get_path_length_layout.argtypes = [H, lp, lp, lp, lp, lp]
         L.i3rc_hip_normalise_path_lengths.argtypes = [H, dp, fp, fp, fp, fp]
+    if hasattr(L, "i3rc_hip_set_path_histogram"):   # (likewise)
+        L.i3rc_hip_set_path_histogram.argtypes = [H, C.c_int, fp]
+        L.i3rc_hip_get_path_histogram_layout.argtypes = [H, lp, lp, lp, lp, lp, lp]
+        L.i3rc_hip_normalise_path_histogram.argtypes = [H, dp, fp, fp, fp, fp]
     if hasattr(L, "i3rc_hip_plan_launch"):   # (likewise)
         L.i3rc_hip_problem_facts.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp, ip, ip, ip, C.c_int]
         L.i3rc_hip_plan_launch.argtypes = [ip, ip, ip, ip, ip, C.c_int, C.c_char_p, C.c_int]

@@ -75,6 +75,8 @@ struct i3rc_hip_integrator : ProblemFacts {   // (the facts every launch is deci
   DevBuf dXs, dYs, dBrdf;
   float brdf0 = 0.f;          // reflectance of the first surface cell (a 1 x 1 surface grid is a plain Lambertian albedo)
   DevBuf dDir;
+  DevBuf dBins;                  // the path histogram's table as the kernels read it (BinTable, kernels.hpp): nBins, then the nBins + 1 edges
+  std::vector<float> binEdges;   // ... and the edges' host copy (empty while the histogram is off)
 
   i3rc_tally_layout layout{};
   TallyView view{};                // the same block as the normalisation sees it (tally_block.hpp, tally_layout), over the host arrays above
@@ -153,6 +155,7 @@ struct i3rc_hip_integrator : ProblemFacts {   // (the facts every launch is deci
   int blocksPerCU = 0;  // 0 = from occupancy query
   std::string lastKernelName;            // kernel the most recent launch ran (i3rc_hip_last_kernel_name)
   int32_t lastPlan[kPlanWords] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // ... and its plan (i3rc_hip_last_plan)
+  int32_t lastPlanBins = -1;             // ... and that plan's fourteenth word (kPlanBinWord)
   int64_t launchLimit = 0;               // photons per kernel launch (i3rc_hip_set_launch_limit); 0 = numCU * 2^22
   std::string err;
 
@@ -171,7 +174,7 @@ struct i3rc_hip_integrator : ProblemFacts {   // (the facts every launch is deci
 
 static void compute_layout(i3rc_hip_integrator *h) {
   TallyView &V = h->view;
-  (void)tally_layout(h->nx, h->ny, h->nz, h->ncomp, h->nDir, h->extra, h->layout, V);
+  (void)tally_layout(h->nx, h->ny, h->nz, h->ncomp, h->nDir, h->extra, h->layout, V, h->pathBins);
   V.xyRegular = h->xyRegular;
   V.areaFrac = h->areaFrac.data(); V.dz = h->layerDepth.data();
 }
@@ -226,15 +229,17 @@ static const ExtraWords kExtraWords[] = {
     {},
     {"i3rc_hip_set_level_fluxes", "level fluxes", "are", "need", "them", "their", "the level fluxes'"},
     {"i3rc_hip_set_actinic_flux", "the actinic flux", "is", "needs", "it", "its", "the actinic flux's"},
-    {"i3rc_hip_set_path_lengths", "path lengths", "are", "need", "them", "their", "the path lengths'"}};
+    {"i3rc_hip_set_path_lengths", "path lengths", "are", "need", "them", "their", "the path lengths'"},
+    {"i3rc_hip_set_path_histogram", "the path histogram", "is", "needs", "it", "its", "the path histogram's"}};
 
-// Switches one kind of the optional diagnostic tally on or off (i3rc_hip_set_level_fluxes, i3rc_hip_set_actinic_flux, i3rc_hip_set_path_lengths).
-static int set_extra_tally(i3rc_hip_integrator *h, ExtraTally kind, bool on) {
+// Switches one kind of the optional diagnostic tally on or off (i3rc_hip_set_level_fluxes, i3rc_hip_set_actinic_flux, i3rc_hip_set_path_lengths,
+// i3rc_hip_set_path_histogram -- whose block is sized by nBins: switching it on while it is on lays the block out anew, cleared).
+static int set_extra_tally(i3rc_hip_integrator *h, ExtraTally kind, bool on, int nBins = 0) {
   if (!h) return 1;
   drop_lookahead(h);
-  if ((h->extra == kind) == on) return 0;
+  if ((h->extra == kind) == on && !(on && kind == EXTRA_PATH_BINS)) return 0;
   const ExtraWords &w = kExtraWords[kind];
-  if (on && h->extra != EXTRA_NONE) {   // the other kind's block lies in the same place
+  if (on && h->extra != EXTRA_NONE && h->extra != kind) {   // the other kind's block lies in the same place
     const ExtraWords &o = kExtraWords[h->extra];
     return h->fail(std::string(w.setter) + ": " + o.noun + " " + o.are + " switched on and " + o.their + " block lies where " + w.possessive +
                    " would; switch " + o.them + " off first (no kernel tallies both)");
@@ -246,6 +251,7 @@ static int set_extra_tally(i3rc_hip_integrator *h, ExtraTally kind, bool on) {
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));   // (launches in flight add to the buffer that is about to be replaced)
   h->extra = on ? kind : EXTRA_NONE;
+  h->pathBins = on ? nBins : 0;
   return realloc_tally(h);
 }
 
@@ -605,6 +611,51 @@ int i3rc_hip_get_path_length_layout(const i3rc_hip_integrator *h, int64_t *up1, 
   return 0;
 }
 
+int i3rc_hip_set_path_histogram(i3rc_hip_integrator *h, int nBins, const float *edges) {
+  if (!h) return 1;
+  if (nBins == 0) {
+    if (h->extra != EXTRA_PATH_BINS) { drop_lookahead(h); return 0; }
+    if (set_extra_tally(h, EXTRA_PATH_BINS, false)) return 1;
+    h->binEdges.clear();
+    return 0;
+  }
+  // (bad bins are refused before anything is touched: a histogram that is on stays on, with the bins it had)
+  const std::string who = "i3rc_hip_set_path_histogram: ";
+  if (nBins < 0 || nBins > kMaxPathBins) return h->fail(who + "1 <= nBins <= " + std::to_string(kMaxPathBins) + " required (0 switches the histogram off); got " + std::to_string(nBins));
+  if (!edges) return h->fail(who + "null edges (nBins + 1 float32 values)");
+  for (int b = 0; b <= nBins; ++b)
+    if (!std::isfinite(edges[b])) return h->fail(who + "edges must be finite; edges[" + std::to_string(b) + "] is not");
+  if (edges[0] != 0.0f) return h->fail(who + "edges[0] must be 0 (a path length is never below it)");
+  for (int b = 0; b < nBins; ++b)
+    if (!(edges[b] < edges[b + 1]))
+      return h->fail(who + "edges must be strictly ascending; edges[" + std::to_string(b + 1) + "] is not above edges[" + std::to_string(b) + "]");
+  if (set_extra_tally(h, EXTRA_PATH_BINS, true, nBins)) return 1;
+  h->binEdges.assign(edges, edges + nBins + 1);
+  std::vector<float> table((size_t)nBins + 2);
+  std::memcpy(&table[0], &nBins, sizeof(float));   // (word 0: nBins as an integer)
+  std::copy(edges, edges + nBins + 1, table.begin() + 1);
+  const hipError_t e = h->dBins.upload(table.data(), sizeof(float) * table.size());
+  if (e != hipSuccess) {   // (no kernel may run without its table: off again)
+    (void)set_extra_tally(h, EXTRA_PATH_BINS, false);
+    h->binEdges.clear();
+    return h->hipfail("i3rc_hip_set_path_histogram: uploading the bin edges", e);
+  }
+  return 0;
+}
+
+int i3rc_hip_get_path_histogram_layout(const i3rc_hip_integrator *h, int64_t *binUp, int64_t *binPathUp, int64_t *binDown, int64_t *binPathDown,
+                                       int64_t *nBins, int64_t *total) {
+  if (!h) return 1;
+  const bool on = h->extra == EXTRA_PATH_BINS;
+  const int64_t block = extra_block_offset(h->layout.counters);
+  int64_t *const out[4] = {binUp, binPathUp, binDown, binPathDown};
+  for (int f = 0; f < 4; ++f)
+    if (out[f]) *out[f] = on ? block + path_bin_field(f, h->pathBins) : -1;
+  if (nBins) *nBins = on ? h->pathBins : 0;
+  if (total) *total = h->layout.total;
+  return 0;
+}
+
 /* Tunables for experiments (not part of the reference API): event-phase ballot threshold, blocks per CU. */
 int i3rc_hip_set_tuning(i3rc_hip_integrator *h, int evThreshold, int blocksPerCU) {
   if (!h) return 1;
@@ -816,13 +867,15 @@ int make_problem(i3rc_hip_integrator *h, const LaunchDecision &d, DevProblem &P,
   P.limitContrib = h->params.limitIntensityContributions; P.zetaMin = h->params.zetaMin;
   P.maxContrib = h->params.maxIntensityContribution; P.maxExt = h->maxExt;
   P.dirCos = (const float *)h->dDir.p;
+  // (the path histogram's launches have no radiance directions -- extra_tally_refused --: the pointer carries the bin table, BinTable)
+  if (h->extra == EXTRA_PATH_BINS && h->nDir == 0) P.dirCos = (const float *)h->dBins.p;
   P.uniformSsa = h->uniformSsa; P.uniformPf = h->uniformPf;
   P.tally = tally;
   const TallyView &V = h->view;
   P.oUp = (int)V.fluxUp; P.oDown = (int)V.fluxDown; P.oAbs = (int)V.fluxAbsorbed; P.oVol = (int)V.volumeAbsorption;
   P.oInt = (int)V.intensityByComponent; P.oExc = (int)V.intensityExcess; P.oCnt = (int)V.counters;
   P.rayQueueCap = d.rayQueueCap;
-  P.ldsTallies = d.ldsTallies; P.ldsVolume = d.ldsVolume; P.ldsIntensity = d.ldsIntensity; P.ldsGrid = d.ldsGrid;
+  P.ldsTallies = d.ldsTallies; P.ldsVolume = d.ldsVolume; P.ldsIntensity = d.ldsIntensity; P.ldsGrid = d.ldsGrid | (d.ldsBins ? kLdsGridBinSums : 0);
   return 0;
 }
 
@@ -908,6 +961,7 @@ constexpr const char *rng_name() {
   if constexpr (Rng::kExtra == EXTRA_LEVELS) return "PhiloxLevelStream";
   else if constexpr (Rng::kExtra == EXTRA_TRACKS) return "PhiloxTrackStream";
   else if constexpr (Rng::kExtra == EXTRA_PATHS) return "PhiloxPathStream";
+  else if constexpr (Rng::kExtra == EXTRA_PATH_BINS) return "PhiloxBinStream";
   else if constexpr (Rng::kReplay) return "ReplayStream";
   else if constexpr (Rng::kBatched) return "PhiloxBatchStream";
   else return "PhiloxStream";
@@ -974,6 +1028,11 @@ std::string no_path_moments_text() {
   return "path lengths have no batch statistics; the diagnostic moments' layout has no slot for them (switch them off, or call "
          "i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)";
 }
+// (nor has the path histogram)
+std::string no_bin_moments_text() {
+  return "the path histogram has no batch statistics; the diagnostic moments' layout has no slot for it (switch it off, or call "
+         "i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)";
+}
 int extra_tally_refused(i3rc_hip_integrator *h, const char *who, bool batches) {
   if (h->extra == EXTRA_NONE) return 0;
   const ExtraWords &w = kExtraWords[h->extra];
@@ -1005,6 +1064,7 @@ int launch_grid(i3rc_hip_integrator *h, const Launch &L, RunArgs &A, hipStream_t
   const void *fn = (const void *)kern->fn;
   h->lastKernelName = kern->name;
   plan_words(*h, L.d, fusedBatches, h->lastPlan);
+  h->lastPlanBins = L.d.ldsBins;
   int perCU = h->blocksPerCU;
   if (perCU <= 0) {
     int occ = 0;
@@ -1546,6 +1606,7 @@ int begin_batch_loop(i3rc_hip_integrator *h, const std::string &who, bool argsOk
     return h->fail(who + ": no diagnostic tally is switched on (i3rc_hip_set_level_fluxes or i3rc_hip_set_actinic_flux first; "
                    "i3rc_hip_run_batches_moments serves a loop without one)");
   if (diagnostic && h->extra == EXTRA_PATHS) return h->fail(who + ": " + no_path_moments_text());
+  if (diagnostic && h->extra == EXTRA_PATH_BINS) return h->fail(who + ": " + no_bin_moments_text());
   if (src->kind != 0) return h->fail(who + ": Directional photon streams only (explicit streams differ from batch to batch)");
   if (nPhotons <= 0) return h->fail((diagnostic ? who + ": " : "") + "setIllumination: must ask for non-negative number of photons.");
   if (extra_tally_refused(h, who.c_str(), !diagnostic)) return 1;
@@ -1662,6 +1723,7 @@ int i3rc_hip_diagnostic_moments_layout_words(int kind, int nx, int ny, int nz, i
 int i3rc_hip_get_diagnostic_moments_layout(const i3rc_hip_integrator *h, i3rc_diagnostic_moments_layout *layout) {
   if (!h || !layout) return 1;
   if (h->extra == EXTRA_PATHS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_get_diagnostic_moments_layout: " + no_path_moments_text());
+  if (h->extra == EXTRA_PATH_BINS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_get_diagnostic_moments_layout: " + no_bin_moments_text());
   const ExtraMomentsLayout L = extra_moments_layout(h->extra, h->nx, h->ny, h->nz);
   layout->kind = (int64_t)h->extra;
   layout->levelFluxUp = L.levelFluxUp; layout->levelFluxDown = L.levelFluxDown; layout->meanLevelFluxUp = L.meanLevelFluxUp;
@@ -1795,7 +1857,7 @@ int i3rc_hip_run_replay(i3rc_hip_integrator *h, int64_t nPhotons, const i3rc_sou
                         int32_t *fateOrder, int32_t *drawsUsed) {
   if (!h) return 1;
   if (!src || !randoms || !drawStart || nPhotons <= 0) return h->fail("i3rc_hip_run_replay: bad arguments");
-  if (h->extra == EXTRA_TRACKS || h->extra == EXTRA_PATHS) {
+  if (h->extra == EXTRA_TRACKS || h->extra == EXTRA_PATHS || h->extra == EXTRA_PATH_BINS) {
     const ExtraWords &w = kExtraWords[h->extra];
     return h->fail(std::string("i3rc_hip_run_replay: ") + w.noun + " " + w.are + " tallied by the production stream's kernels only; the replay build has no such kernel (switch " +
                    w.them + " off)");
@@ -1981,6 +2043,7 @@ const char *i3rc_hip_last_kernel_name(const i3rc_hip_integrator *h) { return h ?
 int i3rc_hip_last_plan(const i3rc_hip_integrator *h, int32_t *out, int n) {
   if (!h || !out) return 1;
   for (int k = 0; k < std::min(n, kPlanWords); ++k) out[k] = h->lastPlan[k];
+  if (n > kPlanBinWord) out[kPlanBinWord] = h->lastPlanBins;
   return 0;
 }
 
@@ -2039,6 +2102,16 @@ int i3rc_hip_normalise_path_lengths(const i3rc_hip_integrator *h, const double *
   return 0;
 }
 
+int i3rc_hip_normalise_path_histogram(const i3rc_hip_integrator *h, const double *t, float *up, float *pathUp, float *down, float *pathDown) {
+  if (!h || !t) return 1;
+  if (h->extra != EXTRA_PATH_BINS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_path_histogram: the path histogram is not switched on");
+  const long long block = extra_block_offset(h->layout.counters);
+  float *const out[4] = {up, pathUp, down, pathDown};   // (as the block is laid out)
+  for (int f = 0; f < 4; ++f)
+    for (int b = 0; out[f] && b <= h->pathBins; ++b) out[f][b] = normalised_path_bin(t, h->layout.counters, block + path_bin_field(f, h->pathBins) + b);
+  return 0;
+}
+
 int i3rc_hip_normalise_actinic_flux(const i3rc_hip_integrator *h, const double *t, float *actinicFlux) {
   if (!h || !t || !actinicFlux) return 1;
   if (h->extra != EXTRA_TRACKS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_actinic_flux: the actinic flux is not switched on");
@@ -2053,12 +2126,13 @@ int i3rc_hip_normalise_actinic_flux(const i3rc_hip_integrator *h, const double *
 namespace {
 // The launch of the general flux kernel under the tag of the handle's extra tally block, through the one path every plain launch
 // takes (defined last, so that these kernels are instantiated behind every other kernel of the library: the level kernels, then the
-// track kernels, then the path kernels).
+// track kernels, then the path kernels, then the histogram kernels).
 int launch_extra(i3rc_hip_integrator *h, const Launch &L, const RunArgs &A, hipStream_t stream, bool timeIt) {
   switch (h->extra) {
     case EXTRA_LEVELS: return launch<PhiloxLevelStream>(h, L, A, stream, timeIt);
     case EXTRA_TRACKS: return launch<PhiloxTrackStream>(h, L, A, stream, timeIt);
     case EXTRA_PATHS: return launch<PhiloxPathStream>(h, L, A, stream, timeIt);
+    case EXTRA_PATH_BINS: return launch<PhiloxBinStream>(h, L, A, stream, timeIt);
     case EXTRA_NONE: break;
   }
   return h->fail("internal: no extra tally block is switched on");
@@ -2072,7 +2146,8 @@ const KernelEntry *find_kernel(const StreamKind &s, const KernelKey &key) {
   const std::vector<KernelEntry> &list = s.replay ? stream_kernels<ReplayStream>() : s.batched ? stream_kernels<PhiloxBatchStream>()
                                          : s.extra == EXTRA_LEVELS ? stream_kernels<PhiloxLevelStream>()
                                          : s.extra == EXTRA_TRACKS ? stream_kernels<PhiloxTrackStream>()
-                                         : s.extra == EXTRA_PATHS ? stream_kernels<PhiloxPathStream>() : stream_kernels<PhiloxStream>();
+                                         : s.extra == EXTRA_PATHS ? stream_kernels<PhiloxPathStream>()
+                                         : s.extra == EXTRA_PATH_BINS ? stream_kernels<PhiloxBinStream>() : stream_kernels<PhiloxStream>();
   for (const KernelEntry &e : list)
     if (e.key == key) return &e;
   return nullptr;
@@ -2103,10 +2178,12 @@ int i3rc_hip_problem_facts(int nx, int ny, int nz, int ncomp, const float *xEdge
 
 /* Host only: what a launch of `kind` would be on a problem of these facts (i3rc_hip_problem_facts), this setup -- binding.SETUP_NAMES:
  * what the setters and the handle's knobs add -- and these switches of the process (binding.ENV_NAMES; NULL: the process's own).
- * kind: the stream (0 plain, 1 fused, 2 replay, 3 level tally, 4 track tally, 5 path tally), the kind of the source, the batches of a fused launch. */
+ * kind: the stream (0 plain, 1 fused, 2 replay, 3 level tally, 4 track tally, 5 path tally, 6 path histogram), the kind of the source, the batches of a
+ * fused launch and -- read for stream 6 only -- the histogram's bins. */
 int i3rc_hip_plan_launch(const int32_t *facts, const int32_t *setup, const int32_t *env, const int32_t *kind, int32_t *out, int nout,
                          char *text, int ntext) {
-  if (!facts || !setup || !kind || !out || !text || ntext < 1 || kind[0] < 0 || kind[0] > 5 || facts[3] < 1) return 2;
+  if (!facts || !setup || !kind || !out || !text || ntext < 1 || kind[0] < 0 || kind[0] > 6 || facts[3] < 1) return 2;
+  if (kind[0] == 6 && (kind[3] < 1 || kind[3] > kMaxPathBins)) return 2;
   ProblemFacts f;
   f.nx = facts[0]; f.ny = facts[1]; f.nz = facts[2]; f.ncomp = facts[3]; f.xyRegular = facts[4]; f.zRegular = facts[5]; f.empty = facts[6] != 0;
   f.absorbing = facts[7] != 0; f.uniformSsa = facts[8] ? 0.5f : -1.f; f.uniformPf = facts[9]; f.cellRecBytes = facts[10];
@@ -2120,17 +2197,18 @@ int i3rc_hip_plan_launch(const int32_t *facts, const int32_t *setup, const int32
   f.comp.assign(f.ncomp, t); f.nInvEntries.assign(f.ncomp, setup[4]); f.nFwdEntries.assign(f.ncomp, 0);
   f.params.useSurfaceBDRF = setup[5]; f.params.useRayTracing = setup[6]; f.nxs = setup[7]; f.nys = setup[8]; f.surfaceSet = setup[9] != 0;
   f.extra = (ExtraTally)setup[10]; f.kernelVariant = setup[11]; f.gridPlace = setup[12]; f.ldsTalliesOn = setup[13] != 0;
+  f.pathBins = kind[0] == 6 ? kind[3] : 0;
   const StreamKind s = kind[0] == 2 ? stream_of<ReplayStream>() : kind[0] == 1 ? stream_of<PhiloxBatchStream>()
-                                                                : plain_stream(kind[0] == 3 ? EXTRA_LEVELS : kind[0] == 4 ? EXTRA_TRACKS : kind[0] == 5 ? EXTRA_PATHS : EXTRA_NONE);
+                                                                : plain_stream(kind[0] == 3 ? EXTRA_LEVELS : kind[0] == 4 ? EXTRA_TRACKS : kind[0] == 5 ? EXTRA_PATHS : kind[0] == 6 ? EXTRA_PATH_BINS : EXTRA_NONE);
   const LaunchDecision d = plan_launch(f, env_from_words(env), {s, kind[1]});
   const KernelEntry *kern = d.refusal.empty() ? find_kernel(s, d.key) : nullptr;
   const std::string say = !d.refusal.empty() ? d.refusal : kern ? kern->name : no_kernel_text(s.batched);
   std::snprintf(text, (size_t)ntext, "%s", say.c_str());
   if (!kern) return 1;
-  int32_t v[kPlanWords + 3];
+  int32_t v[kPlanWords + 4];
   plan_words(f, d, kind[2], v);
-  v[kPlanWords] = (int32_t)d.estimate; v[kPlanWords + 1] = d.rayQueueCap; v[kPlanWords + 2] = d.threads;
-  for (int k = 0; k < std::min(nout, kPlanWords + 3); ++k) out[k] = v[k];
+  v[kPlanWords] = (int32_t)d.estimate; v[kPlanWords + 1] = d.rayQueueCap; v[kPlanWords + 2] = d.threads; v[kPlanWords + 3] = d.ldsBins;
+  for (int k = 0; k < std::min(nout, kPlanWords + 4); ++k) out[k] = v[k];
   return 0;
 }
 

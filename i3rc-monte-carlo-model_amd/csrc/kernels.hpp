@@ -297,6 +297,40 @@ __device__ __forceinline__ void path_add(double *block, int ncol, bool up, int c
   add_global(at + ncol, wl * length);
 }
 
+// THE PATH HISTOGRAM of the same light (EXTRA_PATH_BINS, PhiloxBinStream): the same float64 path register, and at the same two places
+// -- instead of two sums per column -- the weight and weight x path into the bin of float(L) (path_bin, tally_block.hpp: a search of
+// fixed trip count over the float32 edges), domain-wide: binUp | binPathUp | binDown | binPathDown, nBins + 1 float64 words each, the
+// last the overflow bin.  nBins and the edges travel in the device buffer DevProblem::dirCos points to in such a launch (the launch
+// has no radiance directions: nDir == 0, and nothing else reads the pointer): word 0 nBins, then the nBins + 1 edges (BinTable).
+// Where the launch's LDS has room (bit 2 of DevProblem::ldsGrid, plan_launch) a workgroup keeps the 4 (nBins + 1) sums as float64
+// partial sums behind lds_plan's end -- at track_sums_word, as the track sums -- with the edges behind them: two ds_add_f64 per tally
+// and one global float64 atomic per non-zero word at the workgroup's end, at any place of the extinction field.  Elsewhere: two float64
+// atomics in global memory, the edges read from device memory.
+constexpr int kLdsGridBinSums = 4;   // DevProblem::ldsGrid, bit 2 (launches of photon_kernel<PhiloxBinStream, ...> only)
+// the region's length in float words for nBins bins -- the host's allocation and the kernel's carve-up both
+__host__ __device__ inline int bin_region_words(int nBins) { return 2 * 4 * (nBins + 1) + (nBins + 1); }
+// (what a wave keeps of it in scalar registers: the table itself is read through the kernel argument where it is needed)
+struct BinTable {
+  int nBins = 0;
+  lds_f64 *sums = nullptr;           // the workgroup's partial sums (nullptr: the block in global memory is added to), its copy of the edges behind them
+  // (the host has checked 1 <= nBins <= kMaxPathBins; the clamp keeps a kernel that reads anything else inside its LDS region and block)
+  __device__ __forceinline__ void load(const float *table) { nBins = min(max(__builtin_amdgcn_readfirstlane(__float_as_int(table[0])), 1), kMaxPathBins); }
+  __device__ __forceinline__ lds_float *lds_edges() const { return (lds_float *)(sums + 4 * (nBins + 1)); }
+};
+__device__ __forceinline__ void bin_add(const BinTable &B, const float *table, double *block, bool up, float weight, double length) {
+  const float x = (float)length;
+  const int b = B.sums ? path_bin(B.lds_edges(), B.nBins, x) : path_bin(table + 1, B.nBins, x);
+  const unsigned at = (unsigned)path_bin_field(up ? 0 : 2, B.nBins) + (unsigned)b;   // (path_bin clamps: never outside the block)
+  const double wv = (double)weight, wl = wv * length;
+  if (B.sums) {
+    (void)__hip_atomic_fetch_add(B.sums + at, wv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ds_add_f64
+    (void)__hip_atomic_fetch_add(B.sums + at + (B.nBins + 1), wl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  } else {
+    add_global(block + at, wv);
+    add_global(block + at + (B.nBins + 1), wl);
+  }
+}
+
 // Wave-private reservoir of photon indices: one returning atomic per `chunk` photons instead of one per respawn
 // round (the returning atomic costs microseconds; every wave would pay it in ~97 % of its event phases).  The two
 // bounds are wave-uniform and held in scalar registers (readfirstlane tells the compiler so).
@@ -500,6 +534,8 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   lds_float *startSlots = nullptr;   // STORE: this wave's start store (StartSlot, tracer.hpp)
   constexpr bool TRACK = Rng::kExtra == EXTRA_TRACKS;   // actinic flux by track length (PhiloxTrackStream): tallied by the general flux kernel only
   lds_f64 *trackSums = nullptr;      // TRACK: the workgroup's partial sums of the block (nullptr: the block in global memory is added to)
+  constexpr bool BINS = Rng::kExtra == EXTRA_PATH_BINS;   // the path histogram (PhiloxBinStream): tallied by the general flux kernel only
+  BinTable bins;                     // BINS: the bins, and where this workgroup adds to them (bin_add)
   {
     // (one carve-up for the kernel and for the host's allocation: lds_plan, tracer.hpp)
     const LdsPlan lp = lds_plan(P, INTENSITY && !Rng::kReplay, DIRECT, GRID, INTENSITY, TBL ? 16 : 4, 0, STORE);
@@ -512,7 +548,16 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
     L.tInt = (lds_tally *)(base + lp.tInt); L.ext = base + lp.ext; L.cosTab = base + lp.cosTab;
     if constexpr (TRACK && GRID == GRID_LDS)
       if (P.ldsGrid & kLdsGridTrackSums) trackSums = (lds_f64 *)(base + track_sums_word(lp.end));
+    if constexpr (BINS) {
+      bins.load(P.dirCos);
+      if (P.ldsGrid & kLdsGridBinSums) bins.sums = (lds_f64 *)(base + track_sums_word(lp.end));
+    }
   }
+  if constexpr (BINS)
+    if (bins.sums != nullptr) {
+      for (int i = threadIdx.x; i < 4 * (bins.nBins + 1); i += blockDim.x) bins.sums[i] = 0.0;
+      for (int i = threadIdx.x; i <= bins.nBins; i += blockDim.x) bins.lds_edges()[i] = P.dirCos[1 + i];
+    }
   if constexpr (TRACK)
     if (trackSums != nullptr)
       for (int i = threadIdx.x; i < P.nx * P.ny * P.nz; i += blockDim.x) trackSums[i] = 0.0;
@@ -559,7 +604,8 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   static_assert(!LEVELS || (GENERAL && !INTENSITY && !TBL && !DIRECT && !MULTI), "level fluxes: the general flux kernel");
   static_assert(!TRACK || (GENERAL && !INTENSITY && !TBL && !DIRECT && !MULTI && !STORE && !BATCHED && !REPLAY && !LEVELS),
                 "track lengths: the general flux kernel, no start store, not batched");
-  constexpr bool PATH = Rng::kExtra == EXTRA_PATHS;   // path-length moments (PhiloxPathStream): tallied by the general flux kernel only
+  // path-length moments (PhiloxPathStream) and the path histogram (PhiloxBinStream): the lane keeps its photon's path; tallied by the general flux kernel only
+  constexpr bool PATH = Rng::kExtra == EXTRA_PATHS || BINS;
   static_assert(!PATH || (GENERAL && !INTENSITY && !TBL && !DIRECT && !MULTI && !STORE && !BATCHED && !REPLAY),
                 "path lengths: the general flux kernel, no start store, not batched");
   static_assert(!MULTI || (!GENERAL && !TBL && !Rng::kReplay && (INTENSITY || BATCHED)), "MULTI: the widened class -- radiance kernels, and the fused flux kernels (plain flux launches of the class run the general flux kernel)");
@@ -1158,7 +1204,8 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           }
           const int c2 = (r.iy - 1) * Pe.nx + (r.ix - 1);
           tally.boundary(atTop, c2, w);
-          if constexpr (PATH) path_add(extra_block(tally.base(), Pe.oCnt), Pe.nx * Pe.ny, atTop, c2, w, pathLen);
+          if constexpr (BINS) bin_add(bins, Pe.dirCos, extra_block(tally.base(), Pe.oCnt), atTop, w, pathLen);
+          else if constexpr (PATH) path_add(extra_block(tally.base(), Pe.oCnt), Pe.nx * Pe.ny, atTop, c2, w, pathLen);
           if (REPLAY) { fateCol = c2; fateW = w; }
         }
         if (REPLAY) {
@@ -1385,7 +1432,8 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
             r.z = surfaceZ;
             const int c2 = (r.iy - 1) * Pe.nx + (r.ix - 1);
             tally.down(c2, w);
-            if constexpr (PATH) path_add(extra_block(tally.base(), Pe.oCnt), Pe.nx * Pe.ny, false, c2, w, pathLen);   // (the weight before the reflection, the path up to here)
+            if constexpr (BINS) bin_add(bins, Pe.dirCos, extra_block(tally.base(), Pe.oCnt), false, w, pathLen);   // (the weight before the reflection, the path up to here)
+            else if constexpr (PATH) path_add(extra_block(tally.base(), Pe.oCnt), Pe.nx * Pe.ny, false, c2, w, pathLen);   // (likewise)
             if (REPLAY) { fateCol = c2; fateW = w; }
             float mu = exact_sqrt(rng.first());
             while (!(fabsf(mu) > 2.0f * kTiny)) mu = exact_sqrt((GENERAL || MULTI) ? rng.next() : rng.fresh());   // :546-549
@@ -1681,6 +1729,14 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
         const int ncellT = ka->P.nx * ka->P.ny * ka->P.nz;
         for (int i = threadIdx.x; i < ncellT; i += blockDim.x) {
           const double v = trackSums[i];
+          if (v != 0.0) add_global(block + i, v);
+        }
+      }
+    if constexpr (BINS)
+      if (bins.sums != nullptr) {
+        double *const block = extra_block(out, ka->P.oCnt);
+        for (int i = threadIdx.x; i < 4 * (bins.nBins + 1); i += blockDim.x) {
+          const double v = bins.sums[i];
           if (v != 0.0) add_global(block + i, v);
         }
       }

@@ -68,6 +68,7 @@ struct ProblemFacts {
   int nxs = 0, nys = 0;
   bool surfaceSet = false;   // (i3rc_hip_set_surface)
   ExtraTally extra = EXTRA_NONE;   // set_extra_tally: the block plain flux launches also fill, behind the counters (tally_block.hpp)
+  int pathBins = 0;                // ... and, while it is EXTRA_PATH_BINS, the histogram's bins (i3rc_hip_set_path_histogram), else 0
   // the handle's knobs
   int kernelVariant = I3RC_KERNEL_AUTO;  // test / tuning knob (i3rc_hip_select_kernel)
   int gridPlace = I3RC_GRID_AUTO;        // test / tuning knob (i3rc_hip_select_grid_place)
@@ -217,7 +218,8 @@ inline bool direct_rays(const ProblemFacts &f, const EnvKnobs &env) {
   return env.direct && f.nDir == 1 && f.kernelVariant != I3RC_KERNEL_RING && !kNestedBuild;
 }
 
-// its stream -- what the Rng template argument of photon_kernel carries: plain (all false), fused, replay, level tally, track tally, path tally -- ...
+// its stream -- what the Rng template argument of photon_kernel carries: plain (all false), fused, replay, level tally, track tally, path tally,
+// path histogram -- ...
 struct StreamKind {
   bool replay, batched;
   ExtraTally extra;
@@ -229,6 +231,7 @@ inline StreamKind plain_stream(ExtraTally extra) {   // (of a plain launch: the 
   return extra == EXTRA_LEVELS   ? stream_of<PhiloxLevelStream>()
          : extra == EXTRA_TRACKS ? stream_of<PhiloxTrackStream>()
          : extra == EXTRA_PATHS  ? stream_of<PhiloxPathStream>()
+         : extra == EXTRA_PATH_BINS ? stream_of<PhiloxBinStream>()
                                  : stream_of<PhiloxStream>();
 }
 // ... and the kind of its source (i3rc_source::kind, RunArgs::srcKind)
@@ -269,6 +272,8 @@ struct LaunchDecision {
   int place = GRID_GLOBAL;   // GridPlace: where the kernels read the extinction field; the packed form passed is the place's
   int ldsTallies = 0, ldsVolume = 0, ldsIntensity = 0, rayQueueCap = 0;
   int ldsGrid = 0;           // (bit 1, kLdsGridTrackSums: the track-length sums in LDS)
+  int ldsBins = 0;           // the path histogram's sums and edges in LDS (photon_kernel, BINS; DevProblem::ldsGrid's bit 2, kLdsGridBinSums) ...
+  int pathBins = 0;          // ... and its bins, which size that region (bin_region_words)
   KernelKey key{};           // (key.tbl: the inverse table in LDS)
   int threads = 256;
   bool startStore = false;   // the kernel starts its photons from per-wave start stores in LDS (photon_kernel, STORE)
@@ -296,6 +301,8 @@ inline size_t lds_bytes(const LaunchDecision &d, const StreamKind &s, bool direc
   size_t words = (size_t)lp.end;
   if (s.extra == EXTRA_TRACKS)   // the track-length sums behind the plan's end (photon_kernel, TRACK)
     if (d.ldsGrid & kLdsGridTrackSums) words = (size_t)track_sums_word(lp.end) + 2 * (size_t)d.nx * d.ny * d.nz;
+  if (s.extra == EXTRA_PATH_BINS && d.ldsBins)   // the histogram's sums and edges, in the same place (photon_kernel, BINS)
+    words = (size_t)track_sums_word(lp.end) + (size_t)bin_region_words(d.pathBins);
   return (sizeof(float) * words + 15) & ~(size_t)15;
 }
 
@@ -321,7 +328,7 @@ inline LaunchDecision plan_launch(const ProblemFacts &f, const EnvKnobs &env, co
     return refuse("computeRadiativeTransfer: surfaceBDRF requested but no surface description set", true);
   {
     i3rc_tally_layout layout; TallyView view;
-    (void)tally_layout(f.nx, f.ny, f.nz, f.ncomp, f.nDir, f.extra, layout, view);
+    (void)tally_layout(f.nx, f.ny, f.nz, f.ncomp, f.nDir, f.extra, layout, view, f.pathBins);
     if (layout.total >= ((int64_t)1 << 31)) return refuse("tally buffer too large (2^31 elements or more)", true);
   }
   const size_t ncol = (size_t)f.nx * f.ny, ncell = ncol * f.nz;
@@ -369,6 +376,14 @@ inline LaunchDecision plan_launch(const ProblemFacts &f, const EnvKnobs &env, co
   if (s.extra == EXTRA_TRACKS && place == GRID_LDS && env.ldsTallies && f.ldsTalliesOn) {
     d.ldsGrid |= kLdsGridTrackSums;
     if (lds_bytes(d, s, direct, nInv, false, false) > kLdsLaunchMax) d.ldsGrid &= ~kLdsGridTrackSums;
+  }
+  // The path histogram (photon_kernel, BINS): at ANY place of the field, where partial sums in LDS are switched on and the launch's
+  // allocation with the region -- 4 (nBins + 1) float64 sums and the nBins + 1 edges behind the plan's end -- stays within the budget of a
+  // workgroup, the workgroups keep their sums there; else the launch adds to the block in global memory.  Never a refusal.
+  if (s.extra == EXTRA_PATH_BINS) {
+    d.pathBins = f.pathBins;
+    d.ldsBins = env.ldsTallies && f.ldsTalliesOn && f.pathBins >= 1;
+    if (d.ldsBins && lds_bytes(d, s, direct, nInv, false, false) > kLdsBudget) d.ldsBins = 0;
   }
   // Which kernel runs the launch (see photon_kernel).  Fused launches (PhiloxBatchStream) are made for the specialised problems only
   // (fuse_loop): the common class, or the widened one.  Plain launches run the specialised kernels when the problem is in the common
@@ -429,6 +444,9 @@ inline LaunchDecision plan_launch(const ProblemFacts &f, const EnvKnobs &env, co
 
 // what i3rc_hip_last_plan reports of a launch (binding.PLAN_NAMES); the chunk -- word kPlanChunk -- is known once the grid is (launch_grid)
 constexpr int kPlanWords = 13, kPlanChunk = 11;
+// (a fourteenth word, for callers that ask for it: the path histogram's sums in LDS -- binding.PLAN_BIN_NAME; it follows the thirteen in
+// i3rc_hip_last_plan and the three of PLAN_EXTRA_NAMES in i3rc_hip_plan_launch, so that no earlier word moves)
+constexpr int kPlanBinWord = kPlanWords;
 constexpr int kFactWords = 23;   // the words of i3rc_hip_problem_facts (binding.FACT_NAMES)
 inline void plan_words(const ProblemFacts &f, const LaunchDecision &d, int fusedBatches, int32_t *v) {
   const int32_t w[kPlanWords] = {d.ldsGrid ? 1 : 0, d.ldsTallies, d.ldsVolume, d.ldsIntensity, d.key.tbl ? 1 : 0, (int32_t)d.ldsBytes, f.absorbing ? 1 : 0,

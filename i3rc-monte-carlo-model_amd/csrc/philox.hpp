@@ -187,6 +187,7 @@ struct PhiloxBatchStream : PhiloxStreamT<true> {};
 struct PhiloxLevelStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_LEVELS; };
 struct PhiloxTrackStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_TRACKS; };
 struct PhiloxPathStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_PATHS; };
+struct PhiloxBinStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_PATH_BINS; };   // (nor does it contain "PhiloxPathStream")
 
 // Test stream: deviates come from a buffer (the reference's MT19937 floats); see i3rc_hip_run_replay.
 struct ReplayStream {

@@ -32,20 +32,53 @@ enum ExtraTally {
   EXTRA_NONE,
   EXTRA_LEVELS,   // levelFluxUp | levelFluxDown, [nz + 1][ny][nx] each (i3rc_hip_set_level_fluxes)
   EXTRA_TRACKS,   // the actinic flux's track-length sums, [nz][ny][nx] (i3rc_hip_set_actinic_flux)
-  EXTRA_PATHS     // pathUp1 | pathUp2 | pathDown1 | pathDown2, [ny][nx] each: the sums of w L and w L^2 over the photons that fluxUp / fluxDown count,
+  EXTRA_PATHS,    // pathUp1 | pathUp2 | pathDown1 | pathDown2, [ny][nx] each: the sums of w L and w L^2 over the photons that fluxUp / fluxDown count,
                   // L the geometric path since the photon's start (i3rc_hip_set_path_lengths)
+  EXTRA_PATH_BINS // binUp | binPathUp | binDown | binPathDown, nBins + 1 words each, domain-wide: the sums of w and of w L over the same photons, by the
+                  // bin of L (path_bin below; the last word of each field is the overflow bin) (i3rc_hip_set_path_histogram)
 };
+constexpr int kMaxPathBins = 1024;   // (i3rc_hip_set_path_histogram: 1 <= nBins <= 1024)
 I3RC_TALLY_FN long long extra_block_offset(long long countersOffset) { return countersOffset + I3RC_NUM_COUNTERS; }
-// ... and its length in float64 words
+// ... and its length in float64 words (of the kinds the grid sizes: the path histogram's block is sized by its bins, path_bin_block_words)
 I3RC_TALLY_FN long long extra_block_words(ExtraTally kind, int nx, int ny, int nz) {
   const long long ncol = (long long)nx * ny;
   return kind == EXTRA_LEVELS ? 2 * (nz + 1) * ncol : (kind == EXTRA_TRACKS ? ncol * nz : (kind == EXTRA_PATHS ? 4 * ncol : 0));
 }
 
+// THE PATH HISTOGRAM (EXTRA_PATH_BINS): nBins bins over nBins + 1 float32 edges -- edges[0] == 0, strictly ascending, finite -- and an
+// overflow bin behind them.  THE BIN RULE, for the host's tests and the kernel alike: a path L belongs to the bin b with
+// edges[b] <= float(L) < edges[b + 1], and to the overflow bin b = nBins where float(L) >= edges[nBins].  The search makes
+// ceil(log2(nBins + 1)) steps whatever L is -- no exit that depends on the data --, reads no edge beyond edges[nBins], and its answer is
+// clamped to 0 ... nBins, so that nothing is written outside the block (a NaN or a negative L falls into bin 0).
+// Edges: anything indexable that yields float (a host array, device memory, a pointer into LDS).
+template <class Edges>
+I3RC_TALLY_FN int path_bin(Edges edges, int nBins, float x) {
+  int trips = 0;
+  while ((nBins >> trips) != 0) ++trips;   // (the bits of nBins = ceil(log2(nBins + 1)))
+  int b = 0;
+  for (int k = trips - 1; k >= 0; --k) {
+    const int c = b + (1 << k);
+    const int at = c < nBins ? c : nBins;
+    const bool take = (c <= nBins) & (edges[at] <= x);
+    b = take ? c : b;
+  }
+  return b < 0 ? 0 : (b > nBins ? nBins : b);
+}
+// ... the block's length in float64 words, ...
+I3RC_TALLY_FN long long path_bin_block_words(int nBins) { return 4 * ((long long)nBins + 1); }
+// ... where the block's four fields begin (relative to the block), in float64 words: field 0 binUp, 1 binPathUp, 2 binDown, 3 binPathDown
+I3RC_TALLY_FN long long path_bin_field(int field, int nBins) { return (long long)field * ((long long)nBins + 1); }
+// ... and a word of the block as reportResults hands it out: per photon of the launch, domain-wide (so that the sum over binUp is the
+// domain's area-weighted mean fluxUp on every grid)
+I3RC_TALLY_FN float normalised_path_bin(const double *raw, long long countersOffset, long long at) {
+  return (float)(raw[at] / raw[countersOffset + I3RC_CNT_PHOTONS]);
+}
+
 // The packed tally buffer of a grid: the fields of i3rc_tally_layout one behind the other, then the extra block, so that switching it
 // moves no other offset.  Fills L, and V's offsets and sizes (levelUp / levelDown: -1 unless the block is EXTRA_LEVELS; pathUp1 ...
-// pathDown2: -1 unless it is EXTRA_PATHS); returns the extra block's offset, -1 without one.
-inline long long tally_layout(int nx, int ny, int nz, int ncomp, int nDir, ExtraTally extra, i3rc_tally_layout &L, TallyView &V) {
+// pathDown2: -1 unless it is EXTRA_PATHS); returns the extra block's offset, -1 without one.  (nBins: the path histogram's, see
+// path_bin_block_words; its fields lie at path_bin_field from the offset returned -- the view has no words for them)
+inline long long tally_layout(int nx, int ny, int nz, int ncomp, int nDir, ExtraTally extra, i3rc_tally_layout &L, TallyView &V, int nBins = 0) {
   const long long ncol = (long long)nx * ny;
   long long o = 0;
   L.fluxUp = o; o += ncol;
@@ -56,7 +89,7 @@ inline long long tally_layout(int nx, int ny, int nz, int ncomp, int nDir, Extra
   L.intensityExcess = o; o += (long long)(ncomp + 1) * nDir;
   L.counters = o; o += I3RC_NUM_COUNTERS;
   const long long block = extra == EXTRA_NONE ? -1 : extra_block_offset(L.counters);
-  L.total = o + extra_block_words(extra, nx, ny, nz);
+  L.total = o + (extra == EXTRA_PATH_BINS ? path_bin_block_words(nBins) : extra_block_words(extra, nx, ny, nz));
   V.fluxUp = L.fluxUp; V.fluxDown = L.fluxDown; V.fluxAbsorbed = L.fluxAbsorbed; V.volumeAbsorption = L.volumeAbsorption;
   V.intensityByComponent = L.intensityByComponent; V.intensityExcess = L.intensityExcess; V.counters = L.counters;
   V.levelUp = extra == EXTRA_LEVELS ? block : -1;

@@ -554,8 +554,9 @@ __device__ __forceinline__ float cell_extinction(const PR &P, const Lds &L, int 
 // (SHORT: the three proximity tests behind exec masks of their own -- see below; the photon steps of the ring kernels, whose 96 registers
 // the other form overran by two)
 // (LENGTH: the step also hands out, in *length, the path it advances inside the cell it began in -- `step`, or 0 in the arriving step,
-// whose length finish_arrival forms; a failed step leaves *length alone.  photon_kernel<PhiloxTrackStream, ...> and
-// photon_kernel<PhiloxPathStream, ...> alone ask for it: every other instantiation compiles to what it compiled to without the flag.)
+// whose length finish_arrival forms; a failed step leaves *length alone.  photon_kernel<PhiloxTrackStream, ...>,
+// photon_kernel<PhiloxPathStream, ...> and photon_kernel<PhiloxBinStream, ...> alone ask for it: every other instantiation compiles to
+// what it compiled to without the flag.)
 // (CHAIN: the minimum of the three quotients as a chain of `<` selects, which lets a NaN in stx through: for rays whose zero cosines
 // are marked in Ray::slow -- set_direction<true> --, so that the guarded path has replaced every such quotient.  Two instantiations
 // keep it: see photon_kernel.)

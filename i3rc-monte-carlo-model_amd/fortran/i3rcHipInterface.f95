@@ -247,6 +247,21 @@ module i3rcHipInterface
       type(c_ptr), value         :: pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown   ! (nx, ny) each
       integer(c_int)             :: rc
     end function
+    function i3rc_hip_set_path_histogram(h, nBins, edges) bind(C, name = "i3rc_hip_set_path_histogram") result(rc)
+      import
+      type(c_ptr), value        :: h
+      integer(c_int), value     :: nBins                         ! 0: off (edges is not read)
+      real(c_float), intent(in) :: edges(*)                      ! (nBins + 1)
+      integer(c_int)            :: rc
+    end function
+    function i3rc_hip_normalise_path_histogram(h, host, up, pathUp, down, pathDown) &
+             bind(C, name = "i3rc_hip_normalise_path_histogram") result(rc)
+      import
+      type(c_ptr), value         :: h
+      real(c_double), intent(in) :: host(*)
+      type(c_ptr), value         :: up, pathUp, down, pathDown   ! (nBins + 1) each
+      integer(c_int)             :: rc
+    end function
     function i3rc_hip_device_count() bind(C, name = "i3rc_hip_device_count") result(n)
       import
       integer(c_int) :: n

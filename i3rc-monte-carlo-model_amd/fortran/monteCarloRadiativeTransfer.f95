@@ -68,6 +68,11 @@ module monteCarloRadiativeTransfer
     ! length (squared) x incident flux (not in the reference)
     logical :: computePathLengths = .false.
     real, dimension(:, :, :),    pointer :: pathLengths => null()
+    ! ... and, with specifyParameters(pathHistogramEdges = edges), the distribution of that path length over the bins the edges bound
+    ! (nBins + 1, 4), the overflow bin last: pathHistogramUp, pathHistogramPathUp, pathHistogramDown, pathHistogramPathDown -- the bins'
+    ! shares of the domain's mean fluxUp / fluxDown and those times the bins' mean paths (not in the reference)
+    real, dimension(:),          pointer :: pathHistogramEdges => null()
+    real, dimension(:, :),       pointer :: pathHistogram => null()
     double precision :: photonsProcessed = 0.d0, photonsDropped = 0.d0
     ! raw tallies of the batches of the last computeRadiativeTransferBatches (one column per batch)
     real(c_double), dimension(:, :), pointer :: batchTallies => null()
@@ -174,7 +179,7 @@ contains
                                useHybridPhaseFunsForIntenCalcs, hybridPhaseFunWidth,   &
                                numOrdersOrigPhaseFunIntenCalcs,                        &
                                limitIntensityContributions, maxIntensityContribution,  &
-                               status, computeLevelFluxes, computeActinicFlux, computePathLengths)
+                               status, computeLevelFluxes, computeActinicFlux, computePathLengths, pathHistogramEdges)
     type(integrator),                   intent(inout) :: thisIntegrator
     real,                     optional, intent(in   ) :: surfaceAlbedo
     type(surfaceDescription), optional, intent(in   ) :: surfaceBDRF
@@ -195,6 +200,10 @@ contains
     logical,                  optional, intent(in   ) :: computeActinicFlux
     ! (likewise: the path-length moments of reflected and transmitted light, see reportResults)
     logical,                  optional, intent(in   ) :: computePathLengths
+    ! (likewise: the path-length histogram over these bin edges -- 0 first, strictly ascending --, see reportResults; an array of
+    ! size 0 switches it off)
+    real, dimension(:),       optional, intent(in   ) :: pathHistogramEdges
+    real(c_float) :: noEdges(1)
     integer :: i, nDir, nx, ny, nc
     real, dimension(:),    pointer :: xs, ys
     real, dimension(:, :), pointer :: albedoGrid
@@ -371,6 +380,26 @@ contains
         thisIntegrator%pathLengths = 0.
       end if
       thisIntegrator%computePathLengths = computePathLengths
+    end if
+    if(present(pathHistogramEdges)) then
+      if(size(pathHistogramEdges) == 1) then
+        call setStateToFailure(status, "specifyParameters: pathHistogramEdges needs at least two edges (one bin)")
+        return
+      end if
+      if(size(pathHistogramEdges) == 0) then
+        noEdges = 0.
+        if(.not. deviceCall(thisIntegrator, i3rc_hip_set_path_histogram(thisIntegrator%device, 0, noEdges), &
+                            "specifyParameters", status)) return
+      else
+        if(.not. deviceCall(thisIntegrator, i3rc_hip_set_path_histogram(thisIntegrator%device, size(pathHistogramEdges) - 1, &
+                            pathHistogramEdges), "specifyParameters", status)) return
+      end if
+      if(associated(thisIntegrator%pathHistogram)) deallocate(thisIntegrator%pathHistogram, thisIntegrator%pathHistogramEdges)
+      if(size(pathHistogramEdges) > 0) then
+        allocate(thisIntegrator%pathHistogramEdges(size(pathHistogramEdges)), thisIntegrator%pathHistogram(size(pathHistogramEdges), 4))
+        thisIntegrator%pathHistogramEdges = pathHistogramEdges
+        thisIntegrator%pathHistogram = 0.
+      end if
     end if
     call setStateToSuccess(status)
   end subroutine specifyParameters
@@ -621,6 +650,12 @@ contains
       ok = deviceCall(thisIntegrator, i3rc_hip_normalise_path_lengths(thisIntegrator%device, raw,                           &
                       c_loc(thisIntegrator%pathLengths(1, 1, 1)), c_loc(thisIntegrator%pathLengths(1, 1, 2)),                &
                       c_loc(thisIntegrator%pathLengths(1, 1, 3)), c_loc(thisIntegrator%pathLengths(1, 1, 4))), caller, status)
+      if(.not. ok) return
+    end if
+    if(associated(thisIntegrator%pathHistogram)) then
+      ok = deviceCall(thisIntegrator, i3rc_hip_normalise_path_histogram(thisIntegrator%device, raw,                         &
+                      c_loc(thisIntegrator%pathHistogram(1, 1)), c_loc(thisIntegrator%pathHistogram(1, 2)),                  &
+                      c_loc(thisIntegrator%pathHistogram(1, 3)), c_loc(thisIntegrator%pathHistogram(1, 4))), caller, status)
       if(.not. ok) return
     end if
     thisIntegrator%photonsProcessed = raw(layout%counters + 1 + I3RC_CNT_PHOTONS)
@@ -1068,7 +1103,8 @@ contains
   ! ------------------------------------------------------------------------------------------------
   subroutine reportResults(thisIntegrator, meanFluxUp, meanFluxDown, meanFluxAbsorbed, fluxUp, fluxDown, fluxAbsorbed, &
                            absorbedProfile, volumeAbsorption, meanIntensity, intensity, status, levelFluxUp, levelFluxDown, &
-                           actinicFlux, pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown)
+                           actinicFlux, pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown, &
+                           pathHistogramUp, pathHistogramPathUp, pathHistogramDown, pathHistogramPathDown)
     type(integrator),                   intent(in   ) :: thisIntegrator
     real,                     optional, intent(  out) :: meanFluxUp, meanFluxDown, meanFluxAbsorbed
     real, dimension(:, :),    optional, intent(  out) :: fluxUp, fluxDown, fluxAbsorbed
@@ -1084,6 +1120,9 @@ contains
     ! (likewise) (nx, ny): the sums of w L and w L**2 over the photons fluxUp / fluxDown count, L the geometric path since the photon's
     ! start, normalised as fluxUp is: pathLengthUp / fluxUp is the mean path of a column's reflected light
     real, dimension(:, :),    optional, intent(  out) :: pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown
+    ! (likewise) (nBins + 1), the overflow bin last: the sums of w and of w L over the same photons by the bin of L, per photon of the
+    ! run and domain-wide: sum(pathHistogramUp) is the domain's mean fluxUp, pathHistogramPathUp / pathHistogramUp a bin's mean path
+    real, dimension(:),       optional, intent(  out) :: pathHistogramUp, pathHistogramPathUp, pathHistogramDown, pathHistogramPathDown
     integer :: nColumns, d
 
     if(.not. associated(thisIntegrator%fluxUp)) then
@@ -1169,8 +1208,24 @@ contains
     if(present(pathLengthSquaredUp))   call copyPathField(2, pathLengthSquaredUp,   "pathLengthSquaredUp")
     if(present(pathLengthDown))        call copyPathField(3, pathLengthDown,        "pathLengthDown")
     if(present(pathLengthSquaredDown)) call copyPathField(4, pathLengthSquaredDown, "pathLengthSquaredDown")
+    if(present(pathHistogramUp))       call copyBinField(1, pathHistogramUp,       "pathHistogramUp")
+    if(present(pathHistogramPathUp))   call copyBinField(2, pathHistogramPathUp,   "pathHistogramPathUp")
+    if(present(pathHistogramDown))     call copyBinField(3, pathHistogramDown,     "pathHistogramDown")
+    if(present(pathHistogramPathDown)) call copyBinField(4, pathHistogramPathDown, "pathHistogramPathDown")
     if(.not. stateIsFailure(status)) call setStateToSuccess(status)
   contains
+    subroutine copyBinField(which, to, name)
+      integer,            intent(in ) :: which
+      real, dimension(:), intent(out) :: to
+      character(len = *), intent(in ) :: name
+      if(.not. associated(thisIntegrator%pathHistogram)) then
+        call setStateToFailure(status, "reportResults: path histogram information not available")
+      else if(size(to) /= size(thisIntegrator%pathHistogram, 1)) then
+        call setStateToFailure(status, "reportResults: " // name // " array is the wrong size")
+      else
+        to = thisIntegrator%pathHistogram(:, which)
+      end if
+    end subroutine copyBinField
     subroutine copyPathField(which, to, name)
       integer,               intent(in ) :: which
       real, dimension(:, :), intent(out) :: to
@@ -1262,6 +1317,14 @@ contains
         copy%computePathLengths = .true.
       end if
     end if
+    if(associated(original%pathHistogram)) then
+      if(deviceCall(copy, i3rc_hip_set_path_histogram(copy%device, size(original%pathHistogramEdges) - 1, original%pathHistogramEdges), &
+                    "copy_Integrator", status)) then
+        allocate(copy%pathHistogramEdges(size(original%pathHistogramEdges)), copy%pathHistogram(size(original%pathHistogram, 1), 4))
+        copy%pathHistogramEdges = original%pathHistogramEdges
+        copy%pathHistogram = original%pathHistogram
+      end if
+    end if
   end function copy_Integrator
 
   subroutine finalize_Integrator(thisIntegrator)
@@ -1298,6 +1361,7 @@ contains
     if(associated(thisIntegrator%levelFluxUp))          deallocate(thisIntegrator%levelFluxUp, thisIntegrator%levelFluxDown)
     if(associated(thisIntegrator%actinicFlux))          deallocate(thisIntegrator%actinicFlux)
     if(associated(thisIntegrator%pathLengths))          deallocate(thisIntegrator%pathLengths)
+    if(associated(thisIntegrator%pathHistogram))        deallocate(thisIntegrator%pathHistogram, thisIntegrator%pathHistogramEdges)
     thisIntegrator%computeLevelFluxes = .false.; thisIntegrator%computeActinicFlux = .false.; thisIntegrator%computePathLengths = .false.
     thisIntegrator%readyToCompute = .false.; thisIntegrator%computeIntensity = .false.
     thisIntegrator%useSurfaceBDRF = .false.

@@ -176,6 +176,8 @@ class Domain:
 # ---------------------------------------------------------------------------------------------------------
 # the four results of the path-length tally, in the order of its block (i3rc_hip_normalise_path_lengths)
 PATH_LENGTH_NAMES = ("pathLengthUp", "pathLengthSquaredUp", "pathLengthDown", "pathLengthSquaredDown")
+# ... and of the path histogram (i3rc_hip_normalise_path_histogram)
+PATH_HISTOGRAM_NAMES = ("pathHistogramUp", "pathHistogramPathUp", "pathHistogramDown", "pathHistogramPathDown")
 
 
 class Integrator:
@@ -185,7 +187,7 @@ class Integrator:
                    "intensityPhis", "computeIntensity", "useRayTracing", "useRussianRoulette",
                    "useRussianRouletteForIntensity", "zetaMin", "useHybridPhaseFunsForIntenCalcs",
                    "hybridPhaseFunWidth", "numOrdersOrigPhaseFunIntenCalcs", "limitIntensityContributions",
-                   "maxIntensityContribution", "computeLevelFluxes", "computeActinicFlux", "computePathLengths")
+                   "maxIntensityContribution", "computeLevelFluxes", "computeActinicFlux", "computePathLengths", "pathHistogramEdges")
 
     def __init__(self, atmosphere, device=0):
         self._h = C.c_void_p()
@@ -217,6 +219,7 @@ class Integrator:
         self.computeLevelFluxes = False
         self.computeActinicFlux = False
         self.computePathLengths = False
+        self.pathHistogramEdges = None       # (float32 edges while the path histogram is on)
         self._inv_size = [0] * self.ncomp
         self._fwd_size = [0] * self.ncomp
         self._fwd_stale = True
@@ -333,6 +336,25 @@ class Integrator:
             self._check(self._lib.i3rc_hip_set_path_lengths(self._h, int(bool(kw["computePathLengths"]))), "specifyParameters")
             self.computePathLengths = bool(kw["computePathLengths"])
             self._results = None             # (the tally layout has changed)
+
+        if "pathHistogramEdges" in kw:
+            # the path-length distribution of reflected and transmitted light over these bin edges (i3rc_hip_set_path_histogram): not in
+            # the reference.  None or an empty array switches it off.
+            e = kw["pathHistogramEdges"]
+            e = np.zeros(0, np.float32) if e is None else f32(np.asarray(e).ravel())
+            if e.size == 1:
+                raise I3RCError("specifyParameters: pathHistogramEdges needs at least two edges (one bin)")
+            self._check(self._lib.i3rc_hip_set_path_histogram(self._h, max(e.size - 1, 0), pf(e) if e.size else None), "specifyParameters")
+            self.pathHistogramEdges = e.copy() if e.size else None
+            self._results = None             # (the tally layout has changed)
+
+    def path_histogram_layout(self):
+        """(offsets of binUp, binPathUp, binDown, binPathDown, the number of bins, total) of the packed tally buffer, in float64
+        elements; every field has nBins + 1 words, the last the overflow bin; the offsets are -1 and the bins 0 while the histogram is
+        off (i3rc_hip_get_path_histogram_layout)."""
+        v = [C.c_int64(0) for _ in range(6)]
+        self._check(self._lib.i3rc_hip_get_path_histogram_layout(self._h, *[C.byref(x) for x in v]), "path_histogram_layout")
+        return tuple(x.value for x in v)
 
     def path_length_layout(self):
         """(offsets of pathUp1, pathUp2, pathDown1, pathDown2, total) of the packed tally buffer, in float64 elements; the offsets are
@@ -451,6 +473,11 @@ class Integrator:
             for k in PATH_LENGTH_NAMES:
                 res[k] = np.zeros((self.ny, self.nx), np.float32)
             self._check(self._lib.i3rc_hip_normalise_path_lengths(self._h, raw.ctypes.data_as(B.dp), *[pf(res[k]) for k in PATH_LENGTH_NAMES]),
+                        "computeRadiativeTransfer")
+        if self.pathHistogramEdges is not None:
+            for k in PATH_HISTOGRAM_NAMES:
+                res[k] = np.zeros(self.pathHistogramEdges.size, np.float32)   # (nBins + 1: the overflow bin last)
+            self._check(self._lib.i3rc_hip_normalise_path_histogram(self._h, raw.ctypes.data_as(B.dp), *[pf(res[k]) for k in PATH_HISTOGRAM_NAMES]),
                         "computeRadiativeTransfer")
         cnt = raw[lay.counters:lay.counters + B.NUM_COUNTERS]
         res["counters"] = {k: float(cnt[i]) for i, k in enumerate(B.COUNTER_NAMES)}
@@ -573,10 +600,12 @@ class Integrator:
         return self._lib.i3rc_hip_last_kernel_name(self._h).decode()
 
     def last_plan(self):
-        """The plan of the most recent launch (i3rc_hip_last_plan) as a dict of B.PLAN_NAMES; every value -1 before the first."""
-        out = (C.c_int32 * len(B.PLAN_NAMES))()
-        self._check(self._lib.i3rc_hip_last_plan(self._h, out, len(B.PLAN_NAMES)), "last_plan")
-        return dict(zip(B.PLAN_NAMES, (int(v) for v in out)))
+        """The plan of the most recent launch (i3rc_hip_last_plan) as a dict of B.PLAN_NAMES; every value -1 before the first.  While the
+        path histogram is on, also B.PLAN_BIN_NAME: its sums in LDS (1) or in global memory (0)."""
+        names = B.PLAN_NAMES + ([B.PLAN_BIN_NAME] if self.pathHistogramEdges is not None else [])
+        out = (C.c_int32 * len(names))()
+        self._check(self._lib.i3rc_hip_last_plan(self._h, out, len(names)), "last_plan")
+        return dict(zip(names, (int(v) for v in out)))
 
     def kernel_ms_history(self, n):
         ms = np.zeros(n, np.float32)
@@ -585,13 +614,18 @@ class Integrator:
 
     # -- reportResults :711-826
     def reportResults(self, levelFluxUp=False, levelFluxDown=False, actinicFlux=False, pathLengthUp=False, pathLengthSquaredUp=False,
-                      pathLengthDown=False, pathLengthSquaredDown=False):
+                      pathLengthDown=False, pathLengthSquaredDown=False, pathHistogramUp=False, pathHistogramPathUp=False,
+                      pathHistogramDown=False, pathHistogramPathDown=False):
         """levelFluxUp / levelFluxDown = True ask for the level fluxes, (nz + 1, ny, nx) each, level k at zPosition[k] (the shell's optional
         arguments of the same names): an error unless specifyParameters(computeLevelFluxes=True) came before the computation.
         pathLengthUp / pathLengthSquaredUp / pathLengthDown / pathLengthSquaredDown = True ask for the path-length moments of the
         reflected and the transmitted light, the shell's (nx, ny) arrays in fluxUp's own shape here, in units of length (squared) x
         incident flux: pathLengthUp / fluxUp is the mean path of a column's reflected light.  An error unless
-        specifyParameters(computePathLengths=True) came before the computation."""
+        specifyParameters(computePathLengths=True) came before the computation.
+        pathHistogramUp / pathHistogramPathUp / pathHistogramDown / pathHistogramPathDown = True ask for the path histogram, nBins + 1
+        values each (the overflow bin last), per photon of the run and domain-wide: the sum of pathHistogramUp is the domain's mean
+        fluxUp, pathHistogramPathUp / pathHistogramUp a bin's mean path.  An error unless specifyParameters(pathHistogramEdges=...)
+        came before the computation."""
         r = self._results
         if r is None:
             raise I3RCError("reportResults: no results available")
@@ -602,6 +636,9 @@ class Integrator:
         paths = [k for k, asked in zip(PATH_LENGTH_NAMES, (pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown)) if asked]
         if paths and "pathLengthUp" not in r:
             raise I3RCError("reportResults: path length information not available")
+        bins = [k for k, asked in zip(PATH_HISTOGRAM_NAMES, (pathHistogramUp, pathHistogramPathUp, pathHistogramDown, pathHistogramPathDown)) if asked]
+        if bins and "pathHistogramUp" not in r:
+            raise I3RCError("reportResults: path histogram information not available")
         ncol = r32(self.nx * self.ny)
         out = dict(meanFluxUp=r["fluxUp"].sum(dtype=np.float32) / ncol, meanFluxDown=r["fluxDown"].sum(dtype=np.float32) / ncol,
                    meanFluxAbsorbed=r["fluxAbsorbed"].sum(dtype=np.float32) / ncol,
@@ -617,7 +654,7 @@ class Integrator:
             out["levelFluxDown"] = r["levelFluxDown"]
         if actinicFlux:
             out["actinicFlux"] = r["actinicFlux"]
-        for k in paths:
+        for k in paths + bins:
             out[k] = r[k]
         return out
 

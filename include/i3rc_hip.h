@@ -230,6 +230,43 @@ int i3rc_hip_get_path_length_layout(const i3rc_hip_integrator *h, int64_t *up1, 
 int i3rc_hip_normalise_path_lengths(const i3rc_hip_integrator *h, const double *hostTallies, float *pathLengthUp, float *pathLengthSquaredUp,
                                     float *pathLengthDown, float *pathLengthSquaredDown);
 
+/* THE PATH-LENGTH HISTOGRAM of reflected and transmitted light (not in the reference): the distribution p(L) the two moments above
+ * cannot give.  With nBins >= 1, plain flux launches also sort the light that fluxUp and fluxDown count into nBins bins of its
+ * geometric path L, domain-wide, and an overflow bin: four fields of nBins + 1 float64 raw sums each,
+ *   binUp, binPathUp       where fluxUp is tallied:    the sum of w, and of w L (the product in float64), per bin,
+ *   binDown, binPathDown   where fluxDown is tallied:  the same,
+ * w and L exactly the two values the path-length sums above are formed from (a surface arrival's weight is the one before the
+ * reflection, L carries on through a reflection, a photon the tracer drops tallies nothing).
+ * edges: nBins + 1 float32 values, 1 <= nBins <= 1024, edges[0] == 0, strictly ascending, finite.  THE BIN RULE (path_bin,
+ * csrc/tally_block.hpp, shared by the kernel and the host's tests): L belongs to bin b with edges[b] <= float(L) < edges[b + 1], and
+ * to the overflow bin b = nBins where float(L) >= edges[nBins]; the index is clamped, so that nothing is written outside the block.
+ * So sum_b binUp = sum(fluxUp) of the raw sums, binPathUp[b] / binUp[b] is the bin's mean path -- between the bin's edges --, and one
+ * conservative run gives R(k) = sum_b binUp[b] <exp(-k L)>_b for every k, bracketed by exp(-k mean path) from below and the chord
+ * over the bin from above.
+ * nBins == 0 switches the histogram off (edges is not read).  Bad bins are refused with a text that names what is wrong, before
+ * anything is touched: a histogram that is on stays on as it was.  A call with good bins while the histogram is on replaces the bins
+ * and clears the handle's tallies.
+ * The block lies BEHIND the counters of the packed tally buffer, where each other kind of the diagnostic tally has its block: the
+ * kinds are never on together, and each setter refuses while another is on.  No offset of i3rc_tally_layout moves; layout.total grows
+ * by 4 (nBins + 1) (zeroing, fetching, binding and an all-reduce of the packed buffer cover the block).  Switching reallocates the
+ * handle's own buffer (cleared); with a caller-bound buffer in use it is refused.  Off by default: nothing changes then.
+ * While it is on, a launch runs photon_kernel<PhiloxBinStream, false, true, GRID> -- the general flux kernel's photons, counter for
+ * counter -- and is refused exactly where a launch with path lengths on is: radiance directions, max cross-section,
+ * i3rc_hip_run_batches, i3rc_hip_run_batches_moments, i3rc_hip_expect_batches, i3rc_hip_run_replay,
+ * i3rc_hip_run_batches_diagnostic_moments and i3rc_hip_get_diagnostic_moments_layout; i3rc_hip_compute_batch does not look ahead.
+ * Where the launch's LDS has room for them, a workgroup keeps the 4 (nBins + 1) sums and the edges in LDS, at any place of the
+ * extinction field (i3rc_hip_set_lds_tallies(h, 0) switches that off); else the kernel adds to the block in global memory with float64
+ * atomics.  i3rc_hip_last_plan's fourteenth word says which. */
+int i3rc_hip_set_path_histogram(i3rc_hip_integrator *h, int nBins, const float *edges);
+/* Offsets (float64 elements) of binUp, binPathUp, binDown and binPathDown in the packed buffer, -1 each while the histogram is off,
+ * its bins (0 while off; every field has nBins + 1 words) and the buffer's total (= layout.total).  Any of the six may be NULL. */
+int i3rc_hip_get_path_histogram_layout(const i3rc_hip_integrator *h, int64_t *binUp, int64_t *binPathUp, int64_t *binDown, int64_t *binPathDown,
+                                       int64_t *nBins, int64_t *total);
+/* A host copy of the packed tallies, per photon of the block -- float32(raw / counters[I3RC_CNT_PHOTONS]), domain-wide and not per
+ * column: the sum over `up` is the domain's area-weighted mean fluxUp on every grid --: four arrays of nBins + 1 values, the last the
+ * overflow bin.  Any output may be NULL.  Fails while the histogram is off. */
+int i3rc_hip_normalise_path_histogram(const i3rc_hip_integrator *h, const double *hostTallies, float *up, float *pathUp, float *down, float *pathDown);
+
 /* ---- the hot path ---------------------------------------------------------------------------------- */
 
 /* computeRT (:400-707) for one batch of nPhotons, ASYNCHRONOUS on the handle's stream; tallies accumulate.
@@ -413,7 +450,9 @@ const char *i3rc_hip_last_kernel_name(const i3rc_hip_integrator *h);
  * LDS (0 / 1 each); dynamic LDS bytes; absorbing (0 / 1); cell records passed to the kernel (0: none, else their bytes: 8, 16 or 32); batches of
  * the launch if it was a fused group (else 0); place of the extinction field (0 LDS, 1 global, 2 bricks, 3 column records,
  * 4 column records over a base profile); bytes of the waves' start stores in LDS (part of the dynamic LDS bytes; 0: the kernel
- * starts its photons in the event phase); photons a wave takes per visit of the work counter (RunArgs::chunk); the actinic flux's track-length sums in LDS (0 / 1).  All -1 before the first launch.  Returns 0, or 1 on a null argument. */
+ * starts its photons in the event phase); photons a wave takes per visit of the work counter (RunArgs::chunk); the actinic flux's track-length sums in LDS (0 / 1).  All -1 before the first launch.  Returns 0, or 1 on a null argument.
+ * With n >= 14 also out[13]: the path histogram's sums and edges in LDS (1), or its block added to in global memory (0; every launch
+ * of another kind: 0). */
 int i3rc_hip_last_plan(const i3rc_hip_integrator *h, int32_t *out, int n);
 
 /* Experiment knobs (not part of the reference API): lanes that must be waiting before a wavefront runs its
@@ -509,14 +548,14 @@ int i3rc_hip_lds_plan_words(const int32_t *q, int nq, int32_t *out, int nout);
  *   facts      the 23 words above
  *   setup      what the setters and the handle's knobs add, 14 words: nDir; every component has its inverse table, its forward tables
  *              (0 / 1); steps and entries of component 1's inverse table; useSurfaceBDRF, useRayTracing; the surface grid's nx, ny and
- *              whether one is set; the extra tally (0 none, 1 level fluxes, 2 actinic flux, 3 path lengths); the kernel variant (I3RC_KERNEL_*), the
+ *              whether one is set; the extra tally (0 none, 1 level fluxes, 2 actinic flux, 3 path lengths, 4 the path histogram); the kernel variant (I3RC_KERNEL_*), the
  *              grid place (I3RC_GRID_*), i3rc_hip_set_lds_tallies (0 / 1)
  *   env        as above
- *   kind       3 words: the stream (0 plain, 1 fused, 2 replay, 3 level tally, 4 track tally, 5 path tally), the source's kind (i3rc_source::kind),
- *              the batches of a fused launch
+ *   kind       3 words: the stream (0 plain, 1 fused, 2 replay, 3 level tally, 4 track tally, 5 path tally, 6 path histogram), the source's
+ *              kind (i3rc_source::kind), the batches of a fused launch; for stream 6 a fourth word, the histogram's bins
  *   out[0..min(nout, 16) - 1] = the 13 words of i3rc_hip_last_plan as the launch would record them (the chunk, which needs the device:
  *              0), then the estimate of a workgroup's LDS the decisions were made with (bytes), the ray queue's capacity, the
- *              threads of a workgroup
+ *              threads of a workgroup; with nout >= 17 the fourteenth word of i3rc_hip_last_plan
  *   text       the kernel's name as i3rc_hip_last_kernel_name would report it, or the refusal's text
  * Returns 0; 1 where the launch would be refused; 2 on a bad argument. */
 int i3rc_hip_problem_facts(int nx, int ny, int nz, int ncomp, const float *xEdges, const float *yEdges, const float *zEdges,
