@@ -843,7 +843,11 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       raysSkipped = 0u;
     }
     if (!BATCHED && (threadIdx.x & 63) == 0) {   // (BATCHED flux kernels: per lane and batch, see flush_lanes)
-      const uint32_t c[9] = {wc.photons, wc.dropped, wc.steps, wc.scat, wc.surf, wc.top, wc.roul, wc.shadow, wc.calls};
+      // (STORE: tracer calls are derived, not counted -- every trace ends in exactly one scattering, surface arrival, exit through the
+      // top or tracer drop, each counted where the event phase serves it, and every trace has ended when the launch has: over a launch
+      // the sum is the number of traces started, which is all the host ever sees of these hand-overs)
+      const uint32_t calls = STORE ? wc.scat + wc.surf + wc.top + wc.dropped : wc.calls;
+      const uint32_t c[9] = {wc.photons, wc.dropped, wc.steps, wc.scat, wc.surf, wc.top, wc.roul, wc.shadow, calls};
       const ColdArgs ka = cold_args();
       double *const counters = ka->P.tally + ka->P.oCnt;
 #pragma unroll
@@ -1115,11 +1119,17 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
     // (The specialised flux kernels of plain launches make their photons' starts a wavefront at a time -- STORE, part B -- and a
     // turnover lane there closes its photon and reads four words: their quorum is a pair of knobs of its own, tuning.hpp.)
     const bool wantScat = st == ST_EVENT;
-    const bool wantTurn = st == ST_EXIT || st == ST_DROPPED || st == ST_NEW;
+    // (STORE: the three states as ONE compare, so that the ballot below is that compare's own mask -- the three-way OR came out as
+    // a lane mask turned into 0 / 1 in a vector register and compared again: six vector instructions at every pass of the loop)
+    constexpr unsigned kTurnStates = (1u << ST_EXIT) | (1u << ST_DROPPED) | (1u << ST_NEW);
+    const bool wantTurn = STORE ? ((kTurnStates >> (unsigned)st) & 1u) != 0u : (st == ST_EXIT || st == ST_DROPPED || st == ST_NEW);
     const unsigned long long scMask = __ballot(wantScat), tuMask = __ballot(wantTurn);
     const unsigned long long trMask = __ballot(st == ST_TRACE);
     if (scMask == 0ull && tuMask == 0ull && trMask == 0ull) break;   // (no photons left; any ray work has been done in ray mode above)
-    const int nSc = (int)__popcll(scMask), nTu = (int)__popcll(tuMask);
+    int nSc = (int)__popcll(scMask), nTu = (int)__popcll(tuMask);
+    // (STORE: the counts are 32-bit scalars from here on -- left as the 64-bit population counts they come from, their comparisons
+    // with the quorums came out as v_cmp_gt_u64 on scalar pairs, two vector instructions of the expensive class at every pass)
+    if constexpr (STORE) asm volatile("" : "+s"(nSc), "+s"(nTu));
     bool runEvent = nSc + nTu > 0 && (nSc >= evThr || nTu >= kTurnForce || trMask == 0ull);
     const bool doTurn = nTu >= kTurnMin || trMask == 0ull || nSc == 0;
     const bool wantEvent = wantScat || (doTurn && wantTurn);
@@ -1169,6 +1179,20 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       // ---- part A: endings that need no random number -- tracer drop, exit through the top, arrival at a black
       //      surface -- are tallied first so that the lanes can be given their next photon before the wave
       //      generates its random block (part C), which then serves old and new photons in one go.
+      // STORE: parts A and B serve turnover lanes and photons that arrive at the top or at the surface; an event phase without either
+      // -- a wave-uniform fact, known here -- skips both behind ONE scalar branch, its ending counters and the hand-out included.
+      // The wave's counts are taken from the masks of the two height compares themselves, joined by scalar arithmetic with the state
+      // masks of the loop's head: the ballot of a flag that is an AND of compares came out as mask -> 0 / 1 in a vector register ->
+      // mask, once per counter.  (Uniform control flow: a lane's bit in a compare's mask is the lane's own flag.)
+      bool turnPhase = true;
+      unsigned long long geTop = 0ull, leSurf = 0ull;      // STORE: lanes at or above the top / at or below the surface, any state
+      unsigned long long topMask = 0ull, surfMask = 0ull;  // STORE: the lanes part A finds at the top / at the surface (none in a phase that skips it)
+      const unsigned long long turnAll = doTurn ? ~0ull : 0ull;   // (the wave-uniform doTurn as a mask: no branch, no detour through a vector register)
+      if constexpr (STORE) {
+        geTop = __ballot(r.z >= Pe.zMax); leSurf = __ballot(r.z <= surfaceZ);
+        turnPhase = (doTurn && tuMask != 0ull) || (scMask & (geTop | leSurf)) != 0ull;
+      }
+      if (turnPhase) {
       const bool isEv = wantEvent && (st == ST_EVENT || st == ST_EXIT);
       const bool dropped = wantEvent && st == ST_DROPPED;                 // :488-489
       const bool atTop = isEv && r.z >= Pe.zMax;                           // :499-514
@@ -1182,9 +1206,18 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           tally_level_crossings(Pe, L, extra_block(tally.base(), Pe.oCnt), r.x, r.y, atTop ? Pe.zMax : r.z, r.dx, r.dy, r.dz, izFrom,
                                 atTop ? Pe.nz + 1 : (atSurface ? 0 : r.iz), (r.iy - 1) * Pe.nx + (r.ix - 1), r.ix, r.iy, w);
       }
-      wc.dropped += count_lanes(dropped);
-      wc.top += count_lanes(atTop);
-      wc.surf += count_lanes(atSurface);
+      if constexpr (STORE) {
+        const unsigned long long evExit = scMask | (__ballot(st == ST_EXIT) & turnAll);   // isEv, as a mask
+        topMask = evExit & geTop;
+        surfMask = evExit & ~topMask & leSurf;
+        wc.dropped += (unsigned)__popcll(__ballot(st == ST_DROPPED) & turnAll);
+        wc.top += (unsigned)__popcll(topMask);
+        wc.surf += (unsigned)__popcll(surfMask);
+      } else {
+        wc.dropped += count_lanes(dropped);
+        wc.top += count_lanes(atTop);
+        wc.surf += count_lanes(atSurface);
+      }
       if constexpr (BATCHED) {
         if constexpr (LANE_COUNTS) accB.add(atSurface, atTop);
         if (dropped) {
@@ -1218,7 +1251,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       }
       // ---- part B (uniform): hand out photon indices from the wave's reservoir
       const bool isNew = wantEvent && st == ST_NEW;
-      const unsigned long long newMask = __ballot(isNew);
+      const unsigned long long newMask = STORE ? (scMask | (tuMask & turnAll)) & __ballot(st == ST_NEW) : __ballot(isNew);
       if constexpr (BATCHED) {
         if (newMask != 0ull) {
           int need = __popcll(newMask);
@@ -1361,6 +1394,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           }
         }
       }
+      }   // (turnPhase)
       // ---- part C: one random block per lane for this event, then the event itself
       bool didScatter = false, didRoulette = false, startedTrace = false;   // per-lane flags -> wave counters below
       bool fromStore = false;                                               // STORE: this lane's photon starts here, from its slot
@@ -1647,9 +1681,11 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
         qTail += (unsigned)__popcll(pushMask);
       }
       if constexpr (LANE_COUNTS) accA.add(didScatter, didRoulette);
-      wc.scat += count_lanes(didScatter);
-      wc.roul += count_lanes(didRoulette);
-      if constexpr (!BATCHED) wc.calls += count_lanes(startedTrace);   // (BATCHED: a batch's photon traces = its scatterings + surface arrivals + exits + drops)
+      // (STORE -- ray tracing, one component: a photon with an interaction due scatters unless part A found it at the top or at the surface)
+      if constexpr (STORE) wc.scat += (unsigned)__popcll(scMask & ~(topMask | surfMask));
+      else wc.scat += count_lanes(didScatter);
+      if (!STORE || Pe.useRR) wc.roul += count_lanes(didRoulette);     // (STORE: only a launch that plays roulette pays for the count)
+      if constexpr (!BATCHED && !STORE) wc.calls += count_lanes(startedTrace);   // (BATCHED, STORE: a batch's / launch's photon traces = its scatterings + surface arrivals + exits + drops)
       PROF_END(PH_EVENT, __popcll(evMask));
     }
     // -------------------------------------------------------------- VOXEL-STEP phase (photons)
