@@ -30,18 +30,43 @@ What the model follows (the line it restates in brackets):
     never counts: its entries are exactly 0 (Result.exact_zero).  The contribution limit applies to whichever value results [make_ray,
     service phase];
   * counters, and the deviates consumed one by one (I3RC_CNT_RNG_DRAWS); I3RC_CNT_TRACER_CALLS: one per trace of a photon, per traced
-    ray and per second leg.
+    ray and per second leg;
+  * the one diagnostic tally of a flux launch (Problem.extra; ExtraTally in tally_block.hpp), each from what the general flux kernel
+    photon_kernel<Philox{Level,Track,Path,Bin}Stream, false, true, GRID> states:
+      the path L of a photon: 0 at its start -- the start height zstart, not the top -- [part C, ST_NEW: `pathLen = 0.0`], + the
+        geometric length |s| of every traced segment [photon_step: `pathLen += (double)len` per voxel step that is no tracer error;
+        the event phase: `pathLen += (double)part`, finish_arrival<true>], carried through a surface reflection (nothing resets it there);
+      "paths"  pathUp1 | pathUp2 | pathDown1 | pathDown2 [ny, nx]: w L and w L^2 where and in the column where fluxUp / fluxDown are
+        tallied [path_add beside tally.boundary in part A, beside tally.down in part C], a surface arrival with the weight BEFORE
+        the reflection [path_add stands before `w = w * Pe.albedo`];
+      "bins"   binUp | binPathUp | binDown | binPathDown [nBins + 1], overflow last: w and w L at the same places into the bin b of
+        float32(L) with edges[b] <= x < edges[b + 1] [bin_add: `(float)length`; path_bin];
+      "levels" levelFluxUp | levelFluxDown [nz + 1, ny, nx]: a new photon adds 1 to levelFluxDown at the level behind its start layer
+        in its start column [part C, ST_NEW: `down ? r.iz : r.iz - 1`]; a segment from layer a to layer b (1-based; nz + 1 out through
+        the top, 0 onto the surface) adds w to levelFluxUp[a .. b - 1] going up, to levelFluxDown[b .. a - 1] going down [part A:
+        tally_level_crossings with izFrom -- set where the trace starts -- and izTo]; the level the segment ENDS on (top, surface) takes
+        the arrival's own column, every other level the column of the point where the straight segment meets ze[k], wrapped
+        periodically [tally_level_crossings: extrapolated back from the arrival, find_xy]; a reflected photon that goes on adds its
+        weight AFTER the reflection to levelFluxUp[0] in the column where it was reflected [part C: `add_global(... + c2, w)`];
+      "tracks" [nz, ny, nx]: every segment cut by the planes of the grid (float64, periodic in x and y); each piece adds w l to the cell
+        it lies in, w the weight along the segment, before the event at its end [photon_step: track_add of the cell BEFORE the step;
+        the event phase: the arrival's part in the cell the photon stands in]; `trackLayers` [nz]: the same added over a layer's columns.
 The optical path is analytic: with C(z) the extinction integrated from the bottom, a path of optical depth tau along direction
 cosine dz ends where C changes by tau |dz|.  The tracer itself is pinned bit for bit elsewhere (tests/test_gpu_parity.py).
 
 Out of scope (the replay pin and the oracle tests cover them): max cross-section, gridded surfaces, explicit photon sources,
-horizontally varying fields, zetaMin = 0, a reflection's retry (a deviate of exactly 0: asserted not to occur), the diagnostic tallies.
+horizontally varying fields, zetaMin = 0, a reflection's retry (a deviate of exactly 0: asserted not to occur); of the diagnostic
+tallies the fused and moments entry points (they refuse or wrap the kinds: tests/test_gpu_diagnostic_moments.py) and the workgroup's
+LDS sums as such (the same additions in another order: the kinds' own suites).
 
 MARGINS AND BOUNDS.  Every discrete decision records its margin and the model's own bound on the float32 error of the compared
 quantity; a photon is FRAGILE when some margin is below 4 bounds.  The decisions: top / bottom / which layer (one comparison of
 optical depths), the component compare (both sides are float32 values the kernel holds too: bound 0), the roulette compares
 (w < 0.5, spare >= w), the column of an event, an exit or a ray's exit, the sign of the direction's z-cosine in next_direct (its
-frame changes hands there) and the contribution limit; with the local estimate's roulette also pi norm against zetaMin (bound: pi e_norm
+frame changes hands there) and the contribution limit; with a diagnostic tally also the START COLUMN of a new photon (levels; bound: the
+start position's e_h = 2 eps |x|max, the product and the sum of x0 + u (xMax - x0)), the LEVEL COLUMN of every crossing that is not the
+segment's end (levels; bound below) and the BIN of float32(L) (bins; margin: the distance of L to the two edges that bracket it, bound
+e_L + eps L, the conversion's rounding); with the local estimate's roulette also pi norm against zetaMin (bound: pi e_norm
 + 3 eps of the product), r2 zetaMin against pi norm (+ 1 eps), the optical depth to the top against tauFree (e_tau + 2 ulp for fast_log)
 and against tauMax (e_tau + 2 ulp + 1 ulp for fast_div + 3 eps + e_norm / norm), the second leg's remaining depth against tauFree (all
 of these, + the arrival point's rounding) -- each only where its outcome reaches a tally or a counter, and a ray's column only where
@@ -59,10 +84,29 @@ correctly rounded 1 / n would give another one (evaluated per event):
                   Lipschitz constant at that event: the largest singular value of its finite-difference Jacobian on the tangent plane
   weight          one eps per factor
   radiance        the weight's, P at theta +- e_theta (evaluated, not linearised), exp at tau +- e_tau, 1 ulp each for v_rcp / v_exp
+  path L          e_L = the sum over the segments of e_s + steps eps |s|: the along-path error above, one float32 rounding per voxel-step
+                  piece (`step`, a quotient) and for the arrival piece (finish_arrival's exact_div); the float64 additions add nothing
+  paths           per deposit w (e_w L + e_L) for w L, w (e_w L^2 + 2 L e_L) for w L^2
+  bins            w e_w for the weights, the bound of w L for binPath
+  levels          w e_w per deposit; the level column's bound: the arrival's e_xy + back e_dir (back: the path from the crossing to the
+                  arrival) + eps (3 h + 4 (|x|max + h) + |x|max), h = |d_xy| back, for tally_level_crossings' float32 operations: back =
+                  (z - zE[k]) / dz (a difference, a quotient) and dx * back (a product): 3 eps h; x - dx * back, the wrap's difference
+                  and quotient inside floorf and its product by the width: eps (|x|max + h) each; the last difference: eps |x|max; the
+                  clamp rounds nothing
+  tracks          per piece w (e_w l + e_l), e_l = eps l (the piece's quotient) + l e_dir / |dz| + (side faces crossed before it in the
+                  segment) eps (|z|max + 2 dz) / |dz| (z is rounded only where a side face is crossed) + for the first piece the start's
+                  along-path error e_C / ext / |dz|, for the last one the arrival's e_C' / ext' / |dz| (the two terms of e_s); per side
+                  face crossed, in BOTH adjoining cells, the transfer w min(e_xy / |d_n|, the two adjoining pieces' lengths), d_n the
+                  cosine normal to the face: the position's error moves length continuously from a cell to its neighbour -- no discrete
+                  decision; the per-layer sums carry no transfer terms
 (steps: voxel faces crossed + 1).  No constant in it is fitted to what a kernel gives.
 
+A FRAGILE PHOTON AND THE DIAGNOSTIC TALLIES.  The caps (a weight is at most 1 per tally) do not extend to a path, which has no upper
+limit: the diagnostic fields are compared only over photons that are not fragile -- clean_runs gives all maximal runs of them, run(ids=...)
+the model over exactly those photons -- and compare() refuses anything else.
+
 Measured with `python -m tests.stream_model` (fragile photons / photons, per shared case; the cap tests/test_stream_model_cpu.py
-asserts is 0.5 %): see FRAGILE_SHARES at the end of this module."""
+asserts is 0.5 %): see FRAGILE_SHARES at the end of this module, and DIAGNOSTIC_SHARES for the diagnostic cases and kinds."""
 import ctypes
 import ctypes.util
 from dataclasses import dataclass, field
@@ -106,6 +150,14 @@ def direction(mu, phi_deg):
     return np.array([f32(st * f32(_libm.cosf(phi))), f32(st * f32(_libm.sinf(phi))), mu], f32)
 
 
+EXTRAS = (None, "levels", "tracks", "paths", "bins")
+# the fields of each kind's block, in the block's order (tally_block.hpp: ExtraTally, tally_layout, path_bin_field); `trackLayers` is
+# no field of the device's: the track sums added over the columns of a layer, which the caller forms from the block
+EXTRA_FIELDS = {None: (), "levels": ("levelFluxUp", "levelFluxDown"), "tracks": ("tracks",),
+                "paths": ("pathUp1", "pathUp2", "pathDown1", "pathDown2"), "bins": ("binUp", "binPathUp", "binDown", "binPathDown")}
+DERIVED_FIELDS = ("trackLayers",)
+
+
 @dataclass
 class Problem:
     xe: np.ndarray
@@ -127,12 +179,19 @@ class Problem:
     max_contrib: float = None       # the contribution limit; None: off
     rr_intensity: bool = False      # the local estimate's own roulette (useRussianRouletteForIntensity)
     zeta_min: float = 0.3           # ... and its bound (the library's default)
+    extra: str = None               # the one diagnostic tally of the launch (EXTRAS; ExtraTally in tally_block.hpp), flux launches only
+    bin_edges: np.ndarray = None    # extra == "bins": the nBins + 1 float32 edges as handed to the device (edges[0] == 0, ascending)
 
     def __post_init__(self):
         self.xe, self.ye, self.ze = (np.asarray(a, f32) for a in (self.xe, self.ye, self.ze))
         self.ext, self.ssa = np.atleast_2d(np.asarray(self.ext, f32)), np.atleast_2d(np.asarray(self.ssa, f32))
         self.pfi = np.atleast_2d(np.asarray(self.pfi, np.int64))
         self.inv = [np.atleast_2d(np.asarray(t, f32)) for t in self.inv]
+        assert self.extra in EXTRAS, self.extra
+        assert self.extra is None or self.dirs is None, "the diagnostic tallies refuse radiance directions"
+        if self.extra == "bins":
+            self.bin_edges = np.asarray(self.bin_edges, f32)
+            assert self.bin_edges[0] == 0 and np.all(np.diff(self.bin_edges) > 0)
         if self.dirs is not None:
             self.dirs = np.asarray(self.dirs, f32).reshape(-1, 3)
             self.fwd = [np.atleast_2d(np.asarray(t, f32)) for t in self.fwd]
@@ -152,6 +211,7 @@ class Result:
     per_photon: dict                # fate (0 top, 1 surface, 2 roulette / absorbed), order, weight, fragile, counts, deposits
     caps: dict = field(default_factory=dict)
     branches: dict = field(default_factory=dict)   # rays of the local estimate's roulette by what became of them (BRANCHES)
+    extras: dict = field(default_factory=dict)     # the diagnostic kinds' own records: per-photon sums, the pieces a cell received
     exact_zero: dict = field(default_factory=dict)  # per tally: entries nothing can reach, whatever a fragile photon does (a downward direction's, with the roulette)
 
     @property
@@ -168,10 +228,21 @@ BRANCHES = ("small lost", "small won counted", "small won ended inside", "large 
             "second leg counted", "second leg ended inside", "surface small", "surface large", "capped above the limit")
 
 
-def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0):
+# ... and of the diagnostic tallies: each one another convention for the path register, the level ranges or the pieces of a track
+EXTRA_VARIANTS = {"paths": ("path restarts at a reflection", "surface tally with the weight after the reflection", "last segment left out of L"),
+                  "bins": ("path restarts at a reflection", "surface tally with the weight after the reflection", "last segment left out of L",
+                           "bin of L before the last segment"),
+                  "levels": ("crossing counted in the arrival column", "new photon not counted", "downward range shifted by one level",
+                             "reflected photon not counted"),
+                  "tracks": ("weight after the scattering", "piece credited to the cell after the step", "arrival piece left out")}
+
+
+def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0, ids=None):
     """n photons first_photon .. first_photon + n - 1 of the key (seed[0], seed[1] + batch): batch `batch` of a fused launch whose
-    first batch has the key `seed`"""
-    assert variant is None or variant in VARIANTS + RAY_VARIANTS, variant
+    first batch has the key `seed`.  ids: the photon numbers themselves instead (any set of them: photons do not know of each other)"""
+    assert variant is None or variant in VARIANTS + RAY_VARIANTS + EXTRA_VARIANTS.get(P.extra, ()), variant
+    if ids is not None:
+        n = len(ids)
     nx, ny, nz, ncomp = len(P.xe) - 1, len(P.ye) - 1, len(P.ze) - 1, P.ext.shape[0]
     xe, ye, ze = P.xe.astype(f64), P.ye.astype(f64), P.ze.astype(f64)
     x0, y0, Lx, Ly = xe[0], ye[0], xe[-1] - xe[0], ye[-1] - ye[0]
@@ -193,12 +264,31 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0):
     zeta = float(f32(P.zeta_min))
     inv_pi32 = float(f32(1.0) / PI32)   # the float32 constant 1 / pi of the capped value
     branches = {k: 0 for k in BRANCHES}
-    pid = np.uint64(first_photon) + np.arange(n, dtype=np.uint64)
+    pid = np.uint64(first_photon) + np.arange(n, dtype=np.uint64) if ids is None else np.asarray(ids, np.uint64)
     lo, hi = pid & _MASK, (np.zeros(n, np.uint64) if drop_high_word else pid >> _S32)
 
     T = dict(fluxUp=np.zeros((ny, nx)), fluxDown=np.zeros((ny, nx)), volumeAbsorption=np.zeros((nz, ny, nx)),
              intensity=np.zeros((ncomp + 1, max(nd, 1), ny, nx)), intensityExcess=np.zeros((ncomp + 1, max(nd, 1))))
+    extra = P.extra
+    path_kind = extra in ("paths", "bins")
+    edges = P.bin_edges.astype(f64) if extra == "bins" else None
+    nbins = len(edges) - 1 if extra == "bins" else 0
+    shapes = {"levels": (nz + 1, ny, nx), "tracks": (nz, ny, nx), "paths": (ny, nx), "bins": (nbins + 1,)}
+    for k in EXTRA_FIELDS[extra]:
+        T[k] = np.zeros(shapes[extra])
+    if extra == "tracks":
+        T["trackLayers"] = np.zeros(nz)
     Bd = {k: np.zeros_like(v) for k, v in T.items()}
+    # the kinds' own records.  perPhoton: each field's sum over the photon's deposits (levels: per level; `absLayer` what the photon
+    # leaves in each layer as absorption; `wS` the sum of w |s| over its segments); trackPieces: the pieces a cell received
+    X = dict(perPhoton={k: np.zeros((n,) + ((nz + 1,) if extra == "levels" else ())) for k in EXTRA_FIELDS[extra]})
+    if extra == "levels":
+        X["perPhoton"]["absLayer"] = np.zeros((n, nz))
+    if extra == "tracks":
+        X["perPhoton"]["wS"], X["trackPieces"] = np.zeros(n), np.zeros((nz, ny, nx), np.int64)
+    if path_kind:
+        X["deposits"] = []
+    Lp, e_L = np.zeros(n), np.zeros(n)      # PATH: the photon's geometric path since its start [pathLen, kernels.hpp], and its error
     cnt = {k: np.zeros(n, np.int64) for k in ("scatterings", "surfaceHits", "exitsTop", "roulette", "rngDraws", "raysSkipped", "tracerCalls")}
     dep = {k: np.zeros(n) for k in ("fluxUp", "fluxDown", "volumeAbsorption", "intensity")}
     fragile, why = np.zeros(n, bool), {}
@@ -348,6 +438,84 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0):
             np.add.at(Bd["intensity"], (cidx, d, cj, ci), e_con)
             np.add.at(dep["intensity"], idx, con)
 
+    def path_deposit(ph, cjs, cis, up_, wgt, ewt, lbin):
+        """PATH: the photons `ph` end a flux tally in the columns (cjs, cis) with weight wgt: w L, w L^2 [path_add] or, by the bin of
+        float(L), w and w L [bin_add, path_bin]; lbin: the path whose bin is taken (the photon's own, but for a control)"""
+        Lh, eL = Lp[ph], e_L[ph]
+        X["deposits"].append(np.array([ph, Lh, eL + EPS * Lh, wgt, np.full(len(ph), float(up_))]))
+        b1, b2 = wgt * (ewt * Lh + eL), wgt * (ewt * Lh * Lh + 2.0 * Lh * eL)
+        if extra == "paths":
+            for key, val, bd in (("pathUp1" if up_ else "pathDown1", wgt * Lh, b1), ("pathUp2" if up_ else "pathDown2", wgt * Lh * Lh, b2)):
+                np.add.at(T[key], (cjs, cis), val)
+                np.add.at(Bd[key], (cjs, cis), bd)
+                X["perPhoton"][key][ph] += val
+            return
+        xb = lbin.astype(f32).astype(f64)                                          # [bin_add: `const float x = (float)length`]
+        bn = np.clip(np.searchsorted(edges, xb, side="right") - 1, 0, nbins)       # edges[b] <= x < edges[b + 1]; the overflow bin last
+        m = np.where(bn < nbins, edges[np.minimum(bn + 1, nbins)] - lbin, np.inf)
+        decide(ph, np.minimum(lbin - edges[bn], m), eL + EPS * lbin, "bin")       # (the path's own error and the conversion's rounding)
+        for key, val, bd in (("binUp" if up_ else "binDown", wgt, wgt * ewt), ("binPathUp" if up_ else "binPathDown", wgt * Lh, b1)):
+            np.add.at(T[key], bn, val)
+            np.add.at(Bd[key], bn, bd)
+            X["perPhoton"][key][ph] += val
+
+    def track_pieces(g):
+        """TRACK: the segments g cut by the planes of the grid (float64, periodic in x and y); each piece adds weight x length to the cell
+        it lies in [trace_step_lazy LENGTH + track_add in photon_step; finish_arrival<true> + track_add in the event phase]"""
+        m, sg, d = len(g["idx"]), g["s"], g["d"]
+        goes_up = d[2] > 0
+
+        def ragged(counts):
+            counts = counts.astype(np.int64)
+            return np.repeat(np.arange(m), counts), np.arange(int(counts.sum())) - np.repeat(np.cumsum(counts) - counts, counts)
+
+        at, off = ragged(np.abs(g["l1"] - g["l0"]))                                # the layer faces between the two layers
+        k = np.where(goes_up[at], g["l0"][at] + 1 + off, g["l0"][at] - off)
+        segs, ts, ncos = [at], [(ze[k] - g["z"][at]) / d[2, at]], [np.zeros(len(at))]
+        for ax, (eds, org, width, nn, g0, g1, p0) in enumerate(((xe, x0, Lx, nx, g["gx0"], g["gx1"], g["x"]), (ye, y0, Ly, ny, g["gy0"], g["gy1"], g["y"]))):
+            at, off = ragged(np.abs(g1 - g0))                                      # the side faces, counted through the periodic images
+            G = np.where((g1 > g0)[at], g0[at] + 1 + off, g0[at] - off).astype(np.int64)
+            face = org + (G // nn) * width + (eds[G % nn] - org)
+            segs.append(at), ts.append((face - p0[at]) / d[ax, at]), ncos.append(np.abs(d[ax, at]))
+        segs.append(np.arange(m)), ts.append(sg + 0.0), ncos.append(np.full(m, -1.0))   # (-1: the segment's end)
+        at, nc = np.concatenate(segs), np.concatenate(ncos)
+        t = np.clip(np.concatenate(ts), 0.0, sg[at])
+        is_end = nc < 0
+        o = np.lexsort((is_end, t, at))
+        at, t, nc, is_end = at[o], t[o], nc[o], is_end[o]
+        head = np.concatenate([[True], at[1:] != at[:-1]])
+        t0 = np.where(head, 0.0, np.concatenate([[0.0], t[:-1]]))
+        ell, tm = t - t0, 0.5 * (t + t0)
+        px, py, pz = g["x"][at] + d[0, at] * tm, g["y"][at] + d[1, at] * tm, g["z"][at] + d[2, at] * tm
+        ci_ = np.clip(np.searchsorted(xe, px - np.floor((px - x0) / Lx) * Lx, side="right") - 1, 0, nx - 1)
+        cj_ = np.clip(np.searchsorted(ye, py - np.floor((py - y0) / Ly) * Ly, side="right") - 1, 0, ny - 1)
+        lz_ = np.clip(np.searchsorted(ze, pz, side="right") - 1, 0, nz - 1)
+        if variant == "piece credited to the cell after the step":
+            nxt = np.where(is_end, np.arange(len(at)), np.minimum(np.arange(len(at)) + 1, len(at) - 1))
+            ci_, cj_, lz_ = ci_[nxt], cj_[nxt], lz_[nxt]
+        if variant == "arrival piece left out":
+            ell = np.where(is_end & g["ev"][at], 0.0, ell)
+        wt, ewt, adz_ = g["w"][at], g["e_w"][at], np.abs(d[2, at])
+        side = nc > 0
+        cs = np.cumsum(side) - side
+        before = cs - cs[head][np.cumsum(head) - 1]                                # side faces crossed earlier in the segment
+        # a piece's own length: one rounding [the quotient that `step` is, or finish_arrival's], the direction's error, the height's rounding at
+        # every side face crossed before it [(side faces + 1) eps (|z|max + 2 dz) of the height: z is rounded only there], and the
+        # along-path errors of the segment's two ends for the first and the last piece [e_s]
+        e_l = EPS * ell + ell * g["e_dir"][at] / adz_ + before * EPS * (zs + 2 * dzmax) / adz_ + np.where(head, g["first"][at], 0.0) + np.where(is_end, g["last"][at], 0.0)
+        bd = wt * (ewt * ell + e_l)
+        val = wt * ell
+        np.add.at(T["trackLayers"], lz_, val)
+        np.add.at(Bd["trackLayers"], lz_, bd)
+        # a side face: the position's error moves length from one cell to its neighbour, at most the shorter of the two pieces
+        nxt_ell = np.concatenate([ell[1:], [0.0]])
+        tr = np.where(side, wt * np.minimum(np.minimum(g["e_xy"][at] / np.maximum(nc, 1e-300), ell), nxt_ell), 0.0)
+        bd = bd + tr + np.concatenate([[0.0], tr[:-1]])                            # (a side face is never a segment's last entry)
+        np.add.at(T["tracks"], (lz_, cj_, ci_), val)
+        np.add.at(Bd["tracks"], (lz_, cj_, ci_), bd)
+        np.add.at(X["trackPieces"], (lz_, cj_, ci_), 1)
+        np.add.at(X["perPhoton"]["tracks"], g["idx"][at], val)
+
     # ---- block 0: start position, first optical depth -------------------------------------------------------------------------
     all_ = np.arange(n)
     u = roles(all_, 0)
@@ -368,6 +536,13 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0):
     ciy = np.clip(np.searchsorted(ye, y, side="right") - 1, 0, ny - 1).astype(f64)
     lay = np.full(n, min(int(np.searchsorted(ze, zstart, side="right") - 1), nz - 1))
     alive = np.ones(n, bool)
+    if extra == "levels" and variant != "new photon not counted":
+        # a new photon is counted at the face of its start layer that lies behind it, downward, in its start column [part C, ST_NEW:
+        # `down ? r.iz : r.iz - 1`, the column find_xy gave].  The start column is a decision: x0 + u (xMax - x0), one product, one sum
+        ci_, cj_ = cix.astype(np.int64), ciy.astype(np.int64)
+        decide(all_, np.minimum(np.minimum(x - xe[ci_], xe[ci_ + 1] - x), np.minimum(y - ye[cj_], ye[cj_ + 1] - y)), e_h, "start column")
+        np.add.at(T["levelFluxDown"], (lay + 1, cj_, ci_), 1.0)
+        X["perPhoton"]["levelFluxDown"][all_, lay + 1] += 1.0
     pfi_ev = None
     surface_z = float(f32(P.ze[0] + (np.spacing(np.abs(P.ze[0])) if P.ze[0] != 0 else f32(TINY))))   # z0 + spacing(z0)
 
@@ -403,6 +578,47 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0):
         e_s = (e_cn / ext_new + e_c[idx] / ext_old) / adz + np.abs(s) * e_dir[idx] / adz
         e_xy = e_h[idx] + np.abs(s) * e_dir[idx] + np.maximum(np.abs(dvec[0, idx]), np.abs(dvec[1, idx])) * e_s + steps * EPS * (xs + 2 * dxmax)
         xw, yw, ci, cj, _ = column(idx, xu, yu, e_xy, "column")
+        sabs = np.abs(s)
+        L_before = Lp[idx].copy()
+        if path_kind:
+            # the path grows by the pieces the tracer steps [photon_step: `pathLen += (double)len`; the event phase: `pathLen +=
+            # (double)part`]: the segment's along-path error, and one float32 rounding per voxel-step piece and for the arrival piece
+            Lp[idx] += sabs
+            e_L[idx] += e_s + steps * EPS * sabs
+        if extra == "levels":
+            # a segment from layer a to layer b adds its weight to levelFluxUp[a .. b - 1] going up, to levelFluxDown[b .. a - 1] going
+            # down [part A: tally_level_crossings with izFrom, and izTo = nz + 1 at the top, 0 on the surface]
+            a_, b_ = lay[idx] + 1, np.where(top, nz + 1, np.where(bottom, 0, lnew + 1))
+            sh = 1 if variant == "downward range shifted by one level" else 0
+            dh = np.maximum(np.abs(dvec[0, idx]), np.abs(dvec[1, idx]))
+            for k in range(nz + 1):
+                for key, hit, ends in (("levelFluxUp", up & (a_ <= k) & (k <= b_ - 1), top & (k == nz)),
+                                       ("levelFluxDown", ~up & (b_ + sh <= k) & (k <= a_ - 1 + sh), bottom & (k == 0))):
+                    h = np.nonzero(hit)[0]
+                    if not len(h):
+                        continue
+                    li, lj = ci[h].copy(), cj[h].copy()         # the level a segment ends on takes the arrival's own column
+                    far = ~ends[h]
+                    q = h[far]
+                    if len(q) and variant != "crossing counted in the arrival column":
+                        # every other level: the column of the point where the straight segment meets ze[k], which the kernel extrapolates
+                        # BACK from the arrival in float32 [tally_level_crossings]: back = (z - zE[k]) / dz (a difference, a quotient),
+                        # cx = x - dx * back (a product, a difference), cx - floorf((cx - x0) / widthX) * widthX (a difference, a
+                        # quotient, a product, a difference); the clamp rounds nothing
+                        tk = (ze[k] - z[idx[q]]) / dz[q]
+                        back = s[q] - tk
+                        hb = dh[q] * np.abs(back)
+                        e_lc = e_xy[q] + np.abs(back) * e_dir[idx[q]] + EPS * (3 * hb + 4 * (xs + hb) + xs)
+                        _, _, pi_, pj_, _ = column(idx[q], x[idx[q]] + dvec[0, idx[q]] * tk, y[idx[q]] + dvec[1, idx[q]] * tk, e_lc, "level column")
+                        li[far], lj[far] = pi_, pj_
+                    np.add.at(T[key], (k, lj, li), w[idx[h]])
+                    np.add.at(Bd[key], (k, lj, li), w[idx[h]] * e_w[idx[h]])
+                    X["perPhoton"][key][idx[h], k] += w[idx[h]]
+        if extra == "tracks":
+            trk = dict(idx=idx, x=x[idx].copy(), y=y[idx].copy(), z=z[idx].copy(), d=dvec[:, idx].copy(), s=sabs, l0=lay[idx].copy(), l1=lnew,
+                       gx0=cix[idx].copy(), gy0=ciy[idx].copy(), gx1=kx * nx + ci0, gy1=ky * ny + cj0, ev=ev, w=w[idx].copy(), e_w=e_w[idx].copy(),
+                       e_dir=e_dir[idx].copy(), e_xy=e_xy, first=e_c[idx] / ext_old / adz, last=e_cn / ext_new / adz)
+            X["perPhoton"]["wS"][idx] += w[idx] * sabs
         x[idx], y[idx], z[idx] = xw, yw, znew
         cix[idx], ciy[idx], lay[idx] = ci, cj, lnew
         e_c[idx], e_h[idx] = e_cn, e_xy
@@ -413,6 +629,10 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0):
         np.add.at(Bd["fluxUp"], (cj[top], ci[top]), w[t] * e_w[t])
         dep["fluxUp"][t] += w[t]
         cnt["exitsTop"][t] += 1
+        if path_kind and len(t):   # [part A: bin_add / path_add beside tally.boundary, the same column]
+            if variant == "last segment left out of L":
+                Lp[t] = L_before[top]
+            path_deposit(t, cj[top], ci[top], True, w[t], e_w[t], L_before[top] if variant == "bin of L before the last segment" else Lp[t])
         fate[t], wfin[t], alive[t] = 0, w[t], False
 
         # ---- the surface ----------------------------------------------------------------------------------------------------
@@ -422,6 +642,11 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0):
             np.add.at(Bd["fluxDown"], (cj[bottom], ci[bottom]), w[b] * e_w[b])
             dep["fluxDown"][b] += w[b]
             cnt["surfaceHits"][b] += 1
+            if path_kind:   # the weight BEFORE the reflection, the path up to here [part A for a black surface; part C beside tally.down]
+                if variant == "last segment left out of L":
+                    Lp[b] = L_before[bottom]
+                wb = w[b] * alb if variant == "surface tally with the weight after the reflection" else w[b]
+                path_deposit(b, cj[bottom], ci[bottom], False, wb, e_w[b], L_before[bottom] if variant == "bin of L before the last segment" else Lp[b])
             fate[b], wfin[b] = 1, w[b]
             if black:
                 alive[b] = False
@@ -444,6 +669,15 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0):
                 e_dir[g] = SINCOS * np.sqrt(2.0) * sg + 2 * EPS
                 z[g] = surface_z
                 lay[g] = 0
+                if variant == "path restarts at a reflection":
+                    Lp[g], e_L[g] = 0.0, 0.0
+                if extra == "levels" and variant != "reflected photon not counted":
+                    # levelFluxUp[0]: the reflected weight, in the column where it was reflected [part C: `add_global(... + c2, w)`
+                    # behind `w = w * Pe.albedo`, only for a photon that goes on]
+                    gj, gi = cj[bottom][~dead], ci[bottom][~dead]
+                    np.add.at(T["levelFluxUp"], (0, gj, gi), w[g])
+                    np.add.at(Bd["levelFluxUp"], (0, gj, gi), w[g] * e_w[g])
+                    X["perPhoton"]["levelFluxUp"][g, 0] += w[g]
                 if nd:
                     radiance(g, None, x[g], y[g], z[g], None, w[g], e_c[g], e_h[g], e_dir[g], e_w[g], order[g])
                 tau[g] = -np.log(np.maximum(TINY, u[2][~dead]))
@@ -479,7 +713,11 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0):
             np.add.at(T["volumeAbsorption"], (le, cje, cie), inc)
             np.add.at(Bd["volumeAbsorption"], (le, cje, cie), inc * (e_w[e] + 2 * EPS))
             dep["volumeAbsorption"][e] += inc
+            if extra == "levels":
+                X["perPhoton"]["absLayer"][e, le] += inc
             w[e] = np.where(absorbing, w[e] * om, w[e])
+            if variant == "weight after the scattering":
+                trk["w"][ev] = w[e]
             e_w[e] += np.where(absorbing, EPS, 0.0)
             if nd:
                 radiance(e, comp, x[e], y[e], z[e], dvec[:, e], w[e], e_c[e], e_h[e], e_dir[e], e_w[e], order[e])
@@ -545,6 +783,8 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0):
                 dvec[:, g] = snew
                 tau[g] = -np.log(np.maximum(TINY, u[2][keep]))
                 cnt["rngDraws"][g] += 3
+        if extra == "tracks":
+            track_pieces(trk)
 
     T["fluxAbsorbed"] = T["volumeAbsorption"].sum(0)
     Bd["fluxAbsorbed"] = Bd["volumeAbsorption"].sum(0)
@@ -571,7 +811,11 @@ def run(P, seed, first_photon, n, variant=None, drop_high_word=False, batch=0):
         for k in ("intensity", "intensityExcess"):
             exact_zero[k] = np.zeros(T[k].shape, bool)
             exact_zero[k][:, P.dirs[:, 2] < 0] = True
-    return Result(n, T, Bd, counters, per, caps, branches, exact_zero)
+    if path_kind:
+        X["path"], X["pathError"] = Lp, e_L     # every photon's path at its end, and the model's bound on it
+        # every tally of a path, one column each: photon (its index in this run), L, the bound on float(L), weight, 1 up / 0 down
+        X["deposits"] = np.concatenate(X["deposits"], axis=1) if X["deposits"] else np.zeros((5, 0))
+    return Result(n, T, Bd, counters, per, caps, branches, X, exact_zero)
 
 
 def _rowwise(rows, theta):
@@ -596,6 +840,20 @@ def clean_range(model, start=0):
     return int(edges[k] + 1), int(edges[k + 1] - edges[k] - 1)
 
 
+def clean_runs(model, start=0, least=1):
+    """[(first, count)] of ALL maximal runs of at least `least` consecutive photons of a run (from its photon `start` on) none of which is
+    fragile, in order.  The diagnostic tallies are compared over exactly these photons: a path has no upper limit, so nothing caps what
+    a fragile photon may carry into a path sum, a bin or a cell's track length"""
+    frag = np.nonzero(model.per_photon["fragile"])[0]
+    cuts = np.concatenate([[start - 1], frag[frag >= start], [model.n]])
+    return [(int(a + 1), int(b - a - 1)) for a, b in zip(cuts[:-1], cuts[1:]) if b - a - 1 >= max(least, 1)]
+
+
+def run_ids(runs, offset=0):
+    """the photon numbers of the runs [(first, count)], as `run(..., ids=...)` takes them"""
+    return np.concatenate([np.uint64(offset) + np.uint64(a) + np.arange(c, dtype=np.uint64) for a, c in runs])
+
+
 COUNTERS_EXACT = ("photons", "dropped")
 COUNTERS_FRAGILE = ("scatterings", "surfaceHits", "exitsTop", "roulette", "rngDraws", "raysSkipped", "tracerCalls")
 
@@ -618,7 +876,11 @@ def compare(model, tallies, counters, counter_names=COUNTERS_EXACT + COUNTERS_FR
     miss, worst = compare_counters([model], counters, counter_names), {}
     for k, want in model.tallies.items():
         got = np.asarray(tallies[k], f64).reshape(want.shape)
-        slack = float(model.caps[k][frag].sum())
+        if k in model.caps:
+            slack = float(model.caps[k][frag].sum())
+        else:   # a diagnostic field: a path has no upper limit, so a fragile photon has no cap -- such a field is compared over photons none of which is fragile
+            assert not frag.any(), (k, "a diagnostic tally is compared only over photons that are not fragile")
+            slack = 0.0
         tol = model.bounds[k] + slack
         if k in model.exact_zero:
             assert not want[model.exact_zero[k]].any()
@@ -707,13 +969,57 @@ FRAGILE_CAP = 0.005
 FUSED_CLEAN_SEED, FUSED_CLEAN_N, FUSED_CLEAN_CASES = (3, 4), 750, ("r one up", "r three")
 
 
-def problem(case, inverse, forward=None, forward_orig=None, dirs=None):
+def problem(case, inverse, forward=None, forward_orig=None, dirs=None, extra=None, bin_edges=None):
     """the model's problem for a shared case, with the tables (and directions) the host hands to the device"""
     p = case["params"]
     return Problem(case["xe"], case["ye"], case["ze"], case["ext"], case["ssa"], case["pfi"], inverse, mu0=SUN[0], azimuth=SUN[1],
                    albedo=p["albedo"], roulette=p.get("roulette", True), dirs=dirs, fwd=forward, fwd_orig=forward_orig,
                    hybrid=bool(p.get("hybrid")), orders_orig=int(p.get("hybrid", 0)), max_contrib=p.get("limit"),
-                   rr_intensity=bool(p.get("rr_intensity", False)), zeta_min=p.get("zeta_min", 0.3))
+                   rr_intensity=bool(p.get("rr_intensity", False)), zeta_min=p.get("zeta_min", 0.3), extra=extra, bin_edges=bin_edges)
+
+
+# ---- the diagnostic tallies' cases --------------------------------------------------------------------------------------------------
+# The flux cases (the diagnostics refuse radiance directions) at their own sizes: 20 000 photons, 4 x 3 columns, 8 layers.  A case whose
+# share of fragile photons with the kind's new decisions (start column, level column, bin) would exceed FRAGILE_CAP, or whose track
+# bounds would exceed TRACK_RESOLUTION, is RESHAPED for that kind as `r wide` is: the same medium under columns a hundred times as wide
+# (conditions on the inputs, asserted in tests/test_stream_model_cpu.py; the bound and the cap stay)
+KINDS = EXTRAS[1:]
+DIAGNOSTIC_CASES = ("a absorbing", "b records", "c two", "e irregular", "f no roulette", "g black", "g white")
+DIAGNOSTIC_WIDE = {"levels": ("e irregular", "f no roulette", "g white"), "tracks": ("b records", "g white"), "paths": (),
+                   "bins": ("c two", "e irregular", "f no roulette", "g white")}
+# ... and `g white` runs its track lengths over photons 60 000 .. 79 999: the columns do not reshape what misses the resolution there.  A
+# white surface sends photons up again and again, some of them within a few 1e-5 of the horizontal -- just beyond 4 bounds of the
+# "frame" decision --, and one such photon's 28 m inside one cell, uncertain by the relative error e_dir / |dz| of its slant, is a
+# bound of 1.6e-3 of that cell's entry on its own (photons 0 .. 19 999: photon 14 185, |dz| 1.4e-5, e_dir 3.3e-6).  Of the twelve ranges
+# of 20 000 photons from 0 on, this is the first whose worst cell is below half the resolution (4.5e-4)
+DIAGNOSTIC_FIRST = {("tracks", "g white"): 60_000}
+TRACK_RESOLUTION = 1e-3     # summed bound / entry in every cell with TRACK_PIECES pieces: what the statistical tests resolve already
+TRACK_PIECES = 1000
+# The histogram's edges: 0, then a geometric progression (first edge, ratio, bins), chosen on the CPU per case so that the overflow bin
+# holds something but under 1 % of the weight, 20 bins hold 100 photons each and the bin decision leaves the fragile share within the
+# cap.  One progression does not serve every case: the long paths of `f no roulette` and `g white` (no roulette; a white surface) carry
+# the largest path errors and want wide bins, the 20 000 single tallies of `g black` fill 20 bins only where the bins are narrow
+BIN_EDGES = {"a common": (20.0, 1.06, 50), "a absorbing": (20.0, 1.06, 50), "b records": (20.0, 1.06, 50), "c two": (20.0, 1.06, 50), "e irregular": (20.0, 1.06, 50),
+             "f no roulette": (10.0, 1.15, 24), "g black": (20.0, 1.04, 60), "g white": (10.0, 1.15, 30)}
+
+
+def bin_edges(name):
+    first, ratio, nbins = BIN_EDGES[name]
+    return np.concatenate([[0.0], first * f64(ratio) ** np.arange(nbins)]).astype(f32)
+
+
+def diagnostic_case(name, kind):
+    """the shared case `name` as the diagnostic kind runs it: its own, or under columns a hundred times as wide (DIAGNOSTIC_WIDE)"""
+    c = dict(CASES[name])
+    if name in DIAGNOSTIC_WIDE[kind]:
+        c["xe"], c["ye"] = (f32(100.0) * c["xe"]).astype(f32), (f32(100.0) * c["ye"]).astype(f32)
+    return c
+
+
+def unscattered_path(P):
+    """the path of a photon that reaches the surface without an event: (zstart - ze[0]) / |mu0| with the host's direction"""
+    zstart = float(f32(P.ze[0] + f32(f32(f32(1.0) - f32(ULP)) * f32(P.ze[-1] - P.ze[0]))))
+    return (zstart - float(P.ze[0])) / abs(float(direction(-abs(P.mu0), P.azimuth)[2]))
 
 
 def case_directions(case):
@@ -749,6 +1055,16 @@ FRAGILE_SHARES = {
     'r wide': 0.001,
 }
 
+# ... and of every diagnostic case and kind, the kind's own decisions among the reasons, at the shapes and photons S.diagnostic_case,
+# BIN_EDGES and DIAGNOSTIC_FIRST give (`a common`: the histogram's exact-sum case alone)
+DIAGNOSTIC_SHARES = {
+    'levels': {'a absorbing': 0.0035, 'b records': 0.0028, 'c two': 0.0045, 'e irregular': 0.00125, 'f no roulette': 0.002, 'g black': 0.0022, 'g white': 0.00215},
+    'tracks': {'a absorbing': 0.0013, 'b records': 0.00055, 'c two': 0.00245, 'e irregular': 0.00225, 'f no roulette': 0.00455, 'g black': 0.0008, 'g white': 0.00095},
+    'paths': {'a absorbing': 0.0013, 'b records': 0.00135, 'c two': 0.00245, 'e irregular': 0.00225, 'f no roulette': 0.00455, 'g black': 0.0008, 'g white': 0.00435},
+    'bins': {'a common': 0.0046, 'a absorbing': 0.0031, 'b records': 0.00385, 'c two': 0.00445, 'e irregular': 0.0031, 'f no roulette': 0.0042, 'g black': 0.00315,
+             'g white': 0.0038},
+}
+
 if __name__ == "__main__":
     from tests.test_stream_model_cpu import model_for
 
@@ -758,3 +1074,9 @@ if __name__ == "__main__":
         if CASES[name]["params"].get("rr_intensity"):
             first, count = clean_range(r)
             print(f"{'':26s} rays {r.branches}\n{'':26s} clean run {first} + {count}: {model_for(name, first=first, n=count).branches}")
+    from tests.test_stream_model_cpu import diagnostic_model
+
+    for kind in KINDS:
+        for name in DIAGNOSTIC_CASES + (("a common",) if kind == "bins" else ()):
+            r = diagnostic_model(name, kind)
+            print(f"{kind:7s} {name:14s} {'wide' if name in DIAGNOSTIC_WIDE[kind] else 'own ':4s} fragile {r.fragile_share:.5f} {r.per_photon['why']}")

@@ -16,7 +16,18 @@ both shown without a GPU:
     comparison on the run without fragile photons, and on a whole case where one can see them at all (RAY_CONTROLS says which, and why
     a mere re-draw of the rays' deviates is a thousandth of what a whole case allows its fragile photons).  A fused launch starts at
     photon 0: the key S.FUSED_CLEAN_SEED, whose three batches begin with 750 photons none of them fragile, is where the key without
-    the batch fails for fused launches; a ray block without the photon's high word fails on the clean window beyond 2^32."""
+    the batch fails for fused launches; a ray block without the photon's high word fails on the clean window beyond 2^32;
+  * the four diagnostic tallies (Problem.extra: levels, tracks, paths, bins), compared over photons that are not fragile only:
+    identities exact in the model's float64, per photon and per column (levelFluxDown[0] = fluxDown, levelFluxUp[nz] = fluxUp, the
+    sum of levelFluxDown[nz] = n, the bins add up to the fluxes and the path bins to the first moments, the cells' track lengths to
+    the photons' w |s|; without roulette the net level flux into a layer is what the photon leaves there, to 1e-12); batches of the
+    model against tests/level_flux_solver.py at every level, against the equivalence-theorem figures of tests/test_gpu_path_lengths.py
+    (+ the reference's own finite-difference uncertainty) and (1 - omega) sigma dz <actinic flux> against the net-flux divergence, 4
+    standard errors + SOLVER; the conditions on the inputs -- fragile shares with the new decisions within the cap for every case and
+    kind (S.DIAGNOSTIC_SHARES), histogram edges per case with an overflow bin that holds something but under 1 % of the weight, 20 bins
+    of 100 photons and no edge within 1e-4 of the unscattered path, track bounds at most 1e-3 of every cell with 1000 pieces --; and
+    eleven controls (S.EXTRA_VARIANTS), each FAILING the GPU module's comparison on `a absorbing` and on `c two` by the diagnostic
+    fields alone."""
 import functools
 
 import numpy as np
@@ -56,6 +67,32 @@ def case_problem(name):
 @functools.lru_cache(maxsize=None)
 def model_for(name, seed=S.SEED, first=0, n=None, variant=None, drop=False, batch=0):
     return S.run(case_problem(name), seed, first, n or S.CASES[name]["n"], variant=variant, drop_high_word=drop, batch=batch)
+
+
+def diagnostic_problem(name, kind):
+    """the model's problem for the shared flux case `name` with the diagnostic tally `kind` on (S.diagnostic_case: its own columns, or wide ones)"""
+    c = S.diagnostic_case(name, kind)
+    return S.problem(c, [tables(tuple(gs))[0] for gs in c["gs"]], extra=kind, bin_edges=S.bin_edges(name) if kind == "bins" else None)
+
+
+@functools.lru_cache(maxsize=None)
+def diagnostic_model(name, kind, first=None, n=None, variant=None):
+    """the whole case (first: the first photon, by default the kind's and case's own -- S.DIAGNOSTIC_FIRST, else 0)"""
+    first = S.DIAGNOSTIC_FIRST.get((kind, name), 0) if first is None else first
+    return S.run(diagnostic_problem(name, kind), S.SEED, first, n or S.CASES[name]["n"], variant=variant)
+
+
+def diagnostic_runs(name, kind, first=None, n=None, start=0, least=1):
+    """every maximal run (first photon, count) of at least `least` photons of the case none of which is fragile -- with the kind's own
+    decisions among the reasons --, as photon numbers: what the GPU module launches one after the other into one block"""
+    first = S.DIAGNOSTIC_FIRST.get((kind, name), 0) if first is None else first
+    return [(first + a, c) for a, c in S.clean_runs(diagnostic_model(name, kind, first, n), start=start, least=least)]
+
+
+@functools.lru_cache(maxsize=None)
+def diagnostic_clean(name, kind, variant=None, first=None, n=None, start=0, least=1):
+    """the model over exactly the photons of diagnostic_runs: the expected value of every diagnostic entry, with the float32 bound alone"""
+    return S.run(diagnostic_problem(name, kind), S.SEED, 0, 0, variant=variant, ids=S.run_ids(diagnostic_runs(name, kind, first, n, start, least)))
 
 
 # ---- Philox ----------------------------------------------------------------------------------------------------------------------
@@ -389,3 +426,219 @@ def test_a_ray_block_without_the_high_word_fails_the_comparison(name, first):
     clean = model_for(name, first=at, n=count)
     assert not clean.per_photon["fragile"].any()
     assert _fails(clean, model_for(name, first=at, n=count, variant="ray block without the high word")), (name, first)
+
+
+# ---- the diagnostic tallies: level fluxes, track lengths, path moments, the path histogram ----------------------------------------------
+DIAGNOSTICS = [(name, kind) for kind in S.KINDS for name in S.DIAGNOSTIC_CASES]
+LEAST = 64   # the shortest run of photons the GPU module launches on its own
+
+
+@pytest.mark.parametrize("name,kind", DIAGNOSTICS + [("a common", "bins")])
+def test_fragile_share_of_the_diagnostic_cases(name, kind):
+    """a condition on the inputs: with the kind's own decisions (start column, level column, bin) the share stays within the project's
+    cap, and the runs without a fragile photon that the GPU module launches hold nine photons in ten"""
+    r = diagnostic_model(name, kind)
+    assert r.fragile_share <= S.FRAGILE_CAP, (name, kind, r.fragile_share, r.per_photon["why"])
+    assert abs(r.fragile_share - S.DIAGNOSTIC_SHARES[kind][name]) < 1e-9, (name, kind, r.fragile_share)   # (the shares written down are the ones measured)
+    new = {"levels": ("start column", "level column"), "bins": ("bin",)}.get(kind, ())
+    assert all(k in r.per_photon["why"] for k in new[-1:]), r.per_photon["why"]                            # (the new decisions do decide)
+    clean = diagnostic_clean(name, kind, least=LEAST)
+    assert clean.n >= 0.9 * r.n and not clean.per_photon["fragile"].any(), (name, kind, clean.n)
+    assert min(clean.counters[k] for k in ("scatterings", "surfaceHits", "exitsTop")) >= 1000, clean.counters
+    assert S.compare(clean, clean.tallies, clean.counters)[0] == []
+
+
+@pytest.mark.parametrize("kind", S.KINDS)
+def test_the_window_across_two_to_the_32_has_runs_on_both_sides(kind):
+    """1500 photons of `a absorbing` from 2^32 - 700: what the GPU module launches there are the runs of at least 64 photons without a
+    fragile one, and they hold some hundreds of photons below and beyond 2^32.  (The cap on the share is a statement about a case's
+    20 000 photons, asserted above; of 1500 photons it allows 7, and the level columns of this window happen to take 9.)"""
+    runs = diagnostic_runs("a absorbing", kind, first=2 ** 32 - 700, n=1500, least=LEAST)
+    assert sum(c for a, c in runs if a + c <= 2 ** 32) >= 300 and sum(a + c - max(a, 2 ** 32) for a, c in runs if a + c > 2 ** 32) >= 300, runs
+
+
+def test_clean_runs_are_all_the_maximal_runs():
+    r = model_for("a absorbing")
+    runs = S.clean_runs(r)
+    frag = r.per_photon["fragile"]
+    covered = np.zeros(r.n, bool)
+    for a, c in runs:
+        assert c >= 1 and not frag[a:a + c].any() and (a == 0 or frag[a - 1]) and (a + c == r.n or frag[a + c])
+        covered[a:a + c] = True
+    assert np.array_equal(covered, ~frag)
+    assert max(runs, key=lambda t: t[1]) == S.clean_range(r)
+    assert S.clean_runs(r, least=LEAST) == [t for t in runs if t[1] >= LEAST]
+    ids = S.run_ids(runs[:3])
+    assert len(ids) == sum(c for _, c in runs[:3]) and ids[0] == runs[0][0]
+    # ... and the model over those photon numbers is the sum of the model over each run (photons do not know of each other)
+    whole = S.run(case_problem("a absorbing"), S.SEED, 0, 0, ids=ids)
+    parts = [S.run(case_problem("a absorbing"), S.SEED, a, c) for a, c in runs[:3]]
+    assert whole.counters == {k: sum(p.counters[k] for p in parts) for k in whole.counters}
+    assert all(np.allclose(whole.tallies[k], sum(p.tallies[k] for p in parts), rtol=1e-13, atol=0) for k in whole.tallies)
+
+
+def _close(a, b, rtol=1e-12):
+    return np.allclose(a, b, rtol=rtol, atol=rtol * max(1.0, float(np.max(np.abs(b)))))
+
+
+@pytest.mark.parametrize("name", S.DIAGNOSTIC_CASES)
+def test_identities_of_the_diagnostic_tallies(name):
+    """exact in the model's float64, per column and per photon"""
+    import dataclasses
+
+    lev, trk, bins = (diagnostic_model(name, k) for k in ("levels", "tracks", "bins"))
+    nz = lev.tallies["levelFluxUp"].shape[0] - 1
+    up, down = (lev.caps[k] - 1.0 for k in ("fluxUp", "fluxDown"))            # (a cap is 1 + the photon's own deposit)
+    assert _close(lev.tallies["levelFluxDown"][0], lev.tallies["fluxDown"]) and _close(lev.tallies["levelFluxUp"][nz], lev.tallies["fluxUp"])
+    assert _close(lev.extras["perPhoton"]["levelFluxDown"][:, 0], down) and _close(lev.extras["perPhoton"]["levelFluxUp"][:, nz], up)
+    assert lev.tallies["levelFluxDown"][nz].sum() == lev.n and (lev.extras["perPhoton"]["levelFluxDown"][:, nz] >= 1.0).all()
+    # the bins add up to the fluxes, per photon too; the path bins to the first moments of the same problem's path sums
+    pp = bins.extras["perPhoton"]
+    assert _close(pp["binUp"], bins.caps["fluxUp"] - 1.0) and _close(pp["binDown"], bins.caps["fluxDown"] - 1.0)
+    assert _close(bins.tallies["binUp"].sum(), bins.tallies["fluxUp"].sum()) and _close(bins.tallies["binDown"].sum(), bins.tallies["fluxDown"].sum())
+    paths = S.run(dataclasses.replace(diagnostic_problem(name, "bins"), extra="paths", bin_edges=None), S.SEED, 0, bins.n)
+    assert _close(bins.tallies["binPathUp"].sum(), paths.tallies["pathUp1"].sum()) and _close(bins.tallies["binPathDown"].sum(), paths.tallies["pathDown1"].sum())
+    assert _close(pp["binPathUp"], paths.extras["perPhoton"]["pathUp1"]) and _close(pp["binPathDown"], paths.extras["perPhoton"]["pathDown1"])
+    assert (paths.tallies["pathUp2"] * paths.tallies["fluxUp"] >= paths.tallies["pathUp1"] ** 2 * (1 - 1e-12)).all()   # (Cauchy-Schwarz, per column)
+    # the track lengths of all cells are the photons' weighted segments
+    assert _close(trk.extras["perPhoton"]["tracks"], trk.extras["perPhoton"]["wS"])
+    assert _close(trk.tallies["tracks"].sum(), trk.extras["perPhoton"]["wS"].sum()) and _close(trk.tallies["tracks"].sum(axis=(1, 2)), trk.tallies["trackLayers"])
+    assert (trk.bounds["trackLayers"] <= trk.bounds["tracks"].sum(axis=(1, 2)) * (1 + 1e-12)).all()     # (the transfer terms vanish in a layer's sum)
+
+
+def test_net_level_flux_is_the_absorption_without_roulette():
+    """`f no roulette`: what flows into a layer and not out of it is what the photon leaves there as absorption, photon by photon"""
+    r = diagnostic_model("f no roulette", "levels")
+    pp = r.extras["perPhoton"]
+    net = pp["levelFluxDown"] - pp["levelFluxUp"]
+    into = net[:, 1:] - net[:, :-1]
+    assert np.abs(into - pp["absLayer"]).max() < 1e-12, np.abs(into - pp["absLayer"]).max()
+    assert pp["absLayer"].sum() > 0.3 * r.n
+
+
+# ... against independent references: batches of the model as above, 4 standard errors of its own batches + SOLVER
+DIAGNOSTIC_SLABS = [(1.0, 0.9, 0.5), (1.0, 1.0, 0.0), (10.0, 0.9, 0.5), (10.0, 1.0, 0.0)]
+
+
+@functools.lru_cache(maxsize=None)
+def _slab_batches(tau, omega, albedo, kind):
+    import dataclasses
+    from tests.test_plane_parallel import MOMENTS
+
+    n, nb = (30_000 if tau < 5 else 10_000), 10
+    P = dataclasses.replace(_slab(tau, omega, albedo, MOMENTS), extra=kind)
+    return P, [S.run(P, (10, b), 0, n) for b in range(1, nb + 1)]
+
+
+def _mean_se(per):
+    per = np.asarray(per)
+    return per.mean(0), per.std(0, ddof=1) / np.sqrt(len(per))
+
+
+@pytest.mark.parametrize("tau,omega,albedo", DIAGNOSTIC_SLABS)
+def test_model_level_fluxes_against_the_level_solver(tau, omega, albedo):
+    from tests.level_flux_solver import solve_levels
+    from tests.test_plane_parallel import G, MU0, _sampled_moments
+
+    P, rs = _slab_batches(tau, omega, albedo, "levels")
+    ze = P.ze.astype(np.float64)
+    depth = tau * (ze[-1] - ze) / (ze[-1] - ze[0])                      # optical depth above level k
+    want = solve_levels(depth, tau, omega, G, MU0, albedo=albedo, chi=_sampled_moments())
+    for key, ref in zip(("levelFluxUp", "levelFluxDown"), want):
+        got, se = _mean_se([r.tallies[key].sum(axis=(1, 2)) / r.n for r in rs])
+        assert (np.abs(got - ref) <= 4.0 * se + SOLVER).all(), (key, tau, omega, albedo, got - ref, se)
+
+
+@pytest.mark.parametrize("tau,omega,albedo", DIAGNOSTIC_SLABS)
+def test_model_mean_paths_against_the_equivalence_theorem(tau, omega, albedo):
+    """<L> of the reflected and of the transmitted light, and <L^2>, against the figures tests/test_gpu_path_lengths.py derives from the
+    adding-doubling solver; the reference's own finite-difference uncertainty is added as it is there"""
+    from tests.test_gpu_path_lengths import _solver_moments
+
+    P, rs = _slab_batches(tau, omega, albedo, "paths")
+    H = float(P.ze[-1]) - float(P.ze[0])
+    per = [[r.tallies["pathUp1"].sum() / r.tallies["fluxUp"].sum() / H, r.tallies["pathDown1"].sum() / r.tallies["fluxDown"].sum() / H,
+            r.tallies["pathUp2"].sum() / r.tallies["fluxUp"].sum() / H ** 2, r.tallies["pathDown2"].sum() / r.tallies["fluxDown"].sum() / H ** 2] for r in rs]
+    got, se = _mean_se(per)
+    m1, m2, u1, u2 = _solver_moments(tau, omega, albedo)
+    want, unc = np.concatenate([m1, m2]), np.concatenate([u1, u2])
+    assert (want[:2] > 0.5).all() and (se > 0).all()
+    assert (np.abs(got - want) <= 4.0 * se + SOLVER + unc).all(), (tau, omega, albedo, got - want, se, unc)
+
+
+@pytest.mark.parametrize("tau,albedo", [(1.0, 0.0), (1.0, 0.5), (10.0, 0.0), (10.0, 0.5)])
+def test_model_actinic_flux_against_the_net_flux_divergence(tau, albedo):
+    """(1 - omega) sigma dz <actinic flux> of a layer is what the layer absorbs: the solver's net flux into it less the net flux out"""
+    from tests.level_flux_solver import solve_levels
+    from tests.test_plane_parallel import G, MU0, _sampled_moments
+
+    omega = 0.9
+    P, rs = _slab_batches(tau, omega, albedo, "tracks")
+    ze = P.ze.astype(np.float64)
+    sigma, om = float(P.ext[0, 0]), float(P.ssa[0, 0])
+    depth = sigma * (ze[-1] - ze)
+    up, down = solve_levels(depth, depth[0], omega, G, MU0, albedo=albedo, chi=_sampled_moments())
+    net = down - up
+    want = net[1:] - net[:-1]
+    got, se = _mean_se([(1.0 - om) * sigma * r.tallies["trackLayers"] / r.n for r in rs])
+    assert (want > 1e-3).all()
+    assert (np.abs(got - want) <= 4.0 * se + SOLVER).all(), (tau, albedo, got - want, se)
+    # ... and it is the model's own absorption, batch by batch, within the sampling of the collisions
+    own, se_own = _mean_se([(1.0 - om) * sigma * r.tallies["trackLayers"] / r.n - r.tallies["volumeAbsorption"].sum(axis=(1, 2)) / r.n for r in rs])
+    assert (np.abs(own) <= 4.0 * se_own + SOLVER).all(), (own, se_own)
+
+
+# ... the conditions on the inputs
+@pytest.mark.parametrize("name", S.DIAGNOSTIC_CASES + ("a common",))
+def test_the_histograms_edges_suit_the_case(name):
+    e = S.bin_edges(name).astype(np.float64)
+    first, ratio, nbins = S.BIN_EDGES[name]
+    assert e.dtype == np.float64 and len(e) == nbins + 1 and e[0] == 0 and np.allclose(e[2:] / e[1:-1], ratio, rtol=1e-6)   # a geometric progression behind 0
+    r = diagnostic_model(name, "bins")
+    D = r.extras["deposits"]
+    b = np.clip(np.searchsorted(e, D[1].astype(np.float32).astype(np.float64), side="right") - 1, 0, nbins)
+    count = np.bincount(b, minlength=nbins + 1)
+    weight = r.tallies["binUp"] + r.tallies["binDown"]
+    assert np.allclose(np.bincount(b, weights=D[3], minlength=nbins + 1), weight, rtol=1e-12)
+    assert count[-1] > 0 and 0 < weight[-1] < 0.01 * weight.sum(), (name, count[-1], weight[-1] / weight.sum())
+    assert (count[:-1] >= 100).sum() >= 20, (name, count)
+    direct = S.unscattered_path(diagnostic_problem(name, "bins"))
+    assert np.abs(e[1:] / direct - 1.0).min() > 1e-4, (name, direct)     # (else every direct-beam photon would be fragile at once)
+    # (... the direct beam's share of the case, exp(-tau / mu0) of its photons within five binomial standard deviations)
+    P = diagnostic_problem(name, "bins")
+    share = float(np.exp(-np.sum(P.ext.astype(np.float64).sum(0) * np.diff(P.ze.astype(np.float64))) / abs(float(S.direction(-abs(P.mu0), P.azimuth)[2]))))
+    unscattered = np.count_nonzero((np.abs(D[1] / direct - 1.0) < 1e-12) & (D[4] == 0))
+    assert abs(unscattered - share * r.n) <= 5.0 * np.sqrt(share * (1.0 - share) * r.n), (name, unscattered, share * r.n)
+
+
+@pytest.mark.parametrize("name", S.DIAGNOSTIC_CASES)
+def test_the_track_bounds_resolve_what_the_statistics_do_not(name):
+    """in every cell that receives 1000 pieces the summed bound is at most 1e-3 of the entry (a wider bound would pin nothing the
+    statistical tests do not pin already), on the whole case and over the photons the GPU module launches"""
+    for r in (diagnostic_model(name, "tracks"), diagnostic_clean(name, "tracks", least=LEAST)):
+        big = r.extras["trackPieces"] >= S.TRACK_PIECES
+        assert big.sum() >= 0.9 * big.size, (name, big.sum())
+        worst = float((r.bounds["tracks"][big] / r.tallies["tracks"][big]).max())
+        assert worst <= S.TRACK_RESOLUTION, (name, worst)
+        assert (r.bounds["trackLayers"] / r.tallies["trackLayers"]).max() <= 0.3 * S.TRACK_RESOLUTION
+
+
+# ... the controls: a model with one changed convention must FAIL the comparison the GPU module makes -- over the photons that are not
+# fragile, with the float32 bound alone -- on every case listed (a black surface reflects nothing and a white one keeps the weight:
+# `g black` cannot see the reflection's controls, `g white` not the weight after it)
+DIAGNOSTIC_CONTROLS = [(kind, variant, name) for kind in S.KINDS for variant in S.EXTRA_VARIANTS[kind] for name in ("a absorbing", "c two")]
+
+
+@pytest.mark.parametrize("kind,variant,name", DIAGNOSTIC_CONTROLS)
+def test_a_changed_convention_of_a_diagnostic_tally_fails_the_comparison(kind, variant, name):
+    base = diagnostic_clean(name, kind, least=LEAST)
+    other = diagnostic_clean(name, kind, variant=variant, least=LEAST)
+    assert base.counters == other.counters                       # (the photons are the same: only the bookkeeping differs)
+    miss, _ = S.compare(base, other.tallies, other.counters)
+    fields = {m[0] for m in miss}
+    assert fields and fields <= set(S.EXTRA_FIELDS[kind] + S.DERIVED_FIELDS), (kind, variant, name, fields)
+
+
+def test_the_controls_are_the_eleven_asked_for():
+    assert len({v for vs in S.EXTRA_VARIANTS.values() for v in vs}) == 11
+    assert set(S.EXTRA_VARIANTS["paths"]) < set(S.EXTRA_VARIANTS["bins"]) and len(S.EXTRA_VARIANTS["levels"]) == 4 and len(S.EXTRA_VARIANTS["tracks"]) == 3
