@@ -29,6 +29,7 @@
 #pragma once
 #include <cstddef>
 #include "tally_block.hpp"
+#include "event_flags.hpp"
 #include "tracer.hpp"
 #include "tuning.hpp"
 
@@ -525,6 +526,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   Lds L;
   constexpr bool STORE = has_start_store<Rng>(INTENSITY, GENERAL, GRID, MULTI);   // photons start a wavefront at a time: part B of the event phase
+  constexpr bool FLAGS = STORE && I3RC_EVENT_FLAGS != 0;   // the event phase reads launch facts from DevProblem::eventFlags (event_flags.hpp)
   // Which voxel step (trace_step_lazy): the general kernels' guarded division in a branch of its own, and -- CHAIN -- in the fused ring
   // kernels of a bricked field the specialised step as it was before zero cosines fell out of its minimum: with the minimum these two
   // instantiations ran out of scalar registers by two and kept the wave-uniform `adaptEvent` as a lane mask in a vector register,
@@ -630,6 +632,12 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   const float rcpDeltaX = refined_rcp(P.deltaX), rcpDeltaY = refined_rcp(P.deltaY);
   const float surfaceZ = P.z0 + spacingf(P.z0);
   const bool blackSurface = !Rng::kReplay && !useBDRF && !(P.albedo > kTiny) && !INTENSITY;   // arrival at the surface ends the photon
+
+  // RCP_ONCE (the specialised flux kernels of plain launches): the reciprocal of the inverse table's length, which every scattering
+  // made again -- a conversion, v_rcp_f32 and its refinement on a value the launch fixes --, once per wave, in a scalar register
+  constexpr bool RCP_ONCE = STORE && I3RC_TABLE_RCP_ONCE != 0;
+  float tableRcp = 0.0f;
+  if constexpr (RCP_ONCE) tableRcp = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(refined_rcp((float)P.comp0.nInv))));
 
   WaveCounters wc;
   NestedCounters nested;
@@ -917,6 +925,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
 #ifdef I3RC_PROFILE_PHASES
   unsigned long long profCycles[PH_KINDS] = {}, profCount[PH_KINDS] = {}, profLanes[PH_KINDS] = {};
   unsigned long long profMark = 0;
+  unsigned long long profWrap[4] = {};   // STORE: photon-step phases in which no lane / x only / y only / both axes crossed a side wall (index = axis bits)
   const unsigned long long profStart = __builtin_amdgcn_s_memtime();
 #define PROF_BEGIN() (profMark = __builtin_amdgcn_s_memtime())
 #define PROF_END(kind, lanes) do { profCycles[kind] += __builtin_amdgcn_s_memtime() - profMark; profCount[kind]++; profLanes[kind] += (unsigned long long)(lanes); } while (0)
@@ -1522,7 +1531,11 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
                 if (r.z - L.zE[r.iz - 1] <= 0.0f && r.dz > 0.0f) { r.z = r.z - spacingf(r.z); r.iz = r.iz - 1; }
               }
               // the cell's properties are read only where the domain does not share one value (see DevProblem)
-              const bool needCell = GENERAL || MULTI || !(Pe.uniformSsa >= 0.0f) || Pe.uniformSsa < 1.0f || Pe.uniformPf < 1;
+              // (FLAGS: the same expression, evaluated for the launch on the host -- event_flags.hpp -- and tested as a bit: the float
+              // compares of scalar operands came out as vector compares)
+              bool needCell;
+              if constexpr (FLAGS) needCell = (Pe.eventFlags & kNeedCell) != 0u;
+              else needCell = GENERAL || MULTI || !(Pe.uniformSsa >= 0.0f) || Pe.uniformSsa < 1.0f || Pe.uniformPf < 1;
               if (needCell) cell = cell_index(Pe, r.ix, r.iy, r.iz);
               int comp = 1;                                               // :637-638
               // TWO components (cloud + gas, cloud + aerosol: the usual production domain): what the scattering needs of its cell comes as
@@ -1570,6 +1583,9 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
               }
               // single-scattering albedo and phase-function entry of the cell; a value shared by the whole (one-component)
               // domain comes from the kernel arguments instead of two dependent memory reads
+              // (FLAGS: a launch in which nothing absorbs -- every cell shares an albedo of at least 1 -- skips the albedo and the
+              // absorption behind one uniform branch)
+              if (!FLAGS || (Pe.eventFlags & kNoAbsorption) == 0u) {
               float ssa;
               if ((GENERAL || MULTI) && fromRecord) ssa = ssaRec;
               else if (!GENERAL && !MULTI && Pe.uniformSsa >= 0.0f) ssa = Pe.uniformSsa;
@@ -1593,6 +1609,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
                 }
                 w = w * ssa;
               }
+              }   // (kNoAbsorption)
               int pfi;
               if ((GENERAL || MULTI) && fromRecord) pfi = max(pfiRec, 1);
               else if (!GENERAL && !MULTI && Pe.uniformPf >= 1) pfi = Pe.uniformPf;
@@ -1604,6 +1621,17 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
                 evInfo = EventInfo::pack(comp, Pe.useHybrid && order <= Pe.numOrdersOrig, pfi);
               } else if (INTENSITY)
                 intensity_contribution<GRID>(Pe, L, rng, nested, w, r.x, r.y, r.z, r.ix, r.iy, r.iz, r.dx, r.dy, r.dz, comp, order);
+              if constexpr (FLAGS) {
+                // the roulette's deviate, compares and count only where the launch can play and some lane of this phase does: the block
+                // had been made unconditional -- the conversion of spare() is three float64 instructions -- and masked afterwards, in
+                // every event phase of launches whose weights never leave 1
+                if (Pe.useRR && (Pe.eventFlags & kWeightStaysOne) == 0u && __ballot(w < 0.5f) != 0ull) {
+                  if (w < 0.5f) {
+                    didRoulette = true;
+                    if (rng.spare() >= w / 1.0f) w = 0.0f; else w = 1.0f;
+                  }
+                }
+              } else
               if (Pe.useRR && w < 0.5f) {                                  // :673-680
                 didRoulette = true;
                 if (rng.spare() >= w / 1.0f) w = 0.0f; else w = 1.0f;
@@ -1612,6 +1640,10 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
               else {
                 const CompTables ct = (GENERAL || MULTI) ? load_tables(Pe.comp[comp - 1]) : load_tables(Pe.comp0);
                 float cosS;
+                if constexpr (RCP_ONCE) {
+                  if constexpr (TBL) cosS = scattering_cosine<REPLAY>(rng.first(), (const lds_float *)L.cosTab, ct.nInv, tableRcp);
+                  else cosS = scattering_cosine<REPLAY>(rng.first(), ct.invCos + (size_t)(pfi - 1) * ct.nInv, ct.nInv, tableRcp);
+                } else
                 if constexpr (TBL) cosS = scattering_cosine<REPLAY>(rng.first(), (const lds_float *)L.cosTab, ct.nInv, refined_rcp((float)ct.nInv));
                 else cosS = scattering_cosine<REPLAY>(rng.first(), ct.invCos + (size_t)(pfi - 1) * ct.nInv, ct.nInv, refined_rcp((float)ct.nInv));
                 next_direct(rng, cosS, r.dx, r.dy, r.dz);                 // :684-687
@@ -1684,6 +1716,8 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       // (STORE -- ray tracing, one component: a photon with an interaction due scatters unless part A found it at the top or at the surface)
       if constexpr (STORE) wc.scat += (unsigned)__popcll(scMask & ~(topMask | surfMask));
       else wc.scat += count_lanes(didScatter);
+      if constexpr (FLAGS) { if (Pe.useRR && (Pe.eventFlags & kWeightStaysOne) == 0u) wc.roul += count_lanes(didRoulette); }   // (... and whose weights can fall)
+      else
       if (!STORE || Pe.useRR) wc.roul += count_lanes(didRoulette);     // (STORE: only a launch that plays roulette pays for the count)
       if constexpr (!BATCHED && !STORE) wc.calls += count_lanes(startedTrace);   // (BATCHED, STORE: a batch's / launch's photon traces = its scatterings + surface arrivals + exits + drops)
       PROF_END(PH_EVENT, __popcll(evMask));
@@ -1696,6 +1730,9 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       const unsigned nTracing = count_lanes(tracing);
       wc.steps += nTracing;
       PROF_BEGIN();
+#ifdef I3RC_PROFILE_PHASES
+      unsigned wrapAxes = 0u;
+#endif
       if (tracing) {
         if constexpr (LANE_COUNTS) accSteps++;
         StepResult s;
@@ -1709,13 +1746,20 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, true, CHAIN>(P, L, r, true, &len);
           if (s == STEP_CONTINUE || s == STEP_EXIT) pathLen += (double)len;
         } else
-        s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, false, CHAIN>(P, L, r, true);   // (an arrival is finished by the event phase)
+#ifdef I3RC_PROFILE_PHASES
+        s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, false, CHAIN, STORE && I3RC_WRAP_PER_AXIS>(P, L, r, true, nullptr, STORE ? &wrapAxes : nullptr);
+#else
+        s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, false, CHAIN, STORE && I3RC_WRAP_PER_AXIS>(P, L, r, true);   // (an arrival is finished by the event phase)
+#endif
         if (GENERAL && s == STEP_EXIT) finish_exit(P, r);
         // (an exit through the top, or onto a black surface, ends the photon: such lanes wait for the turnover quorum)
         if (s != STEP_CONTINUE)
           st = s == STEP_DONE ? ST_EVENT : (s == STEP_ERROR ? ST_DROPPED : ((r.iz >= 1 || blackSurface) ? ST_EXIT : ST_EVENT));
       }
       PROF_END(PH_STEP, nTracing);
+#ifdef I3RC_PROFILE_PHASES
+      if constexpr (STORE) profWrap[(__ballot((wrapAxes & 1u) != 0u) != 0ull ? 1 : 0) | (__ballot((wrapAxes & 2u) != 0u) != 0ull ? 2 : 0)]++;
+#endif
     };
     photon_step();
 #if I3RC_PHOTON_STEP_AHEAD < 64
@@ -1730,6 +1774,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       unsafeAtomicAdd(P.tally + P.oVol + 3 * k + 1, (double)profCount[k]);
       unsafeAtomicAdd(P.tally + P.oVol + 3 * k + 2, (double)profLanes[k]);
     }
+    for (int k = 0; k < 4; ++k) unsafeAtomicAdd(P.tally + P.oVol + 3 * PH_KINDS + 1 + k, (double)profWrap[k]);
   }
 #endif
 

@@ -36,6 +36,10 @@ struct DevProblem {
   int nx, ny, nz, ncomp;
   int xyRegular, zRegular;
   float x0, y0, z0, xMax, yMax, zMax, deltaX, deltaY, deltaZ;
+  // launch facts of the event phase as one word of bits (event_flags.hpp: event_flags, filled by make_problem), read by the specialised
+  // flux kernels of plain launches alone.  (It lies in the four bytes that padded the pointers below to their alignment: every other
+  // member stays at its offset, and the kernels that do not read the word compile to what they compiled to without it.)
+  unsigned eventFlags;
   const float *xE, *yE, *zE;          // n+1 each (global; staged to LDS by every workgroup)
   const float *totalExt;              // [nz][ny][nx]
   // The same field in bricks of 32 cells = one 128-byte cache line (grids that do not fit in LDS): a ray's next cell
@@ -91,6 +95,8 @@ struct DevProblem {
   int ldsIntensity;                   // 1: intensityByComponent privatised in LDS ((ncomp+1)*nDir*ncol small)
   int rayQueueCap;                    // radiance runs: events a wave's ray queue holds (power of two; kRecWords floats each)
 };
+
+static_assert(offsetof(DevProblem, eventFlags) + sizeof(unsigned) == offsetof(DevProblem, xE), "DevProblem::eventFlags fills the padding in front of the pointers");
 
 // XCD-aware photon order (fields beyond an XCD's L2): the photons of a launch sorted by the eighth of the domain (in y)
 // they start in -- slabIds holds photon numbers relative to firstPhoton, slab after slab; see slab_count_kernel
@@ -560,8 +566,10 @@ __device__ __forceinline__ float cell_extinction(const PR &P, const Lds &L, int 
 // (CHAIN: the minimum of the three quotients as a chain of `<` selects, which lets a NaN in stx through: for rays whose zero cosines
 // are marked in Ray::slow -- set_direction<true> --, so that the guarded path has replaced every such quotient.  Two instantiations
 // keep it: see photon_kernel.)
-template <int GRID, bool CLEARMAP = false, bool BRANCHY = false, bool SHORT = false, bool LENGTH = false, bool CHAIN = false, class PR>
-__device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L, Ray &r, bool hasTarget, float *length = nullptr) {
+// (AXES: the periodic wrap at the end of the step, x behind its own mask and y behind its own -- see there; the photon step of the
+// specialised flux kernels of plain launches alone asks for it)
+template <int GRID, bool CLEARMAP = false, bool BRANCHY = false, bool SHORT = false, bool LENGTH = false, bool CHAIN = false, bool AXES = false, class PR>
+__device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L, Ray &r, bool hasTarget, float *length = nullptr, unsigned *wrapAxes = nullptr) {
   // the extinction of the current cell is requested first: its latency (LDS, or L2 / HBM for grids that do not fit
   // in LDS) is covered by the three face-distance divisions below
   const float ext = cell_extinction<GRID, CLEARMAP>(P, L, r.ix, r.iy, r.iz);
@@ -651,6 +659,34 @@ __device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L,
   // wrap is skipped by the whole wave when no lane needs it (a uniform branch on a ballot: two scalar instructions)
   // (the wave-uniform test as two compares whose lane masks are OR-ed in scalar registers: a ballot of the four conditions below
   // came out as four compares, a select of 0 / 1 and a fifth compare)
+  // (AXES: about one lane of a wave crosses a side wall in a step, and it crosses ONE of them -- on the step cloud the block above is
+  // entered in four step phases of ten, for 0.5 lanes and one axis each.  Each axis behind its own mask: an index that has left
+  // [1, n] has left it by one, below or above, so the mask is `lo || hi`, the outer select's condition, and one more compare tells
+  // which.  The same operations on the same values as below, the nudge's sign included.)
+  if (wrapAxes)   // (the phase profile's count of the step phases that wrap, by axis: no caller passes it in any other build)
+    *wrapAxes = (__builtin_amdgcn_uicmp((unsigned)(r.ix - 1), (unsigned)P.nx, 35) != 0ull ? 1u : 0u) |
+                (__builtin_amdgcn_uicmp((unsigned)(r.iy - 1), (unsigned)P.ny, 35) != 0ull ? 2u : 0u);
+  if constexpr (AXES) {
+    const bool xOut = (unsigned)(r.ix - 1) >= (unsigned)P.nx, yOut = (unsigned)(r.iy - 1) >= (unsigned)P.ny;
+    const unsigned long long xMask = __ballot(xOut), yMask = __ballot(yOut);
+    // (the nudge's sign is that of x's cell increment -- set_direction makes both from `dx >= 0` --, whose own sign bit serves: +1 / -1
+    // as an integer; Ray::nudge then lives in no register of these kernels' loop)
+    const float sign = __int_as_float(r.cx);
+    if (xMask != 0ull) {
+      const bool xLo = r.ix <= 0;
+      const float sxp = copysignf(two_spacingf(r.x), sign);
+      const float wall = xLo ? P.xMax : P.x0;   // (the wall first, ONE addition: the same sum, and selects instead of exec regions)
+      r.x = xOut ? wall + sxp : r.x;
+      r.ix = xOut ? (xLo ? P.nx : 1) : r.ix;
+    }
+    if (yMask != 0ull) {
+      const bool yLo = r.iy <= 0;
+      const float syp = copysignf(two_spacingf(r.y), sign);
+      const float wall = yLo ? P.yMax : P.y0;
+      r.y = yOut ? wall + syp : r.y;
+      r.iy = yOut ? (yLo ? P.ny : 1) : r.iy;
+    }
+  } else
   if ((__builtin_amdgcn_uicmp((unsigned)(r.ix - 1), (unsigned)P.nx, 35 /* unsigned >= */) |
        __builtin_amdgcn_uicmp((unsigned)(r.iy - 1), (unsigned)P.ny, 35)) != 0ull) {
     const bool xLo = r.ix <= 0, xHi = r.ix >= P.nx + 1, yLo = r.iy <= 0, yHi = r.iy >= P.ny + 1;

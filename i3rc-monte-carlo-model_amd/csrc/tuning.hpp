@@ -65,6 +65,17 @@
 #ifndef I3RC_STORE_TURN_FORCE
 #define I3RC_STORE_TURN_FORCE 12
 #endif
+// round 14, the same six kernels: wave-uniform and single-lane work taken out of their phases, one switch per item so that each can be
+// measured against the tree without it (profiles/r14_uniform_work.txt; 0 = the kernels of round 13)
+#ifndef I3RC_WRAP_PER_AXIS
+#define I3RC_WRAP_PER_AXIS 1   /* the periodic wrap of the photon step: x behind its own mask, y behind its own */
+#endif
+#ifndef I3RC_EVENT_FLAGS
+#define I3RC_EVENT_FLAGS 1     /* DevProblem::eventFlags decides absorption, the cell index and the roulette block for the launch */
+#endif
+#ifndef I3RC_TABLE_RCP_ONCE
+#define I3RC_TABLE_RCP_ONCE 1  /* the inverse table's reciprocal length once per wave, not once per scattering */
+#endif
 #ifndef I3RC_PHOTON_STEP_AHEAD
 #define I3RC_PHOTON_STEP_AHEAD 64   /* off: measured -1.6 % (step cloud) ... +2.8 % (Landsat-36), -3 % on the radar field */
 #endif

@@ -42,4 +42,12 @@ while i < len(args):
         if cnt:
             print(f"  {kind:13s} {cyc / total * 100:5.1f} % of wave time  {cnt / n:9.3f} phases/photon  {cyc / cnt:7.0f} cycles/phase  {lanes / cnt:5.1f} lanes/phase")
     print(f"  {'(loop logic)':13s} {(total - acc) / total * 100:5.1f} %")
+    # the specialised flux kernels of plain launches also count the photon-step phases in which some lane crossed a side wall of the
+    # periodic domain (the wrap block of trace_step_lazy), by the axes that needed it
+    wrap = r["raw"][lay.volumeAbsorption + 3 * len(KINDS) + 1:lay.volumeAbsorption + 3 * len(KINDS) + 5]
+    steps = v[3 * 1 + 1]
+    if steps and wrap.sum():
+        none, xo, yo, both = wrap
+        print(f"  wrap block     entered in {(xo + yo + both) / steps * 100:5.1f} % of photon-step phases: x only {xo / steps * 100:5.1f} %, "
+              f"y only {yo / steps * 100:5.1f} %, both {both / steps * 100:5.1f} %  ({steps / n:.3f} step phases per photon)")
     g.finalize_Integrator()
