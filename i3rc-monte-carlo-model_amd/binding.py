@@ -34,6 +34,7 @@ SYMBOLS = [
     "i3rc_hip_set_path_histogram", "i3rc_hip_get_path_histogram_layout", "i3rc_hip_normalise_path_histogram",
     "i3rc_hip_problem_facts", "i3rc_hip_plan_launch",
     "i3rc_hip_run_batches_diagnostic_moments", "i3rc_hip_get_diagnostic_moments_layout", "i3rc_hip_diagnostic_moments_layout_words",
+    "i3rc_hip_set_path_spectrum", "i3rc_hip_get_path_moments_layout", "i3rc_hip_path_moments_layout_words", "i3rc_hip_run_batches_path_moments",
 ]
 
 
@@ -64,7 +65,7 @@ class MomentsLayout(C.Structure):
 
 # i3rc_diagnostic_moments_layout; without its first word, the words of i3rc_hip_diagnostic_moments_layout_words in order
 DIAGNOSTIC_MOMENTS_NAMES = ["levelFluxUp", "levelFluxDown", "meanLevelFluxUp", "meanLevelFluxDown", "actinicFlux", "meanActinicFlux", "total"]
-EXTRA_KINDS = {"none": 0, "levels": 1, "tracks": 2, "paths": 3, "bins": 4}   # (csrc/tally_block.hpp, ExtraTally; path lengths and the path histogram have no batch moments)
+EXTRA_KINDS = {"none": 0, "levels": 1, "tracks": 2, "paths": 3, "bins": 4}   # (csrc/tally_block.hpp, ExtraTally; path lengths and the path histogram have their batch moments in a layout of their own, path_moments_layout below)
 MAX_PATH_BINS = 1024   # (csrc/tally_block.hpp, kMaxPathBins)
 
 
@@ -79,6 +80,28 @@ def diagnostic_moments_layout(kind, nx, ny, nz, nout=len(DIAGNOSTIC_MOMENTS_NAME
     if load().i3rc_hip_diagnostic_moments_layout_words(int(EXTRA_KINDS.get(kind, kind)), int(nx), int(ny), int(nz), out, int(nout)) != 0:
         raise I3RCError("i3rc_hip_diagnostic_moments_layout_words: bad arguments")
     return dict(zip(DIAGNOSTIC_MOMENTS_NAMES, (int(v) for v in out)))
+
+
+# i3rc_path_moments_layout; without its first three words, the words of i3rc_hip_path_moments_layout_words in order
+PATH_MOMENTS_NAMES = ["pathLengthUp", "pathLengthSquaredUp", "pathLengthDown", "pathLengthSquaredDown",
+                      "meanPathLengthUp", "meanPathLengthSquaredUp", "meanPathLengthDown", "meanPathLengthSquaredDown",
+                      "domainPathUp", "domainPathSquaredUp", "domainPathDown", "domainPathSquaredDown",
+                      "histogramUp", "histogramPathUp", "histogramDown", "histogramPathDown",
+                      "spectrumUpLower", "spectrumUpUpper", "spectrumDownLower", "spectrumDownUpper", "total"]
+MAX_PATH_SPECTRUM = 256   # (csrc/tally_block.hpp, kMaxPathSpectrum)
+
+
+class PathMomentsLayout(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ["kind", "nBins", "nK"] + PATH_MOMENTS_NAMES]
+
+
+def path_moments_layout(kind, nx, ny, nBins=0, nK=0, nout=len(PATH_MOMENTS_NAMES)):
+    """i3rc_hip_path_moments_layout_words: a dict of PATH_MOMENTS_NAMES for a kind ("paths" / "bins", or its number), a grid, the
+    histogram's bins and the spectrum's coefficients.  No device needed."""
+    out = (C.c_int64 * max(int(nout), 1))()
+    if load().i3rc_hip_path_moments_layout_words(int(EXTRA_KINDS.get(kind, kind)), int(nx), int(ny), int(nBins), int(nK), out, int(nout)) != 0:
+        raise I3RCError("i3rc_hip_path_moments_layout_words: bad arguments")
+    return dict(zip(PATH_MOMENTS_NAMES, (int(v) for v in out)))
 
 
 # the words of i3rc_hip_last_plan, in order
@@ -246,6 +269,11 @@ def load():
         L.i3rc_hip_run_batches_diagnostic_moments.argtypes = [H, C.c_uint32, C.c_uint32, C.c_int, C.c_int64, C.POINTER(Source), dp, dp, dp, dp, dp]
         L.i3rc_hip_get_diagnostic_moments_layout.argtypes = [H, C.POINTER(DiagnosticMomentsLayout)]
         L.i3rc_hip_diagnostic_moments_layout_words.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, lp, C.c_int]
+    if hasattr(L, "i3rc_hip_run_batches_path_moments"):   # (likewise)
+        L.i3rc_hip_set_path_spectrum.argtypes = [H, C.c_int, fp]
+        L.i3rc_hip_get_path_moments_layout.argtypes = [H, C.POINTER(PathMomentsLayout)]
+        L.i3rc_hip_path_moments_layout_words.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, lp, C.c_int]
+        L.i3rc_hip_run_batches_path_moments.argtypes = [H, C.c_uint32, C.c_uint32, C.c_int, C.c_int64, C.POINTER(Source), dp, dp, dp, dp, dp]
     L.i3rc_hip_device_count.restype = C.c_int
     L.i3rc_hip_version.restype = C.c_char_p
     _lib = L

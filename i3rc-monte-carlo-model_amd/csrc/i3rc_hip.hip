@@ -139,6 +139,10 @@ struct i3rc_hip_integrator : ProblemFacts {   // (the facts every launch is deci
   DevBuf momSum, momSq, momCounters, momArea, momDz;
   // i3rc_hip_run_batches_diagnostic_moments: the same of the optional diagnostic tally (extra_moments_layout), sized by the kind
   DevBuf momExtraSum, momExtraSq;
+  // i3rc_hip_run_batches_path_moments: the same of the two path tallies (path_moments_layout), and the absorption coefficients of the
+  // spectrum (i3rc_hip_set_path_spectrum) with their device copy
+  DevBuf momPathSum, momPathSq, dPathK;
+  std::vector<float> pathK;
 
   // XCD-aware photon order (launch): the sorted photon numbers and the slab bookkeeping of a launch, per stream (launches
   // on different streams -- i3rc_hip_run_batches -- are in flight together)
@@ -1027,12 +1031,12 @@ const std::vector<KernelEntry> &stream_kernels() {
 // (path lengths have no batch statistics: the diagnostic moments' layout has no slot for them)
 std::string no_path_moments_text() {
   return "path lengths have no batch statistics; the diagnostic moments' layout has no slot for them (switch them off, or call "
-         "i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)";
+         "i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch; i3rc_hip_run_batches_path_moments gathers them in a layout of its own)";
 }
 // (nor has the path histogram)
 std::string no_bin_moments_text() {
   return "the path histogram has no batch statistics; the diagnostic moments' layout has no slot for it (switch it off, or call "
-         "i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)";
+         "i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch; i3rc_hip_run_batches_path_moments gathers them in a layout of its own)";
 }
 int extra_tally_refused(i3rc_hip_integrator *h, const char *who, bool batches) {
   if (h->extra == EXTRA_NONE) return 0;
@@ -1223,6 +1227,16 @@ struct ExtraFields {   // the optional diagnostic tally: the kind's extra block,
   __host__ __device__ __forceinline__ int means() const { return (int)extra_moments_means(kind, V.nz); }
   __device__ __forceinline__ void mean(int q, long long &first, long long &at) const { first = (long long)q * V.nx * V.ny; at = fields() + q; }
 };
+struct PathFields {   // the two path tallies: the kind's block as ExtraFields hands it out, and what is no plain column mean (path_moments_layout)
+  TallyView V;
+  ExtraTally kind;
+  int nBins, nK;
+  const float *edges;        // [nBins + 1], the table bin_add reads (device memory)
+  const float *absorption;   // [nK] (device memory)
+  __device__ __forceinline__ float value(const double *raw, int, long long e) const { return normalised_extra_value(V, raw, kind, extra_block_offset(V.counters), e); }
+  __host__ __device__ __forceinline__ long long fields() const { return path_moments_fields(kind, V.nx, V.ny, nBins); }
+  __host__ __device__ __forceinline__ int quantities() const { return path_moments_quantities(kind, nK); }
+};
 // the sum of v over the 256 threads of a workgroup (what thread 0 returns is used)
 __device__ __forceinline__ double workgroup_sum(double v) {
   __shared__ double part[4];
@@ -1277,6 +1291,50 @@ __global__ void __launch_bounds__(256) moments_means_kernel(Fields F, const doub
     unsafeAtomicAdd(sumSq + at, x * x);
   }
   if (q == 0 && counterTotals && threadIdx.x < I3RC_NUM_COUNTERS) unsafeAtomicAdd(counterTotals + threadIdx.x, raw[F.V.counters + threadIdx.x]);
+}
+
+// the path tallies' other quantities: one workgroup per (batch, quantity), threads striding over the columns or the bins.  Path
+// lengths: q = 0 .. 3 the plain column mean of field q, q = 4 .. 7 the domain's ratio of field q - 4's raw sum to the raw sum of fluxUp
+// (fields 0, 1) or fluxDown (2, 3).  The histogram: q = which * nK + j, which = 0 .. 3 for spectrumUpLower | UpUpper | DownLower |
+// DownUpper at absorption[j], from the raw bins in float64 (path_spectrum_term), per photon of the batch.  One rounding to float32 each.
+__global__ void __launch_bounds__(256) path_quantities_kernel(PathFields F, const double *blocks, long long stride, double *sum, double *sumSq) {
+  const int nq = F.quantities(), b = blockIdx.x / nq, q = blockIdx.x - b * nq;
+  const double *raw = blocks + (size_t)b * stride;
+  const long long block = extra_block_offset(F.V.counters), at = F.fields() + q;
+  double x;
+  if (F.kind == EXTRA_PATHS) {
+    const long long ncol = (long long)F.V.nx * F.V.ny;
+    if (q < 4) {
+      double v = 0.0;
+      for (long long k = threadIdx.x; k < ncol; k += 256) v += (double)F.value(raw, b, q * ncol + k);
+      v = workgroup_sum(v);
+      x = (double)(float)(v / (double)ncol);
+    } else {
+      const double *path = raw + block + (q - 4) * ncol, *flux = raw + (q < 6 ? F.V.fluxUp : F.V.fluxDown);
+      double num = 0.0, den = 0.0;
+      for (long long k = threadIdx.x; k < ncol; k += 256) { num += path[k]; den += flux[k]; }
+      num = workgroup_sum(num);
+      __syncthreads();   // (workgroup_sum's partial sums are read: the second sum writes them again)
+      den = workgroup_sum(den);
+      x = (double)domain_path_ratio(num, den);
+    }
+  } else {
+    const int which = q / F.nK, nb = F.nBins + 1;
+    const double k = (double)F.absorption[q - which * F.nK];
+    const double *weight = raw + block + path_bin_field(which < 2 ? 0 : 2, F.nBins), *path = weight + nb;
+    double v = 0.0;
+    for (int bin = threadIdx.x; bin < nb; bin += 256) {
+      double lower, upper;
+      path_spectrum_term(F.edges, F.nBins, bin, weight[bin], path[bin], k, lower, upper);
+      v += (which & 1) ? upper : lower;
+    }
+    v = workgroup_sum(v);
+    x = (double)(float)(v / raw[F.V.counters + I3RC_CNT_PHOTONS]);
+  }
+  if (threadIdx.x == 0) {
+    unsafeAtomicAdd(sum + at, x);
+    unsafeAtomicAdd(sumSq + at, x * x);
+  }
 }
 
 // Do the batches of a driver's loop -- nBatches of nPhotons each -- share one grid, group by group (see FusedSlot)?  The specialised
@@ -1439,6 +1497,13 @@ int begin_moments(i3rc_hip_integrator *h) {
     if (m->p) HIPCHK(h, hipMemset(m->p, 0, m->bytes));
   return 0;
 }
+// ... and those of the path tally that is switched on (after begin_moments)
+int begin_path_moments(i3rc_hip_integrator *h) {
+  const size_t bytes = (size_t)path_moments_layout(h->extra, h->nx, h->ny, h->pathBins, (int)h->pathK.size()).total * sizeof(double);
+  if (h->momPathSum.bytes != bytes || !h->momPathSum.p) { HIPCHK(h, h->momPathSum.alloc(bytes)); HIPCHK(h, h->momPathSq.alloc(bytes)); }
+  for (DevBuf *m : {&h->momPathSum, &h->momPathSq}) HIPCHK(h, hipMemset(m->p, 0, m->bytes));
+  return 0;
+}
 
 // One moments pass: the fields and means F yields of `count` raw blocks on `stream`, x and x^2 added to `sum` / `sumSq`
 template <class Fields>
@@ -1469,15 +1534,30 @@ int accumulate_moments(i3rc_hip_integrator *h, hipStream_t stream, const double 
   }
   F.excessSums = (const double *)excess.p;
   launch_moments(stream, F, blocks, count, stride, h->momSum, h->momSq, (double *)h->momCounters.p);
-  if (h->extra != EXTRA_NONE) launch_moments(stream, ExtraFields{F.V, h->extra}, blocks, count, stride, h->momExtraSum, h->momExtraSq, nullptr);
+  if (h->extra == EXTRA_LEVELS || h->extra == EXTRA_TRACKS)
+    launch_moments(stream, ExtraFields{F.V, h->extra}, blocks, count, stride, h->momExtraSum, h->momExtraSq, nullptr);
+  if (h->extra == EXTRA_PATHS || h->extra == EXTRA_PATH_BINS) {   // (i3rc_hip_run_batches_path_moments: no other loop runs with these kinds on)
+    // (the edges behind the table's first word, nBins: see i3rc_hip_set_path_histogram)
+    const PathFields P{F.V, h->extra, h->pathBins, (int)h->pathK.size(), h->extra == EXTRA_PATH_BINS ? (const float *)h->dBins.p + 1 : nullptr,
+                       (const float *)h->dPathK.p};
+    // (one slice of the batch range: these kinds come one batch per call, never in a fused group)
+    const long long fieldBlocks = (P.fields() + 255) / 256;
+    hipLaunchKernelGGL(moments_fields_kernel<PathFields>, dim3((unsigned)fieldBlocks, 1u), dim3(256), 0, stream, P, blocks, count, stride,
+                       (double *)h->momPathSum.p, (double *)h->momPathSq.p);
+    if (P.quantities() > 0)
+      hipLaunchKernelGGL(path_quantities_kernel, dim3((unsigned)(count * P.quantities())), dim3(256), 0, stream, P, blocks, stride,
+                         (double *)h->momPathSum.p, (double *)h->momPathSq.p);
+  }
   HIPCHK(h, hipGetLastError());
   return 0;
 }
 
 // ... and the sums of a finished loop to the caller's arrays (counters, and the diagnostic pair: where the caller wants them)
-int download_moments(i3rc_hip_integrator *h, double *sum, double *sumSquares, double *counters, double *extraSum, double *extraSumSquares) {
+int download_moments(i3rc_hip_integrator *h, double *sum, double *sumSquares, double *counters, double *extraSum, double *extraSumSquares,
+                     double *pathSum = nullptr, double *pathSumSquares = nullptr) {
   const std::pair<double *, const DevBuf *> copies[] = {{sum, &h->momSum}, {sumSquares, &h->momSq}, {counters, &h->momCounters},
-                                                         {extraSum, &h->momExtraSum}, {extraSumSquares, &h->momExtraSq}};
+                                                         {extraSum, &h->momExtraSum}, {extraSumSquares, &h->momExtraSq},
+                                                         {pathSum, &h->momPathSum}, {pathSumSquares, &h->momPathSq}};
   for (const auto &c : copies)
     if (c.first) HIPCHK(h, hipMemcpy(c.first, c.second->p, c.second->bytes, hipMemcpyDeviceToHost));
   return 0;
@@ -1600,17 +1680,25 @@ int copy_back_slot(i3rc_hip_integrator *h, i3rc_hip_integrator::PipeSlot &sl, co
 // batch count), then the handle made ready -- the look-ahead called off (i3rc_hip_compute_batch shares the slots), and whatever the
 // caller had in flight on the handle's stream comes first.  diagnostic: the loop is one WITH a diagnostic tally, which must be on and
 // fit a plain launch (the call then names itself in front of the photon count's text too); any other loop has none.
-int begin_batch_loop(i3rc_hip_integrator *h, const std::string &who, bool argsOk, const i3rc_source *src, int64_t nPhotons, bool diagnostic) {
+// paths: the loop is one with a path tally (i3rc_hip_run_batches_path_moments), which must be on likewise.
+int begin_batch_loop(i3rc_hip_integrator *h, const std::string &who, bool argsOk, const i3rc_source *src, int64_t nPhotons, bool diagnostic,
+                     bool paths = false) {
   if (!h) return 1;
   if (!argsOk) return h->fail(who + ": bad arguments");
+  if (paths) {
+    if (h->extra != EXTRA_PATHS && h->extra != EXTRA_PATH_BINS)
+      return h->fail(who + ": no path tally is switched on (i3rc_hip_set_path_lengths or i3rc_hip_set_path_histogram first; "
+                     "i3rc_hip_run_batches_diagnostic_moments serves the other diagnostic tallies)");
+    diagnostic = false;   // (nor does the diagnostic moments' refusal of these kinds apply)
+  }
   if (diagnostic && h->extra == EXTRA_NONE)
     return h->fail(who + ": no diagnostic tally is switched on (i3rc_hip_set_level_fluxes or i3rc_hip_set_actinic_flux first; "
                    "i3rc_hip_run_batches_moments serves a loop without one)");
   if (diagnostic && h->extra == EXTRA_PATHS) return h->fail(who + ": " + no_path_moments_text());
   if (diagnostic && h->extra == EXTRA_PATH_BINS) return h->fail(who + ": " + no_bin_moments_text());
   if (src->kind != 0) return h->fail(who + ": Directional photon streams only (explicit streams differ from batch to batch)");
-  if (nPhotons <= 0) return h->fail((diagnostic ? who + ": " : "") + "setIllumination: must ask for non-negative number of photons.");
-  if (extra_tally_refused(h, who.c_str(), !diagnostic)) return 1;
+  if (nPhotons <= 0) return h->fail((diagnostic || paths ? who + ": " : "") + "setIllumination: must ask for non-negative number of photons.");
+  if (extra_tally_refused(h, who.c_str(), !diagnostic && !paths)) return 1;
   HIPCHK(h, hipSetDevice(h->device));
   drop_lookahead(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1692,8 +1780,9 @@ int i3rc_hip_get_moments_layout(const i3rc_hip_integrator *h, i3rc_moments_layou
 // general kernels -- a diagnostic tally's among them --, long batches) one launch per batch, each batch's block normalised and added up
 // on its slot's stream behind its trace.
 static int run_batches_moments(i3rc_hip_integrator *h, const char *who, uint32_t seed0, uint32_t seed1, int nBatches, int64_t nPhotons,
-                               const i3rc_source *src, double *sum, double *sumSquares, double *counters, double *extraSum, double *extraSumSquares) {
-  if (begin_moments(h)) return 1;
+                               const i3rc_source *src, double *sum, double *sumSquares, double *counters, double *extraSum, double *extraSumSquares,
+                               double *pathSum = nullptr, double *pathSumSquares = nullptr) {
+  if (begin_moments(h) || (pathSum && begin_path_moments(h))) return 1;
   const int rc =
       h->extra == EXTRA_NONE && fuse_loop(h, nPhotons, nBatches)   // (no fused kernel fills a diagnostic block: extra_tally_refused)
           ? run_batches_fused(h, seed0, seed1, nBatches, nPhotons, src, nullptr)
@@ -1703,7 +1792,7 @@ static int run_batches_moments(i3rc_hip_integrator *h, const char *who, uint32_t
                 [&](i3rc_hip_integrator::PipeSlot &sl) {
                   return hipStreamSynchronize(sl.stream) == hipSuccess ? 0 : h->fail(std::string(who) + ": waiting for the batches failed");
                 });
-  return rc || download_moments(h, sum, sumSquares, counters, extraSum, extraSumSquares);
+  return rc || download_moments(h, sum, sumSquares, counters, extraSum, extraSumSquares, pathSum, pathSumSquares);
 }
 
 int i3rc_hip_run_batches_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1, int nBatches, int64_t nPhotons,
@@ -1740,6 +1829,57 @@ int i3rc_hip_run_batches_diagnostic_moments(i3rc_hip_integrator *h, uint32_t see
   static const char who[] = "i3rc_hip_run_batches_diagnostic_moments";
   return begin_batch_loop(h, who, src && sum && sumSquares && extraSum && extraSumSquares && nBatches >= 1, src, nPhotons, true) ||
          run_batches_moments(h, who, seed0, seed1, nBatches, nPhotons, src, sum, sumSquares, counters, extraSum, extraSumSquares);
+}
+
+int i3rc_hip_path_moments_layout_words(int kind, int nx, int ny, int nBins, int nK, int64_t *out, int nout) {
+  if ((kind != EXTRA_PATHS && kind != EXTRA_PATH_BINS) || nx < 1 || ny < 1 || nK < 0 || nK > kMaxPathSpectrum || !out || nout < kPathMomentsWords) return 1;
+  if (kind == EXTRA_PATH_BINS && (nBins < 1 || nBins > kMaxPathBins)) return 1;
+  const PathMomentsLayout L = path_moments_layout((ExtraTally)kind, nx, ny, nBins, nK);
+  const int64_t v[kPathMomentsWords] = {L.pathLengthUp, L.pathLengthSquaredUp, L.pathLengthDown, L.pathLengthSquaredDown,
+                                        L.meanPathLengthUp, L.meanPathLengthSquaredUp, L.meanPathLengthDown, L.meanPathLengthSquaredDown,
+                                        L.domainPathUp, L.domainPathSquaredUp, L.domainPathDown, L.domainPathSquaredDown,
+                                        L.histogramUp, L.histogramPathUp, L.histogramDown, L.histogramPathDown,
+                                        L.spectrumUpLower, L.spectrumUpUpper, L.spectrumDownLower, L.spectrumDownUpper, L.total};
+  for (int k = 0; k < kPathMomentsWords; ++k) out[k] = v[k];
+  return 0;
+}
+
+int i3rc_hip_get_path_moments_layout(const i3rc_hip_integrator *h, i3rc_path_moments_layout *layout) {
+  if (!h || !layout) return 1;
+  if (h->extra != EXTRA_PATHS && h->extra != EXTRA_PATH_BINS)
+    return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_get_path_moments_layout: no path tally is switched on");
+  layout->kind = (int64_t)h->extra;
+  layout->nBins = h->extra == EXTRA_PATH_BINS ? h->pathBins : 0;
+  layout->nK = (int64_t)h->pathK.size();
+  // (the struct's offsets are the words of i3rc_hip_path_moments_layout_words, in order)
+  return i3rc_hip_path_moments_layout_words((int)h->extra, h->nx, h->ny, h->pathBins, (int)h->pathK.size(), &layout->pathLengthUp, kPathMomentsWords);
+}
+
+int i3rc_hip_set_path_spectrum(i3rc_hip_integrator *h, int nK, const float *absorption) {
+  if (!h) return 1;
+  const std::string who = "i3rc_hip_set_path_spectrum: ";
+  if (nK < 0 || nK > kMaxPathSpectrum)
+    return h->fail(who + "0 <= nK <= " + std::to_string(kMaxPathSpectrum) + " required (0 switches the spectrum off); got " + std::to_string(nK));
+  if (nK > 0 && !absorption) return h->fail(who + "null absorption coefficients (nK float32 values)");
+  for (int j = 0; j < nK; ++j) {
+    if (!std::isfinite(absorption[j])) return h->fail(who + "absorption coefficients must be finite; absorption[" + std::to_string(j) + "] is not");
+    if (absorption[j] < 0.0f) return h->fail(who + "absorption coefficients must not be negative; absorption[" + std::to_string(j) + "] is");
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (nK > 0) {
+    const hipError_t e = h->dPathK.upload(absorption, sizeof(float) * (size_t)nK);
+    if (e != hipSuccess) { h->pathK.clear(); return h->hipfail("i3rc_hip_set_path_spectrum: uploading the absorption coefficients", e); }
+  }
+  h->pathK.assign(absorption, absorption + nK);
+  return 0;
+}
+
+// A driver's batch loop with a path tally switched on, its statistics gathered on the device: see include/i3rc_hip.h
+int i3rc_hip_run_batches_path_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1, int nBatches, int64_t nPhotons, const i3rc_source *src,
+                                      double *sum, double *sumSquares, double *counters, double *pathSum, double *pathSumSquares) {
+  static const char who[] = "i3rc_hip_run_batches_path_moments";
+  return begin_batch_loop(h, who, src && sum && sumSquares && pathSum && pathSumSquares && nBatches >= 1, src, nPhotons, false, true) ||
+         run_batches_moments(h, who, seed0, seed1, nBatches, nPhotons, src, sum, sumSquares, counters, nullptr, nullptr, pathSum, pathSumSquares);
 }
 
 // computeRadiativeTransfer for one batch of a driver's loop, looking ahead: see include/i3rc_hip.h
@@ -2109,7 +2249,8 @@ int i3rc_hip_normalise_path_histogram(const i3rc_hip_integrator *h, const double
   const long long block = extra_block_offset(h->layout.counters);
   float *const out[4] = {up, pathUp, down, pathDown};   // (as the block is laid out)
   for (int f = 0; f < 4; ++f)
-    for (int b = 0; out[f] && b <= h->pathBins; ++b) out[f][b] = normalised_path_bin(t, h->layout.counters, block + path_bin_field(f, h->pathBins) + b);
+    for (int b = 0; out[f] && b <= h->pathBins; ++b)
+      out[f][b] = normalised_extra_value(h->view, t, EXTRA_PATH_BINS, block, path_bin_field(f, h->pathBins) + b);
   return 0;
 }
 

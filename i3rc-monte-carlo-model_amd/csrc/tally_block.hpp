@@ -4,6 +4,8 @@
 // Plain C++17: no HIP header is needed (a host compiler alone builds tests/normalise_main.cpp against it).
 #pragma once
 
+#include <cmath>
+
 #include "../../include/i3rc_hip.h"
 
 #if defined(__HIP__) || defined(__HIPCC__)
@@ -144,6 +146,8 @@ I3RC_TALLY_FN float normalised_extra_value(const TallyView &V, const double *raw
     const int kz = (int)(e / ncol);
     return normalised_actinic_flux(V, raw, block, kz, e - kz * ncol);
   }
+  // (the path histogram: e counts through binUp | binPathUp | binDown | binPathDown, per photon of the block and not per column)
+  if (kind == EXTRA_PATH_BINS) return normalised_path_bin(raw, V.counters, block + e);
   return normalised_column_flux(V, raw, block + e, e % ncol);
 }
 
@@ -170,6 +174,69 @@ I3RC_TALLY_FN ExtraMomentsLayout extra_moments_layout(ExtraTally kind, int nx, i
 }
 // ... the fields in front of the means (= extra_block_words: the moments' fields lie as the block's elements do), and the means
 I3RC_TALLY_FN long long extra_moments_means(ExtraTally kind, int nz) { return kind == EXTRA_LEVELS ? 2 * (nz + 1) : (kind == EXTRA_TRACKS ? nz : 0); }
+
+// THE PATH MOMENTS (i3rc_hip_run_batches_path_moments): where the sums over a loop's batches of the two path tallies' results lie in a
+// block of their own, in float64 words; what the kind has not is -1, and total is 0 for any other kind.
+//   EXTRA_PATHS      the four fields [ny][nx] in the block's order, their plain column means (float32(sum over the columns / number of
+//                    columns), as every other mean), then the DOMAIN's path figures: float32(sum over the columns of raw pathUp1 / sum
+//                    over the columns of raw fluxUp) = <L> of the reflected light, the same of pathUp2 = <L^2>, and the two of the
+//                    transmitted light over fluxDown; 0 where the denominator is 0.  The ratio of raw sums is the area-weighted one on every grid.
+//   EXTRA_PATH_BINS  the four fields of nBins + 1 words, then for each of nK absorption coefficients the lower and the upper bound of
+//                    sum_b u_b <exp(-k L)>_b / photons, of the reflected and of the transmitted light (path_spectrum_term below)
+struct PathMomentsLayout {
+  long long pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown;                   // [ny][nx] each
+  long long meanPathLengthUp, meanPathLengthSquaredUp, meanPathLengthDown, meanPathLengthSquaredDown;   // 1 each
+  long long domainPathUp, domainPathSquaredUp, domainPathDown, domainPathSquaredDown;                   // 1 each
+  long long histogramUp, histogramPathUp, histogramDown, histogramPathDown;                             // nBins + 1 each
+  long long spectrumUpLower, spectrumUpUpper, spectrumDownLower, spectrumDownUpper;                     // nK each
+  long long total;
+};
+constexpr int kPathMomentsWords = 21;   // (the words of PathMomentsLayout, in order: i3rc_hip_path_moments_layout_words)
+constexpr int kMaxPathSpectrum = 256;   // (i3rc_hip_set_path_spectrum: 0 <= nK <= 256)
+I3RC_TALLY_FN PathMomentsLayout path_moments_layout(ExtraTally kind, int nx, int ny, int nBins, int nK) {
+  const long long ncol = (long long)nx * ny, nb = (long long)nBins + 1;
+  PathMomentsLayout L = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0};
+  if (kind == EXTRA_PATHS) {
+    L.pathLengthUp = 0; L.pathLengthSquaredUp = ncol; L.pathLengthDown = 2 * ncol; L.pathLengthSquaredDown = 3 * ncol;
+    L.meanPathLengthUp = 4 * ncol; L.meanPathLengthSquaredUp = 4 * ncol + 1; L.meanPathLengthDown = 4 * ncol + 2; L.meanPathLengthSquaredDown = 4 * ncol + 3;
+    L.domainPathUp = 4 * ncol + 4; L.domainPathSquaredUp = 4 * ncol + 5; L.domainPathDown = 4 * ncol + 6; L.domainPathSquaredDown = 4 * ncol + 7;
+    L.total = 4 * ncol + 8;
+  } else if (kind == EXTRA_PATH_BINS) {
+    L.histogramUp = 0; L.histogramPathUp = nb; L.histogramDown = 2 * nb; L.histogramPathDown = 3 * nb;
+    L.spectrumUpLower = 4 * nb; L.spectrumUpUpper = 4 * nb + nK; L.spectrumDownLower = 4 * nb + 2 * (long long)nK; L.spectrumDownUpper = 4 * nb + 3 * (long long)nK;
+    L.total = 4 * nb + 4 * (long long)nK;
+  }
+  return L;
+}
+// ... the fields in front of the other quantities (they lie as the block's elements do), and the number of those quantities
+I3RC_TALLY_FN long long path_moments_fields(ExtraTally kind, int nx, int ny, int nBins) {
+  return kind == EXTRA_PATHS ? 4 * (long long)nx * ny : (kind == EXTRA_PATH_BINS ? path_bin_block_words(nBins) : 0);
+}
+I3RC_TALLY_FN int path_moments_quantities(ExtraTally kind, int nK) { return kind == EXTRA_PATHS ? 8 : (kind == EXTRA_PATH_BINS ? 4 * nK : 0); }
+
+// What bin b (nBins: the overflow bin) of raw weight u and raw path sum p adds to the two bounds of sum_b u_b <exp(-k L)>_b, in
+// float64: the bin's mean path m = p / u, clamped to the bin's float32 edges, gives u exp(-k m) from below (Jensen) and the chord over
+// the bin from above; the overflow bin has no upper edge, so its mean path is only kept above its edge and its upper bound is
+// u exp(-k edge).  An empty bin adds nothing.  Edges: as path_bin's.
+template <class Edges>
+I3RC_TALLY_FN void path_spectrum_term(Edges edges, int nBins, int b, double u, double p, double k, double &lower, double &upper) {
+  lower = 0.0; upper = 0.0;
+  if (!(u > 0.0)) return;
+  const double e0 = (double)edges[b < nBins ? b : nBins];
+  double m = p / u;
+  m = m < e0 ? e0 : m;
+  if (b >= nBins) {
+    lower = u * ::exp(-k * m);
+    upper = u * ::exp(-k * e0);
+    return;
+  }
+  const double e1 = (double)edges[b + 1];
+  m = m > e1 ? e1 : m;
+  lower = u * ::exp(-k * m);
+  upper = u * ((e1 - m) * ::exp(-k * e0) + (m - e0) * ::exp(-k * e1)) / (e1 - e0);
+}
+// ... and a domain path figure from the two raw sums over the columns
+I3RC_TALLY_FN float domain_path_ratio(double pathSum, double fluxSum) { return fluxSum > 0.0 ? (float)(pathSum / fluxSum) : 0.0f; }
 
 // What component j (0: the surface) adds to the column's radiance in direction d beyond its own sum: its share of the excess of
 // limited contributions, in proportion to the field (:327-347).  excessSums[j * nDir + d] = the sum over the columns of component j's

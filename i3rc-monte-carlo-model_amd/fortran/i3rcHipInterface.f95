@@ -37,6 +37,15 @@ module i3rcHipInterface
     integer(c_int64_t) :: kind, levelFluxUp, levelFluxDown, meanLevelFluxUp, meanLevelFluxDown, actinicFlux, meanActinicFlux, total
   end type i3rc_diagnostic_moments_layout
 
+  type, bind(C) :: i3rc_path_moments_layout
+    integer(c_int64_t) :: kind, nBins, nK,                                                                            &
+                          pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown,                   &
+                          meanPathLengthUp, meanPathLengthSquaredUp, meanPathLengthDown, meanPathLengthSquaredDown,   &
+                          domainPathUp, domainPathSquaredUp, domainPathDown, domainPathSquaredDown,                   &
+                          histogramUp, histogramPathUp, histogramDown, histogramPathDown,                             &
+                          spectrumUpLower, spectrumUpUpper, spectrumDownLower, spectrumDownUpper, total
+  end type i3rc_path_moments_layout
+
   integer, parameter :: I3RC_CNT_PHOTONS = 0, I3RC_CNT_DROPPED = 1, I3RC_NUM_COUNTERS = 16
   integer, parameter :: I3RC_MAX_COMPONENTS = 255, I3RC_MAX_DIRECTIONS = 255
 
@@ -173,6 +182,33 @@ module i3rcHipInterface
       real(c_double), intent(out)   :: total(*), totalSquares(*)             ! i3rc_moments_layout%total each
       real(c_double), intent(out)   :: counters(*)                           ! I3RC_NUM_COUNTERS
       real(c_double), intent(out)   :: extraTotal(*), extraTotalSquares(*)   ! i3rc_diagnostic_moments_layout%total each
+      integer(c_int)                :: rc
+    end function
+    function i3rc_hip_set_path_spectrum(h, nK, absorption) bind(C, name = "i3rc_hip_set_path_spectrum") result(rc)
+      import
+      type(c_ptr), value        :: h
+      integer(c_int), value     :: nK                    ! 0 switches the spectrum off (absorption is not read)
+      real(c_float), intent(in) :: absorption(*)
+      integer(c_int)            :: rc
+    end function
+    function i3rc_hip_get_path_moments_layout(h, layout) bind(C, name = "i3rc_hip_get_path_moments_layout") result(rc)
+      import
+      type(c_ptr), value                          :: h
+      type(i3rc_path_moments_layout), intent(out) :: layout
+      integer(c_int)                              :: rc
+    end function
+    function i3rc_hip_run_batches_path_moments(h, seed0, seed1, nBatches, nPhotons, src, total, totalSquares, counters, &
+                                               pathTotal, pathTotalSquares)                                             &
+             bind(C, name = "i3rc_hip_run_batches_path_moments") result(rc)
+      import
+      type(c_ptr), value            :: h
+      integer(c_int32_t), value     :: seed0, seed1          ! batch k is traced with the key (seed0, seed1 + k)
+      integer(c_int), value         :: nBatches
+      integer(c_int64_t), value     :: nPhotons
+      type(i3rc_source), intent(in) :: src
+      real(c_double), intent(out)   :: total(*), totalSquares(*)           ! i3rc_moments_layout%total each
+      real(c_double), intent(out)   :: counters(*)                         ! I3RC_NUM_COUNTERS
+      real(c_double), intent(out)   :: pathTotal(*), pathTotalSquares(*)   ! i3rc_path_moments_layout%total each
       integer(c_int)                :: rc
     end function
     function i3rc_hip_expect_batches(h, seed0, seed1, nBatches, nPhotons, src, accepted) &

@@ -85,8 +85,13 @@ module monteCarloRadiativeTransfer
     integer :: momentBatches = 0
     ! ... and, of the last computeRadiativeTransferDiagnosticMoments, those of the diagnostic tally that was on
     ! (i3rc_diagnostic_moments_layout; diagnosticKind: 1 level fluxes, 2 the actinic flux)
+    ! ... or, of the last computeRadiativeTransferPathMoments, those of the path tally that was on (i3rc_path_moments_layout;
+    ! diagnosticKind: 3 path lengths, 4 the path histogram): a loop has one kind at most, and the sums of either travel alike
     real(c_double), dimension(:), pointer :: diagnosticSums => null(), diagnosticSquares => null()
     integer :: diagnosticKind = 0
+    ! the absorption coefficients at which the path moments bracket the band's fluxes from the histogram
+    ! (specifyParameters(absorptionCoefficients = k); not associated: none)
+    real, dimension(:),          pointer :: absorptionCoefficients => null()
   end type integrator
 
   public :: integrator
@@ -98,6 +103,8 @@ module monteCarloRadiativeTransfer
   public :: computeRadiativeTransferBatchMoments, reportBatchMoments, sumBatchMomentsAcrossProcesses
   ! ... also of the level fluxes or the actinic flux, whichever is switched on
   public :: computeRadiativeTransferDiagnosticMoments, reportDiagnosticMoments
+  ! ... and of the path lengths or the path histogram, with what is derived from them batch by batch
+  public :: computeRadiativeTransferPathMoments, reportPathMoments
 contains
   ! ------------------------------------------------------------------------------------------------
   ! Creation
@@ -179,7 +186,8 @@ contains
                                useHybridPhaseFunsForIntenCalcs, hybridPhaseFunWidth,   &
                                numOrdersOrigPhaseFunIntenCalcs,                        &
                                limitIntensityContributions, maxIntensityContribution,  &
-                               status, computeLevelFluxes, computeActinicFlux, computePathLengths, pathHistogramEdges)
+                               status, computeLevelFluxes, computeActinicFlux, computePathLengths, pathHistogramEdges, &
+                               absorptionCoefficients)
     type(integrator),                   intent(inout) :: thisIntegrator
     real,                     optional, intent(in   ) :: surfaceAlbedo
     type(surfaceDescription), optional, intent(in   ) :: surfaceBDRF
@@ -203,6 +211,9 @@ contains
     ! (likewise: the path-length histogram over these bin edges -- 0 first, strictly ascending --, see reportResults; an array of
     ! size 0 switches it off)
     real, dimension(:),       optional, intent(in   ) :: pathHistogramEdges
+    ! (likewise: the absorption coefficients, each >= 0 in 1 / the grid's length unit, at which computeRadiativeTransferPathMoments
+    ! brackets the band's fluxes from the histogram, see reportPathMoments; an array of size 0 switches that off)
+    real, dimension(:),       optional, intent(in   ) :: absorptionCoefficients
     real(c_float) :: noEdges(1)
     integer :: i, nDir, nx, ny, nc
     real, dimension(:),    pointer :: xs, ys
@@ -399,6 +410,21 @@ contains
         allocate(thisIntegrator%pathHistogramEdges(size(pathHistogramEdges)), thisIntegrator%pathHistogram(size(pathHistogramEdges), 4))
         thisIntegrator%pathHistogramEdges = pathHistogramEdges
         thisIntegrator%pathHistogram = 0.
+      end if
+    end if
+    if(present(absorptionCoefficients)) then
+      if(size(absorptionCoefficients) == 0) then
+        noEdges = 0.
+        if(.not. deviceCall(thisIntegrator, i3rc_hip_set_path_spectrum(thisIntegrator%device, 0, noEdges), &
+                            "specifyParameters", status)) return
+      else
+        if(.not. deviceCall(thisIntegrator, i3rc_hip_set_path_spectrum(thisIntegrator%device, size(absorptionCoefficients), &
+                            absorptionCoefficients), "specifyParameters", status)) return
+      end if
+      if(associated(thisIntegrator%absorptionCoefficients)) deallocate(thisIntegrator%absorptionCoefficients)
+      if(size(absorptionCoefficients) > 0) then
+        allocate(thisIntegrator%absorptionCoefficients(size(absorptionCoefficients)))
+        thisIntegrator%absorptionCoefficients = absorptionCoefficients
       end if
     end if
     call setStateToSuccess(status)
@@ -792,22 +818,24 @@ contains
     real,               intent(in   ) :: solarMu, solarAzimuth
     type(ErrorMessage), intent(inout) :: status
 
-    call computeBatchMoments(thisIntegrator, .false., iseed, firstBatch, numBatches, solarMu, solarAzimuth, numberOfPhotons, status)
+    call computeBatchMoments(thisIntegrator, 0, iseed, firstBatch, numBatches, solarMu, solarAzimuth, numberOfPhotons, status)
   end subroutine computeRadiativeTransferBatchMoments
 
-  ! What stands behind computeRadiativeTransferBatchMoments and (diagnostic) computeRadiativeTransferDiagnosticMoments
-  subroutine computeBatchMoments(thisIntegrator, diagnostic, iseed, firstBatch, numBatches, solarMu, solarAzimuth, &
+  ! What stands behind computeRadiativeTransferBatchMoments (tally 0), computeRadiativeTransferDiagnosticMoments (1: a diagnostic
+  !   tally's moments too) and computeRadiativeTransferPathMoments (2: a path tally's)
+  subroutine computeBatchMoments(thisIntegrator, tally, iseed, firstBatch, numBatches, solarMu, solarAzimuth, &
                                  numberOfPhotons, status)
     type(integrator),   intent(inout) :: thisIntegrator
-    logical,            intent(in   ) :: diagnostic
+    integer,            intent(in   ) :: tally
     integer,            intent(in   ) :: iseed, firstBatch, numBatches, numberOfPhotons
     real,               intent(in   ) :: solarMu, solarAzimuth
     type(ErrorMessage), intent(inout) :: status
     type(i3rc_source)                    :: source
     type(i3rc_moments_layout)            :: layout
     type(i3rc_diagnostic_moments_layout) :: extra
+    type(i3rc_path_moments_layout)       :: paths
     real(c_double)                       :: counters(I3RC_NUM_COUNTERS)
-    logical                              :: done
+    logical                              :: done, diagnostic
 
     if(.not. isReady_Integrator(thisIntegrator)) then
       call setStateToFailure(status, "computeRadiativeTransfer: problem not completely specified.")
@@ -823,9 +851,15 @@ contains
     if(.not. deviceCall(thisIntegrator, i3rc_hip_get_moments_layout(thisIntegrator%device, layout), &
                         "computeRadiativeTransfer", status)) return
     extra%kind = 0
+    diagnostic = tally == 1
     if(diagnostic) then
       if(.not. deviceCall(thisIntegrator, i3rc_hip_get_diagnostic_moments_layout(thisIntegrator%device, extra), &
                           "computeRadiativeTransfer", status)) return
+    end if
+    if(tally == 2) then
+      if(.not. deviceCall(thisIntegrator, i3rc_hip_get_path_moments_layout(thisIntegrator%device, paths), &
+                          "computeRadiativeTransfer", status)) return
+      extra%kind = paths%kind
     end if
     if(associated(thisIntegrator%momentSums)) deallocate(thisIntegrator%momentSums, thisIntegrator%momentSquares)
     if(associated(thisIntegrator%diagnosticSums)) deallocate(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares)
@@ -837,6 +871,13 @@ contains
       done = deviceCall(thisIntegrator, i3rc_hip_run_batches_diagnostic_moments(thisIntegrator%device, int(iseed, c_int32_t), &
                         int(firstBatch, c_int32_t), int(numBatches, c_int), int(numberOfPhotons, c_int64_t), source,         &
                         thisIntegrator%momentSums, thisIntegrator%momentSquares, counters,                                   &
+                        thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares), "computeRadiativeTransfer", status)
+      if(.not. done) deallocate(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares)
+    else if(tally == 2) then
+      allocate(thisIntegrator%diagnosticSums(paths%total), thisIntegrator%diagnosticSquares(paths%total))
+      done = deviceCall(thisIntegrator, i3rc_hip_run_batches_path_moments(thisIntegrator%device, int(iseed, c_int32_t),     &
+                        int(firstBatch, c_int32_t), int(numBatches, c_int), int(numberOfPhotons, c_int64_t), source,       &
+                        thisIntegrator%momentSums, thisIntegrator%momentSquares, counters,                                 &
                         thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares), "computeRadiativeTransfer", status)
       if(.not. done) deallocate(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares)
     else
@@ -913,8 +954,127 @@ contains
     real,               intent(in   ) :: solarMu, solarAzimuth
     type(ErrorMessage), intent(inout) :: status
 
-    call computeBatchMoments(thisIntegrator, .true., iseed, firstBatch, numBatches, solarMu, solarAzimuth, numberOfPhotons, status)
+    call computeBatchMoments(thisIntegrator, 1, iseed, firstBatch, numBatches, solarMu, solarAzimuth, numberOfPhotons, status)
   end subroutine computeRadiativeTransferDiagnosticMoments
+
+  ! ------------------------------------------------------------------------------------------------
+  ! Not in the reference: computeRadiativeTransferBatchMoments for a loop WITH A PATH TALLY switched on (specifyParameters:
+  !   computePathLengths or pathHistogramEdges; i3rc_hip_run_batches_path_moments).  Every batch is one launch of its own -- the
+  !   photons computeRadiativeTransfer traces for seed (/ iseed, batch /) with the tally on --, and its path lengths (or its
+  !   histogram) are normalised and added up on the device beside everything else, together with what users derive from them and
+  !   what is not linear in the tallies, so that its standard error has to be formed batch by batch: the domain's mean path <L> and
+  !   <L^2> of the reflected and the transmitted light, or, at every coefficient of specifyParameters(absorptionCoefficients = k),
+  !   the lower and the upper bound of the band's reflected and transmitted flux.  reportBatchMoments serves the ordinary moments
+  !   of such a loop as ever, reportPathMoments these -- last dimension 1 = sum of x, 2 = sum of x**2 over the batches.
+  ! ------------------------------------------------------------------------------------------------
+  subroutine computeRadiativeTransferPathMoments(thisIntegrator, iseed, firstBatch, numBatches, solarMu, solarAzimuth, &
+                                                 numberOfPhotons, status)
+    type(integrator),   intent(inout) :: thisIntegrator
+    integer,            intent(in   ) :: iseed, firstBatch, numBatches, numberOfPhotons
+    real,               intent(in   ) :: solarMu, solarAzimuth
+    type(ErrorMessage), intent(inout) :: status
+
+    call computeBatchMoments(thisIntegrator, 2, iseed, firstBatch, numBatches, solarMu, solarAzimuth, numberOfPhotons, status)
+  end subroutine computeRadiativeTransferPathMoments
+
+  subroutine reportPathMoments(thisIntegrator, pathLengthUpStats, pathLengthSquaredUpStats, pathLengthDownStats,             &
+                               pathLengthSquaredDownStats, meanPathLengthUpStats, meanPathLengthSquaredUpStats,              &
+                               meanPathLengthDownStats, meanPathLengthSquaredDownStats, domainPathUpStats,                   &
+                               domainPathSquaredUpStats, domainPathDownStats, domainPathSquaredDownStats,                    &
+                               pathHistogramUpStats, pathHistogramPathUpStats, pathHistogramDownStats,                       &
+                               pathHistogramPathDownStats, spectrumUpLowerStats, spectrumUpUpperStats,                       &
+                               spectrumDownLowerStats, spectrumDownUpperStats, status)
+    type(integrator),                   intent(in   ) :: thisIntegrator
+    real, dimension(:, :, :), optional, intent(  out) :: pathLengthUpStats, pathLengthSquaredUpStats, &
+                                                         pathLengthDownStats, pathLengthSquaredDownStats           ! (nx, ny, 2)
+    real, dimension(2),       optional, intent(  out) :: meanPathLengthUpStats, meanPathLengthSquaredUpStats, &
+                                                         meanPathLengthDownStats, meanPathLengthSquaredDownStats
+    real, dimension(2),       optional, intent(  out) :: domainPathUpStats, domainPathSquaredUpStats, &
+                                                         domainPathDownStats, domainPathSquaredDownStats
+    real, dimension(:, :),    optional, intent(  out) :: pathHistogramUpStats, pathHistogramPathUpStats, &
+                                                         pathHistogramDownStats, pathHistogramPathDownStats        ! (nBins + 1, 2)
+    real, dimension(:, :),    optional, intent(  out) :: spectrumUpLowerStats, spectrumUpUpperStats, &
+                                                         spectrumDownLowerStats, spectrumDownUpperStats            ! (nK, 2)
+    type(ErrorMessage),                 intent(inout) :: status
+    type(i3rc_path_moments_layout) :: layout
+    integer :: nx, ny
+
+    if(.not. associated(thisIntegrator%diagnosticSums) .or. thisIntegrator%diagnosticKind < 3) then
+      call setStateToFailure(status, "reportPathMoments: no path moments have been computed.")
+      return
+    end if
+    ! (a path tally that has been switched off since is what the library says here; another kind, bins or coefficients below)
+    layout%kind = 0; layout%total = -1
+    if(i3rc_hip_get_path_moments_layout(thisIntegrator%device, layout) /= 0) layout%kind = 0
+    if(layout%kind /= thisIntegrator%diagnosticKind .or. layout%total /= size(thisIntegrator%diagnosticSums)) then
+      call setStateToFailure(status, "reportPathMoments: the problem has changed since the moments were computed.")
+      return
+    end if
+    nx = size(thisIntegrator%fluxUp, 1); ny = size(thisIntegrator%fluxUp, 2)
+    if(present(pathLengthUpStats))          call fieldMoments(layout%pathLengthUp,          pathLengthUpStats,          "pathLengthUpStats")
+    if(present(pathLengthSquaredUpStats))   call fieldMoments(layout%pathLengthSquaredUp,   pathLengthSquaredUpStats,   "pathLengthSquaredUpStats")
+    if(present(pathLengthDownStats))        call fieldMoments(layout%pathLengthDown,        pathLengthDownStats,        "pathLengthDownStats")
+    if(present(pathLengthSquaredDownStats)) call fieldMoments(layout%pathLengthSquaredDown, pathLengthSquaredDownStats, "pathLengthSquaredDownStats")
+    if(present(meanPathLengthUpStats))          call oneMoment(layout%meanPathLengthUp,          meanPathLengthUpStats)
+    if(present(meanPathLengthSquaredUpStats))   call oneMoment(layout%meanPathLengthSquaredUp,   meanPathLengthSquaredUpStats)
+    if(present(meanPathLengthDownStats))        call oneMoment(layout%meanPathLengthDown,        meanPathLengthDownStats)
+    if(present(meanPathLengthSquaredDownStats)) call oneMoment(layout%meanPathLengthSquaredDown, meanPathLengthSquaredDownStats)
+    if(present(domainPathUpStats))          call oneMoment(layout%domainPathUp,          domainPathUpStats)
+    if(present(domainPathSquaredUpStats))   call oneMoment(layout%domainPathSquaredUp,   domainPathSquaredUpStats)
+    if(present(domainPathDownStats))        call oneMoment(layout%domainPathDown,        domainPathDownStats)
+    if(present(domainPathSquaredDownStats)) call oneMoment(layout%domainPathSquaredDown, domainPathSquaredDownStats)
+    if(present(pathHistogramUpStats))       call rowMoments(layout%histogramUp,       int(layout%nBins) + 1, pathHistogramUpStats,       "pathHistogramUpStats",       "path histogram")
+    if(present(pathHistogramPathUpStats))   call rowMoments(layout%histogramPathUp,   int(layout%nBins) + 1, pathHistogramPathUpStats,   "pathHistogramPathUpStats",   "path histogram")
+    if(present(pathHistogramDownStats))     call rowMoments(layout%histogramDown,     int(layout%nBins) + 1, pathHistogramDownStats,     "pathHistogramDownStats",     "path histogram")
+    if(present(pathHistogramPathDownStats)) call rowMoments(layout%histogramPathDown, int(layout%nBins) + 1, pathHistogramPathDownStats, "pathHistogramPathDownStats", "path histogram")
+    if(present(spectrumUpLowerStats))   call rowMoments(layout%spectrumUpLower,   int(layout%nK), spectrumUpLowerStats,   "spectrumUpLowerStats",   "path histogram")
+    if(present(spectrumUpUpperStats))   call rowMoments(layout%spectrumUpUpper,   int(layout%nK), spectrumUpUpperStats,   "spectrumUpUpperStats",   "path histogram")
+    if(present(spectrumDownLowerStats)) call rowMoments(layout%spectrumDownLower, int(layout%nK), spectrumDownLowerStats, "spectrumDownLowerStats", "path histogram")
+    if(present(spectrumDownUpperStats)) call rowMoments(layout%spectrumDownUpper, int(layout%nK), spectrumDownUpperStats, "spectrumDownUpperStats", "path histogram")
+    if(.not. stateIsFailure(status)) call setStateToSuccess(status)
+  contains
+    ! (a kind that is not the loop's: its offset is -1)
+    subroutine fieldMoments(at, to, name)
+      integer(c_int64_t),       intent(in ) :: at
+      real, dimension(:, :, :), intent(out) :: to
+      character(len = *),       intent(in ) :: name
+      integer :: i, j
+      if(at < 0) then
+        call setStateToFailure(status, "reportPathMoments: path length information not available")
+      else if(any(shape(to) /= (/ nx, ny, 2 /))) then
+        call setStateToFailure(status, "reportPathMoments: " // name // " array is the wrong size")
+      else
+        do j = 1, ny
+          do i = 1, nx
+            to(i, j, 1) = real(thisIntegrator%diagnosticSums   (at + i + nx * (j - 1)))
+            to(i, j, 2) = real(thisIntegrator%diagnosticSquares(at + i + nx * (j - 1)))
+          end do
+        end do
+      end if
+    end subroutine fieldMoments
+    subroutine oneMoment(at, to)
+      integer(c_int64_t), intent(in ) :: at
+      real, dimension(2), intent(out) :: to
+      if(at < 0) then
+        call setStateToFailure(status, "reportPathMoments: path length information not available")
+      else
+        to = (/ real(thisIntegrator%diagnosticSums(at + 1)), real(thisIntegrator%diagnosticSquares(at + 1)) /)
+      end if
+    end subroutine oneMoment
+    subroutine rowMoments(at, n, to, name, what)
+      integer(c_int64_t),    intent(in ) :: at
+      integer,               intent(in ) :: n
+      real, dimension(:, :), intent(out) :: to
+      character(len = *),    intent(in ) :: name, what
+      if(at < 0) then
+        call setStateToFailure(status, "reportPathMoments: " // what // " information not available")
+      else if(any(shape(to) /= (/ n, 2 /))) then
+        call setStateToFailure(status, "reportPathMoments: " // name // " array is the wrong size")
+      else
+        call copyMeanMoments(thisIntegrator%diagnosticSums, thisIntegrator%diagnosticSquares, at, to)
+      end if
+    end subroutine rowMoments
+  end subroutine reportPathMoments
 
   ! What reportBatchMoments and reportDiagnosticMoments hand out of a pair of moment blocks (sums and sums of squares over the batches),
   !   from the 0-based word `at` on: a field's words, x fastest, into to(:, :, :, 1:2) -- element by element: a cloud field's volume is
@@ -958,7 +1118,7 @@ contains
     type(i3rc_diagnostic_moments_layout) :: layout
     integer :: nx, ny, nz
 
-    if(.not. associated(thisIntegrator%diagnosticSums)) then
+    if(.not. associated(thisIntegrator%diagnosticSums) .or. thisIntegrator%diagnosticKind > 2) then
       call setStateToFailure(status, "reportDiagnosticMoments: no diagnostic moments have been computed.")
       return
     end if
@@ -1325,6 +1485,13 @@ contains
         copy%pathHistogram = original%pathHistogram
       end if
     end if
+    if(associated(original%absorptionCoefficients)) then
+      if(deviceCall(copy, i3rc_hip_set_path_spectrum(copy%device, size(original%absorptionCoefficients), original%absorptionCoefficients), &
+                    "copy_Integrator", status)) then
+        allocate(copy%absorptionCoefficients(size(original%absorptionCoefficients)))
+        copy%absorptionCoefficients = original%absorptionCoefficients
+      end if
+    end if
   end function copy_Integrator
 
   subroutine finalize_Integrator(thisIntegrator)
@@ -1362,6 +1529,7 @@ contains
     if(associated(thisIntegrator%actinicFlux))          deallocate(thisIntegrator%actinicFlux)
     if(associated(thisIntegrator%pathLengths))          deallocate(thisIntegrator%pathLengths)
     if(associated(thisIntegrator%pathHistogram))        deallocate(thisIntegrator%pathHistogram, thisIntegrator%pathHistogramEdges)
+    if(associated(thisIntegrator%absorptionCoefficients)) deallocate(thisIntegrator%absorptionCoefficients)
     thisIntegrator%computeLevelFluxes = .false.; thisIntegrator%computeActinicFlux = .false.; thisIntegrator%computePathLengths = .false.
     thisIntegrator%readyToCompute = .false.; thisIntegrator%computeIntensity = .false.
     thisIntegrator%useSurfaceBDRF = .false.

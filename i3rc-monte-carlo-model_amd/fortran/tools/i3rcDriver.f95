@@ -10,6 +10,12 @@
 ! upward and downward flux through every layer interface, or every cell's actinic flux by photon track length -- and the run reports
 ! it with the standard error over the batches like everything else: the domain means per level (layer) in outputLevelFluxFile /
 ! outputActinicFluxFile of /fileNames/, the fields in the netCDF file.  Both off (the default): the driver's files are what they were.
+! Likewise computePathLengths, or pathHistogramEdges (0 first, ascending; unset: off) with absorptionCoefficients (>= 0; unset: none),
+! switch one of the two path tallies on: the path-length moments of the reflected and the transmitted light with the domain's mean path
+! <L> and <L^2>, or the path histogram with the two bounds of the band's fluxes at every coefficient -- quantities that are not linear
+! in the tallies, whose standard errors are therefore formed from batch values gathered on the device.  outputPathLengthFile /
+! outputPathHistogramFile of /fileNames/ take the domain's figures, the netCDF file the fields.  <L> and <L^2> are lengths: solarFlux
+! does not scale them.
 !   i3rcDriver namelistFile
 program i3rcDriver
   use ErrorMessages,               only: ErrorMessage, stateIsFailure
@@ -22,11 +28,12 @@ program i3rcDriver
                                          finalize_Integrator, computeRadiativeTransfer, reportResults,           &
                                          computeRadiativeTransferBatches, selectBatchResults, &
                                          computeRadiativeTransferBatchMoments, reportBatchMoments, sumBatchMomentsAcrossProcesses, &
-                                         computeRadiativeTransferDiagnosticMoments, reportDiagnosticMoments
+                                         computeRadiativeTransferDiagnosticMoments, reportDiagnosticMoments, &
+                                         computeRadiativeTransferPathMoments, reportPathMoments
   use UserInterface,               only: printStatus, getOneArgument
   implicit none
 
-  integer, parameter :: maxDirections = 20
+  integer, parameter :: maxDirections = 20, maxPathEdges = 1025, maxAbsorption = 256
   ! -- namelist variables (names and defaults as in the reference driver :58-87)
   real    :: solarFlux = 1., surfaceAlbedo = 0., solarMu = 1., solarAzimuth = 0.
   real    :: intensityMus(maxDirections) = 0., intensityPhis(maxDirections) = 0.
@@ -41,23 +48,29 @@ program i3rcDriver
   real    :: maxIntensityContribution = 77.
   logical :: reportVolumeAbsorption = .false., reportAbsorptionProfile = .false.
   logical :: computeLevelFluxes = .false., computeActinicFlux = .false.   ! (not in the reference: the shell's diagnostic tallies)
+  ! (likewise: the shell's path tallies; a negative value ends either list)
+  logical :: computePathLengths = .false.
+  real    :: pathHistogramEdges(maxPathEdges) = -1., absorptionCoefficients(maxAbsorption) = -1.
   character(len = 256) :: domainFileName = "", outputFluxFile = "", outputRadFile = "", outputAbsProfFile = "", &
-                          outputAbsVolumeFile = "", outputNetcdfFile = "", outputLevelFluxFile = "", outputActinicFluxFile = ""
+                          outputAbsVolumeFile = "", outputNetcdfFile = "", outputLevelFluxFile = "", outputActinicFluxFile = "", &
+                          outputPathLengthFile = "", outputPathHistogramFile = ""
   namelist /radiativeTransfer/ solarFlux, solarMu, solarAzimuth, surfaceAlbedo, intensityMus, intensityPhis
   namelist /monteCarlo/ numPhotonsPerBatch, numBatches, iseed, nPhaseIntervals
   namelist /algorithms/ useRayTracing, useRussianRoulette, useHybridPhaseFunsForIntenCalcs, hybridPhaseFunWidth, &
                         numOrdersOrigPhaseFunIntenCalcs, useRussianRouletteForIntensity, zetaMin,               &
-                        limitIntensityContributions, maxIntensityContribution, computeLevelFluxes, computeActinicFlux
+                        limitIntensityContributions, maxIntensityContribution, computeLevelFluxes, computeActinicFlux, &
+                        computePathLengths, pathHistogramEdges, absorptionCoefficients
   namelist /output/ reportVolumeAbsorption, reportAbsorptionProfile
   namelist /fileNames/ domainFileName, outputRadFile, outputFluxFile, outputAbsProfFile, outputAbsVolumeFile, outputNetcdfFile, &
-                       outputLevelFluxFile, outputActinicFluxFile
+                       outputLevelFluxFile, outputActinicFluxFile, outputPathLengthFile, outputPathHistogramFile
 
   character(len = 256) :: namelistFile
   integer :: nx, ny, nz, nDir, numProcs, thisProc, perProc, batch, firstBatch
   integer :: inFlight, groupSize, groupStart, inGroup, deviceMoments
   real    :: tallyWords
   character(len = 32) :: envText
-  logical :: wantRadiance, momentsAreGlobal = .false.
+  integer :: nEdges, nK, f
+  logical :: wantRadiance, wantPaths, momentsAreGlobal = .false.
   real    :: t0, t1, t2, cpuSetup
   integer :: nc, v, rc                       ! netCDF result file: file id, variable id, return code
   real, allocatable :: xEdges(:), yEdges(:), zEdges(:)
@@ -68,6 +81,10 @@ program i3rcDriver
   ! ... of the diagnostic tally that is switched on: the fields, and the domain means per level (layer)
   real, allocatable :: mLevelUp(:, :, :, :), mLevelDown(:, :, :, :), mMeanLevelUp(:, :), mMeanLevelDown(:, :), &
                        mActinic(:, :, :, :), mMeanActinic(:, :)
+  ! ... of the path tally that is switched on: (:, :, :, f) the four fields with (:, f) their column means and the domain's <L>, <L^2>
+  ! of the reflected and the transmitted light; or (:, :, f) the histogram's four fields and the spectrum's four bounds
+  real, allocatable :: mPath(:, :, :, :), mBins(:, :, :), mSpectrum(:, :, :)
+  real :: mMeanPath(2, 4), mDomainPath(2, 4)
   type(domain)               :: cloud
   type(ErrorMessage)         :: status
   type(randomNumberSequence) :: randoms
@@ -89,6 +106,19 @@ program i3rcDriver
   if(.not. wantRadiance) outputRadFile = ""
   if(.not. computeLevelFluxes) outputLevelFluxFile = ""
   if(.not. computeActinicFlux) outputActinicFluxFile = ""
+  nEdges = 0
+  do while(nEdges < maxPathEdges)
+    if(pathHistogramEdges(nEdges + 1) < 0.) exit
+    nEdges = nEdges + 1
+  end do
+  nK = 0
+  do while(nK < maxAbsorption)
+    if(absorptionCoefficients(nK + 1) < 0.) exit
+    nK = nK + 1
+  end do
+  wantPaths = computePathLengths .or. nEdges > 0
+  if(.not. computePathLengths) outputPathLengthFile = ""
+  if(nEdges == 0) outputPathHistogramFile = ""
 
   ! -- problem set-up
   call read_Domain(domainFileName, cloud, status);                                call printStatus(status)
@@ -119,6 +149,17 @@ program i3rcDriver
   end if
   if(computeActinicFlux) then
     call specifyParameters(mc, computeActinicFlux = .true., status = status);     call printStatus(status)
+  end if
+  if(computePathLengths) then
+    call specifyParameters(mc, computePathLengths = .true., status = status);     call printStatus(status)
+  end if
+  if(nEdges > 0) then
+    call specifyParameters(mc, pathHistogramEdges = pathHistogramEdges(:nEdges), status = status)
+    call printStatus(status)
+  end if
+  if(nK > 0) then
+    call specifyParameters(mc, absorptionCoefficients = absorptionCoefficients(:nK), status = status)
+    call printStatus(status)
   end if
   if(.not. isReady_Integrator(mc)) stop "Integrator is not ready."
 
@@ -162,8 +203,11 @@ program i3rcDriver
   deviceMoments = 1
   call get_environment_variable("I3RC_DRIVER_MOMENTS", envText, status = rc)
   if(rc == 0 .and. len_trim(envText) > 0) read(envText, *, iostat = rc) deviceMoments
-  if(computeLevelFluxes .or. computeActinicFlux .or. (deviceMoments /= 0 .and. inFlight /= 1)) then
-    if(computeLevelFluxes .or. computeActinicFlux) then
+  if(computeLevelFluxes .or. computeActinicFlux .or. wantPaths .or. (deviceMoments /= 0 .and. inFlight /= 1)) then
+    if(wantPaths) then
+      ! (likewise a path tally's: what is derived from it batch by batch cannot be formed afterwards)
+      call computeRadiativeTransferPathMoments(mc, iseed, firstBatch, perProc, solarMu, solarAzimuth, numPhotonsPerBatch, status)
+    else if(computeLevelFluxes .or. computeActinicFlux) then
       ! (a diagnostic's statistics are gathered on the device or not at all: one launch per batch, the batches overlapping)
       call computeRadiativeTransferDiagnosticMoments(mc, iseed, firstBatch, perProc, solarMu, solarAzimuth, numPhotonsPerBatch, status)
     else
@@ -193,6 +237,27 @@ program i3rcDriver
       allocate(mActinic(nx, ny, nz, 2), mMeanActinic(nz, 2))
       call reportDiagnosticMoments(mc, actinicFluxStats = mActinic, meanActinicFluxStats = mMeanActinic, status = status)
       call printStatus(status)
+    end if
+    if(computePathLengths) then
+      allocate(mPath(nx, ny, 2, 4))
+      call reportPathMoments(mc, pathLengthUpStats = mPath(:, :, :, 1), pathLengthSquaredUpStats = mPath(:, :, :, 2),           &
+                             pathLengthDownStats = mPath(:, :, :, 3), pathLengthSquaredDownStats = mPath(:, :, :, 4),         &
+                             meanPathLengthUpStats = mMeanPath(:, 1), meanPathLengthSquaredUpStats = mMeanPath(:, 2),         &
+                             meanPathLengthDownStats = mMeanPath(:, 3), meanPathLengthSquaredDownStats = mMeanPath(:, 4),     &
+                             domainPathUpStats = mDomainPath(:, 1), domainPathSquaredUpStats = mDomainPath(:, 2),             &
+                             domainPathDownStats = mDomainPath(:, 3), domainPathSquaredDownStats = mDomainPath(:, 4), status = status)
+      call printStatus(status)
+    end if
+    if(nEdges > 0) then
+      allocate(mBins(nEdges, 2, 4), mSpectrum(nK, 2, 4))
+      call reportPathMoments(mc, pathHistogramUpStats = mBins(:, :, 1), pathHistogramPathUpStats = mBins(:, :, 2),              &
+                             pathHistogramDownStats = mBins(:, :, 3), pathHistogramPathDownStats = mBins(:, :, 4), status = status)
+      call printStatus(status)
+      if(nK > 0) then
+        call reportPathMoments(mc, spectrumUpLowerStats = mSpectrum(:, :, 1), spectrumUpUpperStats = mSpectrum(:, :, 2),        &
+                               spectrumDownLowerStats = mSpectrum(:, :, 3), spectrumDownUpperStats = mSpectrum(:, :, 4), status = status)
+        call printStatus(status)
+      end if
     end if
     perProc = 0   ! (the loop below has nothing left to do)
   end if
@@ -252,7 +317,20 @@ program i3rcDriver
     call reduce2(mMeanActinic); call reduce4(mActinic)
   end if
 
+  do f = 1, 4
+    if(computePathLengths) then
+      call reduce3(mPath(:, :, :, f)); call momentsToStatistics(mMeanPath(:, f)); call lengthStatistics(mDomainPath(:, f))
+    end if
+    if(nEdges > 0) then
+      call reduce2(mBins(:, :, f))
+      if(nK > 0) call reduce2(mSpectrum(:, :, f))
+    end if
+  end do
+
   if(MasterProc) then
+    if(len_trim(outputPathLengthFile) > 0) call writePathLengthFile
+    if(len_trim(outputPathHistogramFile) > 0) call writePathHistogramFile
+    if(len_trim(outputPathLengthFile) + len_trim(outputPathHistogramFile) > 0) print *, "Wrote ASCII figures of the path tally"
     if(len_trim(outputLevelFluxFile) > 0) call writeLevelFluxFile
     if(len_trim(outputActinicFluxFile) > 0) call writeActinicFluxFile
     if(len_trim(outputLevelFluxFile) + len_trim(outputActinicFluxFile) > 0) print *, "Wrote ASCII profiles of the diagnostic tally"
@@ -280,6 +358,13 @@ contains
     m = solarFlux * m / numBatches
     m(2) = sqrt(max(0., m(2) - m(1)**2) / (numBatches - 1))
   end subroutine momentsToStatistics
+
+  ! (a length, or its square: no flux scales it)
+  subroutine lengthStatistics(m)
+    real, intent(inout) :: m(2)
+    m = m / numBatches
+    m(2) = sqrt(max(0., m(2) - m(1)**2) / (numBatches - 1))
+  end subroutine lengthStatistics
 
   subroutine reduce3(m)
     real, intent(inout) :: m(:, :, :)
@@ -375,6 +460,37 @@ contains
     close(12)
   end subroutine writeActinicFluxFile
 
+  ! the domain's path figures: the mean path and the mean squared path of the reflected and of the transmitted light, then the domain
+  ! means of the four path-length fields (length x flux: pathLengthUp / fluxUp is a column's mean path)
+  subroutine writePathLengthFile
+    open(unit = 12, file = trim(outputPathLengthFile), status = "unknown")
+    call writeHeader(12, "Path Lengths", "Domain Path Lengths")
+    write(12, '(A)') '!  Mean and StdErr of: <L>_Up  <L^2>_Up  <L>_Down  <L^2>_Down  (reflected / transmitted light; length, length^2)'
+    write(12, '(8(1X,ES14.6))') mDomainPath
+    write(12, '(A)') '!  Mean and StdErr of the domain means of: pathLengthUp  pathLengthSquaredUp  pathLengthDown  pathLengthSquaredDown'
+    write(12, '(8(1X,ES14.6))') mMeanPath
+    close(12)
+  end subroutine writePathLengthFile
+
+  ! one row per bin of the path length (the overflow bin last: its upper edge is printed as -1), then one row per absorption coefficient
+  subroutine writePathHistogramFile
+    integer :: b, j
+    open(unit = 12, file = trim(outputPathHistogramFile), status = "unknown")
+    call writeHeader(12, "Path Histogram", "Domain Path Histogram")
+    write(12, '(A)') '!  Bin: lower edge, upper edge; then Mean and StdErr of: Flux_Up  Flux_Up x path  Flux_Down  Flux_Down x path'
+    do b = 1, nEdges
+      write(12, '(2(1X,ES14.6),2(1X,2(1X,F9.4),2(1X,ES14.6)))') pathHistogramEdges(b), merge(pathHistogramEdges(min(b + 1, nEdges)), -1., b < nEdges), &
+                                                               mBins(b, :, 1), mBins(b, :, 2), mBins(b, :, 3), mBins(b, :, 4)
+    end do
+    if(nK > 0) then
+      write(12, '(A)') '!  Absorption coefficient; then Mean and StdErr of the band''s: Flux_Up lower bound, upper bound  Flux_Down lower bound, upper bound'
+      do j = 1, nK
+        write(12, '(1X,ES14.6,4(1X,2(1X,F9.4)))') absorptionCoefficients(j), mSpectrum(j, :, 1), mSpectrum(j, :, 2), mSpectrum(j, :, 3), mSpectrum(j, :, 4)
+      end do
+    end if
+    close(12)
+  end subroutine writePathHistogramFile
+
   subroutine writeVolumeFile
     integer :: i, j, k
     open(unit = 12, file = trim(outputAbsVolumeFile), status = "unknown")
@@ -413,7 +529,7 @@ contains
   ! names as the reference driver's writeResults_netcdf (:609-854), so that scripts reading its files read these.
   subroutine writeNetcdfFile
     use netcdf
-    integer :: xDim, yDim, zDim, dirDim, levelDim
+    integer :: xDim, yDim, zDim, dirDim, levelDim, binDim, absorptionDim
     logical :: wantZ
 
     wantZ = reportAbsorptionProfile .or. reportVolumeAbsorption .or. computeActinicFlux
@@ -471,6 +587,22 @@ contains
       ! (the track-length estimator's variance diverges in cells without extinction)
       rc = nf90_put_att(nc, v, "note", "not to be trusted in cells without extinction")
     end if
+    if(computePathLengths) then
+      call definePair("pathLengthUp", (/ xDim, yDim /));   call definePair("pathLengthSquaredUp", (/ xDim, yDim /))
+      call definePair("pathLengthDown", (/ xDim, yDim /)); call definePair("pathLengthSquaredDown", (/ xDim, yDim /))
+    end if
+    if(nEdges > 0) then
+      rc = nf90_def_dim(nc, "pathBin", nEdges, binDim)
+      rc = nf90_def_var(nc, "pathBinEdge", nf90_float, binDim, v)      ! (every bin's lower edge, the overflow bin's last)
+      call definePair("pathHistogramUp", (/ binDim /));   call definePair("pathHistogramPathUp", (/ binDim /))
+      call definePair("pathHistogramDown", (/ binDim /)); call definePair("pathHistogramPathDown", (/ binDim /))
+      if(nK > 0) then
+        rc = nf90_def_dim(nc, "absorption", nK, absorptionDim)
+        rc = nf90_def_var(nc, "absorptionCoefficient", nf90_float, absorptionDim, v)
+        call definePair("spectrumUpLower", (/ absorptionDim /));   call definePair("spectrumUpUpper", (/ absorptionDim /))
+        call definePair("spectrumDownLower", (/ absorptionDim /)); call definePair("spectrumDownUpper", (/ absorptionDim /))
+      end if
+    end if
     rc = nf90_enddef(nc)
     if(rc /= nf90_NoErr) print *, "netCDF output: definitions failed ", rc
 
@@ -497,6 +629,26 @@ contains
     end if
     if(computeActinicFlux) then
       call put3("actinicFlux", mActinic(:, :, :, 1));     call put3("actinicFlux_StdErr", mActinic(:, :, :, 2))
+    end if
+    if(computePathLengths) then
+      call put2("pathLengthUp", mPath(:, :, 1, 1));          call put2("pathLengthUp_StdErr", mPath(:, :, 2, 1))
+      call put2("pathLengthSquaredUp", mPath(:, :, 1, 2));   call put2("pathLengthSquaredUp_StdErr", mPath(:, :, 2, 2))
+      call put2("pathLengthDown", mPath(:, :, 1, 3));        call put2("pathLengthDown_StdErr", mPath(:, :, 2, 3))
+      call put2("pathLengthSquaredDown", mPath(:, :, 1, 4)); call put2("pathLengthSquaredDown_StdErr", mPath(:, :, 2, 4))
+    end if
+    if(nEdges > 0) then
+      call put1("pathBinEdge", pathHistogramEdges(:nEdges))
+      call put1("pathHistogramUp", mBins(:, 1, 1));       call put1("pathHistogramUp_StdErr", mBins(:, 2, 1))
+      call put1("pathHistogramPathUp", mBins(:, 1, 2));   call put1("pathHistogramPathUp_StdErr", mBins(:, 2, 2))
+      call put1("pathHistogramDown", mBins(:, 1, 3));     call put1("pathHistogramDown_StdErr", mBins(:, 2, 3))
+      call put1("pathHistogramPathDown", mBins(:, 1, 4)); call put1("pathHistogramPathDown_StdErr", mBins(:, 2, 4))
+      if(nK > 0) then
+        call put1("absorptionCoefficient", absorptionCoefficients(:nK))
+        call put1("spectrumUpLower", mSpectrum(:, 1, 1));   call put1("spectrumUpLower_StdErr", mSpectrum(:, 2, 1))
+        call put1("spectrumUpUpper", mSpectrum(:, 1, 2));   call put1("spectrumUpUpper_StdErr", mSpectrum(:, 2, 2))
+        call put1("spectrumDownLower", mSpectrum(:, 1, 3)); call put1("spectrumDownLower_StdErr", mSpectrum(:, 2, 3))
+        call put1("spectrumDownUpper", mSpectrum(:, 1, 4)); call put1("spectrumDownUpper_StdErr", mSpectrum(:, 2, 4))
+      end if
     end if
     rc = nf90_close(nc)
     if(rc /= nf90_NoErr) print *, "netCDF output: close failed ", rc

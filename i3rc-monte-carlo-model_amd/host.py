@@ -178,6 +178,10 @@ class Domain:
 PATH_LENGTH_NAMES = ("pathLengthUp", "pathLengthSquaredUp", "pathLengthDown", "pathLengthSquaredDown")
 # ... and of the path histogram (i3rc_hip_normalise_path_histogram)
 PATH_HISTOGRAM_NAMES = ("pathHistogramUp", "pathHistogramPathUp", "pathHistogramDown", "pathHistogramPathDown")
+# ... and what the path moments add to them (i3rc_path_moments_layout): the column means and the domain's <L>, <L^2>; the spectrum's bounds
+PATH_MOMENT_SCALARS = ("meanPathLengthUp", "meanPathLengthSquaredUp", "meanPathLengthDown", "meanPathLengthSquaredDown",
+                       "domainPathUp", "domainPathSquaredUp", "domainPathDown", "domainPathSquaredDown")
+PATH_SPECTRUM_NAMES = ("spectrumUpLower", "spectrumUpUpper", "spectrumDownLower", "spectrumDownUpper")
 
 
 class Integrator:
@@ -187,7 +191,7 @@ class Integrator:
                    "intensityPhis", "computeIntensity", "useRayTracing", "useRussianRoulette",
                    "useRussianRouletteForIntensity", "zetaMin", "useHybridPhaseFunsForIntenCalcs",
                    "hybridPhaseFunWidth", "numOrdersOrigPhaseFunIntenCalcs", "limitIntensityContributions",
-                   "maxIntensityContribution", "computeLevelFluxes", "computeActinicFlux", "computePathLengths", "pathHistogramEdges")
+                   "maxIntensityContribution", "computeLevelFluxes", "computeActinicFlux", "computePathLengths", "pathHistogramEdges", "absorptionCoefficients")
 
     def __init__(self, atmosphere, device=0):
         self._h = C.c_void_p()
@@ -220,6 +224,7 @@ class Integrator:
         self.computeActinicFlux = False
         self.computePathLengths = False
         self.pathHistogramEdges = None       # (float32 edges while the path histogram is on)
+        self.absorptionCoefficients = np.zeros(0, np.float32)   # (the spectrum of the path moments; empty: off)
         self._inv_size = [0] * self.ncomp
         self._fwd_size = [0] * self.ncomp
         self._fwd_stale = True
@@ -347,6 +352,14 @@ class Integrator:
             self._check(self._lib.i3rc_hip_set_path_histogram(self._h, max(e.size - 1, 0), pf(e) if e.size else None), "specifyParameters")
             self.pathHistogramEdges = e.copy() if e.size else None
             self._results = None             # (the tally layout has changed)
+
+        if "absorptionCoefficients" in kw:
+            # the absorption coefficients at which the path moments bracket R(k) from the histogram (i3rc_hip_set_path_spectrum): not in
+            # the reference.  None or an empty array switches the spectrum off.
+            k = kw["absorptionCoefficients"]
+            k = np.zeros(0, np.float32) if k is None else f32(np.asarray(k).ravel())
+            self._check(self._lib.i3rc_hip_set_path_spectrum(self._h, int(k.size), pf(k) if k.size else None), "specifyParameters")
+            self.absorptionCoefficients = k.copy()
 
     def path_histogram_layout(self):
         """(offsets of binUp, binPathUp, binDown, binPathDown, the number of bins, total) of the packed tally buffer, in float64
@@ -538,6 +551,40 @@ class Integrator:
         mean over the columns of every level or layer, per batch.  In cells without extinction the actinic flux's variance diverges
         (INTEGRATION.md): its standard errors are not to be trusted there."""
         return self._batch_moments(True, seed, numBatches, solarMu, solarAzimuth, numberOfPhotons)
+
+    def computeRadiativeTransferPathMoments(self, seed, numBatches, solarMu, solarAzimuth, numberOfPhotons):
+        """computeRadiativeTransferBatchMoments for a loop with a path tally switched on (specifyParameters: computePathLengths or
+        pathHistogramEdges; i3rc_hip_run_batches_path_moments): batch k is what computeRadiativeTransfer(new_RandomNumberSequence(
+        (seed[0], seed[1] + k)), ...) traces with the tally on.  The two dicts also hold the sums of pathLengthUp ... pathLengthSquaredDown
+        (ny, nx), of their column means meanPathLength... and of the domain's <L> and <L^2>, domainPathUp ... domainPathSquaredDown -- or of
+        pathHistogramUp ... pathHistogramPathDown (nBins + 1) and, with absorptionCoefficients, of spectrumUpLower ... spectrumDownUpper
+        (nK): the two bounds of the band's reflectance and transmittance at every coefficient, per batch."""
+        if not self.isReady_Integrator():
+            raise I3RCError("computeRadiativeTransfer: problem not completely specified.")
+        self._ensure_tables()
+        lay, play = B.MomentsLayout(), B.PathMomentsLayout()
+        self._check(self._lib.i3rc_hip_get_moments_layout(self._h, C.byref(lay)), "computeRadiativeTransfer")
+        self._check(self._lib.i3rc_hip_get_path_moments_layout(self._h, C.byref(play)), "computeRadiativeTransfer")
+        bufs = [np.zeros(lay.total, np.float64), np.zeros(lay.total, np.float64), np.zeros(B.NUM_COUNTERS, np.float64),
+                np.zeros(play.total, np.float64), np.zeros(play.total, np.float64)]
+        self._check(self._lib.i3rc_hip_run_batches_path_moments(self._h, int(seed[0]), int(seed[1]), int(numBatches), int(numberOfPhotons),
+                                                               C.byref(_directional(solarMu, solarAzimuth)), *[b.ctypes.data_as(B.dp) for b in bufs]),
+                    "computeRadiativeTransfer")
+        out = []
+        for m, x in ((bufs[0], bufs[3]), (bufs[1], bufs[4])):
+            d = self._unpack_moments(lay, m, None, None)
+            if play.kind == B.EXTRA_KINDS["paths"]:
+                for k in PATH_LENGTH_NAMES:
+                    d[k] = x[getattr(play, k):getattr(play, k) + self.nx * self.ny].reshape(self.ny, self.nx)
+                for k in PATH_MOMENT_SCALARS:
+                    d[k] = x[getattr(play, k)]
+            else:
+                for k, word in zip(PATH_HISTOGRAM_NAMES, ("histogramUp", "histogramPathUp", "histogramDown", "histogramPathDown")):
+                    d[k] = x[getattr(play, word):getattr(play, word) + play.nBins + 1]
+                for k in PATH_SPECTRUM_NAMES:
+                    d[k] = x[getattr(play, k):getattr(play, k) + play.nK]
+            out.append(d)
+        return out[0], out[1], {k: float(bufs[2][i]) for i, k in enumerate(B.COUNTER_NAMES)}
 
     def _batch_moments(self, diagnostic, seed, numBatches, solarMu, solarAzimuth, numberOfPhotons):
         """either moments call of the library: (sums, sums of squares, counters), the diagnostic tally's sums in the same two dicts"""

@@ -217,7 +217,8 @@ int i3rc_hip_normalise_actinic_flux(const i3rc_hip_integrator *h, const double *
  * counter for counter -- and is refused, before anything is touched, when radiance directions are set (nDir > 0) or max cross-section
  * is in use (useRayTracing = 0); i3rc_hip_run_batches, i3rc_hip_run_batches_moments, i3rc_hip_expect_batches, i3rc_hip_run_replay,
  * i3rc_hip_run_batches_diagnostic_moments and i3rc_hip_get_diagnostic_moments_layout are refused (the diagnostic moments' layout has no
- * slot for this kind: it has no batch statistics); i3rc_hip_compute_batch does not look ahead.  Through layers WITHOUT extinction over a
+ * slot for this kind); its batch statistics -- of the four fields, their means and the domain's <L> and <L^2> -- come from
+ * i3rc_hip_run_batches_path_moments, in a layout of their own; i3rc_hip_compute_batch does not look ahead.  Through layers WITHOUT extinction over a
  * reflecting surface the estimate of <L> has infinite variance and <L^2> diverges logarithmically (a Lambertian reflection into mu
  * crosses such a layer on a path of dz / mu); extinction in every cell removes the problem. */
 int i3rc_hip_set_path_lengths(i3rc_hip_integrator *h, int on);
@@ -254,6 +255,8 @@ int i3rc_hip_normalise_path_lengths(const i3rc_hip_integrator *h, const double *
  * counter -- and is refused exactly where a launch with path lengths on is: radiance directions, max cross-section,
  * i3rc_hip_run_batches, i3rc_hip_run_batches_moments, i3rc_hip_expect_batches, i3rc_hip_run_replay,
  * i3rc_hip_run_batches_diagnostic_moments and i3rc_hip_get_diagnostic_moments_layout; i3rc_hip_compute_batch does not look ahead.
+ * Its batch statistics -- of the four fields and of the two bounds of R(k) at the coefficients of i3rc_hip_set_path_spectrum -- come
+ * from i3rc_hip_run_batches_path_moments, in a layout of their own.
  * Where the launch's LDS has room for them, a workgroup keeps the 4 (nBins + 1) sums and the edges in LDS, at any place of the
  * extinction field (i3rc_hip_set_lds_tallies(h, 0) switches that off); else the kernel adds to the block in global memory with float64
  * atomics.  i3rc_hip_last_plan's fourteenth word says which. */
@@ -369,6 +372,50 @@ int i3rc_hip_diagnostic_moments_layout_words(int kind, int nx, int ny, int nz, i
 int i3rc_hip_run_batches_diagnostic_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1, int nBatches, int64_t nPhotons,
                                             const i3rc_source *src, double *sum, double *sumSquares, double *counters,
                                             double *extraSum, double *extraSumSquares);
+
+/* THE PATH MOMENTS (not in the reference): batch statistics of the two path tallies above and of what users derive from them, which is
+ * not linear in the tallies -- so a standard error has to be formed batch by batch, as the reference's drivers form every other one
+ * (Example-Drivers/monteCarloDriver.f95:300-321, :358-378).
+ * Layout (in float64 elements) of a block of path moments; kind: 3 path lengths, 4 the path histogram (ExtraTally, csrc/tally_block.hpp);
+ * the offsets of what the kind has not are -1.  Every value is rounded once to float32 per batch, as reportResults hands its results out.
+ *   path lengths: the four fields as i3rc_hip_normalise_path_lengths gives them; their plain means over the columns (as meanFluxUp is
+ *     formed, :739-742); and the DOMAIN's path figures, domainPathUp = float(sum over the columns of raw pathUp1 / sum over the columns
+ *     of raw fluxUp) = <L> of the reflected light, domainPathSquaredUp the same of pathUp2 = <L^2>, the two Down words over fluxDown;
+ *     0 where the denominator is 0.  The ratio of raw sums is the area-weighted ratio on every grid.
+ *   the histogram: the four fields as i3rc_hip_normalise_path_histogram gives them; and for every absorption coefficient k_j of
+ *     i3rc_hip_set_path_spectrum the two bounds of R(k_j) = sum_b binUp[b] <exp(-k_j L)>_b / photons, in units of the incident flux:
+ *     from below exp(-k m_b) at the bin's mean path m_b = binPathUp[b] / binUp[b] (clamped to the bin's edges), from above the chord
+ *     over the bin; the overflow bin has exp(-k edges[nBins]) from above (path_spectrum_term, csrc/tally_block.hpp; float64, the
+ *     device's exp).  spectrumUpLower[j] <= R(k_j) <= spectrumUpUpper[j]; k = 0 gives the domain's mean fluxUp in both.  The Down words:
+ *     the same of the transmitted light. */
+typedef struct i3rc_path_moments_layout {
+  int64_t kind, nBins, nK;
+  int64_t pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown;                   /* nx*ny each ([ny][nx]) */
+  int64_t meanPathLengthUp, meanPathLengthSquaredUp, meanPathLengthDown, meanPathLengthSquaredDown;   /* 1 each                */
+  int64_t domainPathUp, domainPathSquaredUp, domainPathDown, domainPathSquaredDown;                   /* 1 each                */
+  int64_t histogramUp, histogramPathUp, histogramDown, histogramPathDown;                             /* nBins + 1 each        */
+  int64_t spectrumUpLower, spectrumUpUpper, spectrumDownLower, spectrumDownUpper;                     /* nK each               */
+  int64_t total;
+} i3rc_path_moments_layout;
+/* The absorption coefficients of the spectrum: 0 <= nK <= 256 float32 values, each finite and >= 0, in 1 / the grid's length unit.
+ * nK == 0 switches the spectrum off (absorption is not read).  Bad values are refused with a text that names what is wrong, before
+ * anything is touched.  Independent of i3rc_hip_set_path_histogram: it only sizes the path moments' layout and moves no offset of the
+ * tally block. */
+int i3rc_hip_set_path_spectrum(i3rc_hip_integrator *h, int nK, const float *absorption);
+/* The layout of the path tally that is switched on; fails with "no path tally is switched on" for any other kind. */
+int i3rc_hip_get_path_moments_layout(const i3rc_hip_integrator *h, i3rc_path_moments_layout *layout);
+/* ... and as host code of its own (no device needed): out[0..20] = the struct's words behind nK, in order.  Returns 0; 1 on a kind
+ * other than 3 / 4, a size below 1, nBins outside 1 ... 1024 for kind 4, nK outside 0 ... 256, a null out or nout < 21. */
+int i3rc_hip_path_moments_layout_words(int kind, int nx, int ny, int nBins, int nK, int64_t *out, int nout);
+/* A driver's batch loop WITH A PATH TALLY SWITCHED ON (i3rc_hip_set_path_lengths or i3rc_hip_set_path_histogram), its statistics
+ * gathered on the device.  Batch k = 0 .. nBatches-1 is exactly what i3rc_hip_launch_batch(seed0, seed1 + k, 0, nPhotons) traces with
+ * the kind on, always one launch per batch with up to 6 batches in flight, never a fused group.  sum / sumSquares / counters are filled
+ * as i3rc_hip_run_batches_moments fills them (i3rc_moments_layout), pathSum / pathSumSquares (i3rc_path_moments_layout) with x and x*x
+ * of every word of the layout above, from the same photons.  Nothing of a batch is copied to the host.  Refused, with the entry
+ * point's name in front: no path tally switched on; radiance directions or max cross-section (as i3rc_hip_launch_batch refuses them);
+ * sources other than Directional; bad arguments; nPhotons <= 0.  Synchronous; nothing stays in flight after a failure. */
+int i3rc_hip_run_batches_path_moments(i3rc_hip_integrator *h, uint32_t seed0, uint32_t seed1, int nBatches, int64_t nPhotons, const i3rc_source *src,
+                                      double *sum, double *sumSquares, double *counters, double *pathSum, double *pathSumSquares);
 
 /* computeRadiativeTransfer (:262-398) for ONE batch of a driver's loop -- i3rc_hip_zero_tallies + i3rc_hip_launch_batch(seed0,
  * seed1, 0, nPhotons) + i3rc_hip_fetch_tallies into hostTallies, in a tally buffer and on a stream of the library's own --
