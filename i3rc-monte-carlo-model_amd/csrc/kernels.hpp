@@ -527,6 +527,9 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   Lds L;
   constexpr bool STORE = has_start_store<Rng>(INTENSITY, GENERAL, GRID, MULTI);   // photons start a wavefront at a time: part B of the event phase
   constexpr bool FLAGS = STORE && I3RC_EVENT_FLAGS != 0;   // the event phase reads launch facts from DevProblem::eventFlags (event_flags.hpp)
+  // ... and how their photon step spells its addresses and its outcome (StepForm, tracer.hpp): one switch of tuning.hpp per bit
+  constexpr int STEP_FORM = !STORE ? 0 : (I3RC_STEP_BIASED_ADDRESS ? STEP_BIASED : 0) | (I3RC_STEP_STATE_SELECTS ? STEP_MASKS : 0) |
+                                         (I3RC_STEP_COLD_ERROR ? STEP_COLD_ERROR : 0);
   // Which voxel step (trace_step_lazy): the general kernels' guarded division in a branch of its own, and -- CHAIN -- in the fused ring
   // kernels of a bricked field the specialised step as it was before zero cosines fell out of its minimum: with the minimum these two
   // instantiations ran out of scalar registers by two and kept the wave-uniform `adaptEvent` as a lane mask in a vector register,
@@ -1536,7 +1539,9 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
               bool needCell;
               if constexpr (FLAGS) needCell = (Pe.eventFlags & kNeedCell) != 0u;
               else needCell = GENERAL || MULTI || !(Pe.uniformSsa >= 0.0f) || Pe.uniformSsa < 1.0f || Pe.uniformPf < 1;
-              if (needCell) cell = cell_index(Pe, r.ix, r.iy, r.iz);
+              // (STEP_BIASED: the index from cell_word -- cell_address.hpp --, its three `- 1` as one scalar constant taken off the sum)
+              if (needCell) cell = (STEP_FORM & STEP_BIASED) != 0 ? (int)(cell_word(Pe.nx, Pe.ny, r.ix, r.iy, r.iz) - (unsigned)(Pe.nx * Pe.ny + Pe.nx + 1))
+                                                                  : cell_index(Pe, r.ix, r.iy, r.iz);
               int comp = 1;                                               // :637-638
               // TWO components (cloud + gas, cloud + aerosol: the usual production domain): what the scattering needs of its cell comes as
               // ONE 16-byte record (DevProblem::cellRec) -- one cache line, one trip to L2 -- and the component's pair is picked when the
@@ -1745,6 +1750,33 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           float len = 0.0f;
           s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, true, CHAIN>(P, L, r, true, &len);
           if (s == STEP_CONTINUE || s == STEP_EXIT) pathLen += (double)len;
+        } else if constexpr (STEP_FORM != 0) {   // (STORE, round 15: the step in another spelling -- StepForm, tracer.hpp)
+          StepMasks sm;
+          // (the field in LDS: the bias the step reads the extinction through -- cell_address.hpp; launch-uniform, so the compiler makes it in
+          // front of the loop, and opaque to it there: it otherwise takes the constant apart again and adds its pieces per step)
+          sm.ldsBias = 0u;
+          if constexpr ((STEP_FORM & STEP_BIASED) != 0 && GRID == GRID_LDS) { sm.ldsBias = ext_address_bias(P, L); asm("" : "+s"(sm.ldsBias)); }
+#ifdef I3RC_PROFILE_PHASES
+          s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, false, CHAIN, I3RC_WRAP_PER_AXIS != 0, STEP_FORM>(P, L, r, true, nullptr, &wrapAxes, &sm);
+#else
+          s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, false, CHAIN, I3RC_WRAP_PER_AXIS != 0, STEP_FORM>(P, L, r, true, nullptr, nullptr, &sm);
+#endif
+          if constexpr ((STEP_FORM & STEP_MASKS) != 0) {
+            // the mapping below as ONE chain of selects on the masks the step has anyway -- arrived, above the top, below the bottom; they
+            // exclude one another --, the bottom's state wave-uniform, a scalar select: the nested form came out as two compares, a
+            // select and a second exec region with a compare, a mask OR and a select of its own
+            int next = sm.bottom ? (blackSurface ? ST_EXIT : ST_EVENT) : ST_TRACE;
+            next = sm.top ? ST_EXIT : next;
+            st = sm.reach ? ST_EVENT : next;
+            if constexpr (!(STEP_FORM & STEP_COLD_ERROR)) st = sm.error ? ST_DROPPED : st;
+          } else if (s != STEP_CONTINUE) {
+            st = s == STEP_DONE ? ST_EVENT : (s == STEP_ERROR ? ST_DROPPED : ((r.iz >= 1 || blackSurface) ? ST_EXIT : ST_EVENT));
+          }
+          if constexpr ((STEP_FORM & STEP_COLD_ERROR) != 0) {   // the step's error exit: r.acc = -2 and the dropped state, as the early exit gave them
+            if (__builtin_expect(__ballot(sm.error) != 0ull, 0))
+              if (sm.error) { r.acc = -2.0f; st = ST_DROPPED; }
+          }
+          s = STEP_CONTINUE;   // (the state is set)
         } else
 #ifdef I3RC_PROFILE_PHASES
         s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, false, CHAIN, STORE && I3RC_WRAP_PER_AXIS>(P, L, r, true, nullptr, STORE ? &wrapAxes : nullptr);

@@ -10,6 +10,7 @@
 
 #include "../../include/i3rc_hip.h"
 #include "philox.hpp"
+#include "cell_address.hpp"
 
 namespace i3rc {
 
@@ -538,6 +539,32 @@ __device__ __forceinline__ float cell_extinction(const PR &P, const Lds &L, int 
   if (GRID == GRID_BRICKS) return P.extBrick[brick_index(P, ix, iy, iz)];
   return P.totalExt[cell_index(P, ix, iy, iz)];
 }
+// The same word of the same field with its address in the biased-base form of cell_address.hpp: the indices' three `- 1` and the base in
+// ONE launch-uniform constant, where cell_index costs a read six vector instructions more than the two multiplies, the three-way add
+// and the shift-and-add it needs.  The photon step of the specialised flux kernels of plain launches alone asks for it
+// (trace_step_lazy, STEP_BIASED); the field in LDS, read linearly from global memory, or as column records.
+//   ldsBias   GRID_LDS: cell_address_bias of Lds::ext, made once per wave by the caller (ext_address_bias)
+template <class PR>
+__device__ __forceinline__ uint32_t ext_address_bias(const PR &P, const Lds &L) { return cell_address_bias((uint32_t)lds_address(L.ext), P.nx, P.ny); }
+template <int GRID, class PR>
+__device__ __forceinline__ float cell_extinction_biased(const PR &P, uint32_t ldsBias, int ix, int iy, int iz) {
+  static_assert(GRID == GRID_LDS || GRID == GRID_GLOBAL || GRID == GRID_COLUMNS, "the biased form: the three places of the specialised flux kernels");
+  if constexpr (GRID == GRID_LDS) return lds_read((int)cell_address(ldsBias, P.nx, P.ny, ix, iy, iz));
+  if constexpr (GRID == GRID_COLUMNS) {
+    // (the descriptor's base moved down by the bias, its extent up by as much: the records' own end stays where it was, and the nx + 1
+    // records' worth in front of them is never asked for -- the indices begin at 1)
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    const int lead = (P.nx + 1) << 3;
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)P.colRec - lead), 0, ((P.nx * P.ny) << 3) + lead, 0x00020000);
+    const u32x2 rec = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)column_address(0u, P.nx, ix, iy, 3), 0, 0);
+    return ((unsigned)iz - (rec.y & 0xffffu)) <= (rec.y >> 16) ? __uint_as_float(rec.x) : 0.0f;
+  }
+  if constexpr (GRID == GRID_GLOBAL) {
+    // (the 64-bit base less the bias's constant, a scalar pair; the word's number zero-extended: it may pass 2^30 by that constant)
+    const char *const base = (const char *)P.totalExt - 4ll * ((long long)P.nx * P.ny + P.nx + 1);
+    return *(const float *)(base + ((unsigned long long)cell_word(P.nx, P.ny, ix, iy, iz) << 2));
+  }
+}
 
 
 // One iteration of accumulationLoop, accumulateExtinctionAlongPath :1690-1806.  hasTarget == false: trace to the
@@ -568,11 +595,25 @@ __device__ __forceinline__ float cell_extinction(const PR &P, const Lds &L, int 
 // keep it: see photon_kernel.)
 // (AXES: the periodic wrap at the end of the step, x behind its own mask and y behind its own -- see there; the photon step of the
 // specialised flux kernels of plain launches alone asks for it)
-template <int GRID, bool CLEARMAP = false, bool BRANCHY = false, bool SHORT = false, bool LENGTH = false, bool CHAIN = false, bool AXES = false, class PR>
-__device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L, Ray &r, bool hasTarget, float *length = nullptr, unsigned *wrapAxes = nullptr) {
+// (FORM, bits of StepForm: how the step spells addresses and its outcome, never what it computes -- the photon step of the specialised flux
+// kernels of plain launches alone asks for any of them, one tuning.hpp switch each:
+//   STEP_BIASED      the extinction's address in the biased-base form (cell_extinction_biased; StepMasks::ldsBias goes IN);
+//   STEP_MASKS       the caller selects its lane state from the step's own lane masks, which any bit of FORM hands out in *masks;
+//   STEP_COLD_ERROR  no early exit for `step <= 0` (no workload takes it): a failed lane runs the step's selects on its rubbish, and the
+//                    CALLER gives it what the early exit gave -- r.acc = -2 and the dropped state -- behind one wave-uniform branch on
+//                    StepMasks::error, the defaults inside it; the value returned for such a lane means nothing.  Its position and
+//                    indices, which the early exit left alone, are then rubbish too, and nobody reads them: the photon is dropped and
+//                    its lane's next photon sets all of them anew.)
+enum StepForm { STEP_BIASED = 1, STEP_MASKS = 2, STEP_COLD_ERROR = 4 };
+struct StepMasks { uint32_t ldsBias; bool reach, top, bottom, error; };
+template <int GRID, bool CLEARMAP = false, bool BRANCHY = false, bool SHORT = false, bool LENGTH = false, bool CHAIN = false, bool AXES = false, int FORM = 0, class PR>
+__device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L, Ray &r, bool hasTarget, float *length = nullptr, unsigned *wrapAxes = nullptr,
+                                                      StepMasks *masks = nullptr) {
   // the extinction of the current cell is requested first: its latency (LDS, or L2 / HBM for grids that do not fit
   // in LDS) is covered by the three face-distance divisions below
-  const float ext = cell_extinction<GRID, CLEARMAP>(P, L, r.ix, r.iy, r.iz);
+  float ext;
+  if constexpr ((FORM & STEP_BIASED) != 0) ext = cell_extinction_biased<GRID>(P, masks->ldsBias, r.ix, r.iy, r.iz);
+  else ext = cell_extinction<GRID, CLEARMAP>(P, L, r.ix, r.iy, r.iz);
   const int cx = r.cx, cy = r.cy, cz = r.cz;
   const float ex = lds_read(r.ex + (r.ix << 2)), ey = lds_read(r.ey + (r.iy << 2)), ez = lds_read(r.ez + (r.iz << 2));
   float stx, sty, stz;
@@ -625,7 +666,13 @@ __device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L,
   }
   // :1711-1714 `if(thisStep <= 0.)`, written so that a NaN step (a NaN direction or position) ends the trace as well:
   // the reference's comparison lets NaN through and its loop never ends
-  if (__builtin_expect(!(step > 0.0f), 0)) { r.acc = -2.0f; return STEP_ERROR; }
+  if constexpr (!(FORM & STEP_COLD_ERROR)) {
+    if (__builtin_expect(!(step > 0.0f), 0)) {
+      r.acc = -2.0f;
+      if constexpr (FORM != 0) { masks->reach = masks->top = masks->bottom = false; masks->error = true; }
+      return STEP_ERROR;
+    }
+  }
 
   const float tauCell = step * ext;
   bool reach = false;
@@ -702,6 +749,7 @@ __device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L,
   // trace is over, and the height is put there by whoever needs it (finish_exit: the event phase for photons; a local-estimate
   // ray's end only asks for its layer index)
   const bool top = r.iz > P.nz, bottom = r.iz < 1;
+  if constexpr (FORM != 0) { masks->reach = reach; masks->top = top; masks->bottom = bottom; masks->error = (FORM & STEP_COLD_ERROR) != 0 && !(step > 0.0f); }
   return reach ? STEP_DONE : ((top || bottom) ? STEP_EXIT : STEP_CONTINUE);
 }
 // the height of a ray that has left the grid :1793-1804 (a ray inside keeps its own)

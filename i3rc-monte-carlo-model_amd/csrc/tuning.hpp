@@ -76,6 +76,17 @@
 #ifndef I3RC_TABLE_RCP_ONCE
 #define I3RC_TABLE_RCP_ONCE 1  /* the inverse table's reciprocal length once per wave, not once per scattering */
 #endif
+// round 15, the same six kernels: how their photon step spells addresses and its outcome -- the float operations and their order are
+// untouched; one switch per item, 0 = the kernels of round 14 (profiles/r15_step_addressing.txt)
+#ifndef I3RC_STEP_BIASED_ADDRESS
+#define I3RC_STEP_BIASED_ADDRESS 1   /* the extinction read's address (and the event phase's one cell index) in the biased-base form of cell_address.hpp */
+#endif
+#ifndef I3RC_STEP_STATE_SELECTS
+#define I3RC_STEP_STATE_SELECTS 1    /* the lane state after a step: one chain of selects on the step's own masks, the bottom's value a scalar */
+#endif
+#ifndef I3RC_STEP_COLD_ERROR
+#define I3RC_STEP_COLD_ERROR 1       /* the error exit of the step (no workload takes it) behind one uniform branch, its defaults inside */
+#endif
 #ifndef I3RC_PHOTON_STEP_AHEAD
 #define I3RC_PHOTON_STEP_AHEAD 64   /* off: measured -1.6 % (step cloud) ... +2.8 % (Landsat-36), -3 % on the radar field */
 #endif
