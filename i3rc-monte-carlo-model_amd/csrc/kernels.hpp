@@ -30,6 +30,7 @@
 #include <cstddef>
 #include "tally_block.hpp"
 #include "event_flags.hpp"
+#include "pass_decision.hpp"
 #include "tracer.hpp"
 #include "tuning.hpp"
 
@@ -530,6 +531,15 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   // ... and how their photon step spells its addresses and its outcome (StepForm, tracer.hpp): one switch of tuning.hpp per bit
   constexpr int STEP_FORM = !STORE ? 0 : (I3RC_STEP_BIASED_ADDRESS ? STEP_BIASED : 0) | (I3RC_STEP_STATE_SELECTS ? STEP_MASKS : 0) |
                                          (I3RC_STEP_COLD_ERROR ? STEP_COLD_ERROR : 0);
+  // ... and how the head of their loop decides a pass and hands the decision to the event phase: one switch of tuning.hpp each
+  constexpr bool PASS_BITS = STORE && I3RC_PASS_DECISION != 0;   // stop / runEvent / doTurn as bits of one 32-bit scalar (pass_decision.hpp)
+  constexpr bool TURN_WORD = STORE && I3RC_TURN_ALL_WORD != 0;   // doTurn as a 64-bit -1 / 0 word made once per event phase
+  // ... and their lanes' states in a numbering of their own, in which the three turnover states are the range's end -- NEW 3, DROPPED 4,
+  // EXIT 5, the finished lane's DONE in DROPPED's place at 2 -- and `wantTurn` is one compare.  Every other kernel keeps LaneState's numbers.
+  constexpr bool TURN_RANGE = STORE && I3RC_TURN_STATE_RANGE != 0;
+  constexpr int kStDropped = TURN_RANGE ? (int)ST_DONE : (int)ST_DROPPED, kStDone = TURN_RANGE ? (int)ST_DROPPED : (int)ST_DONE;
+  static_assert(!TURN_RANGE || (ST_NEW == 3 && kStDropped == 4 && ST_EXIT == 5 && kStDone < ST_NEW && ST_TRACE < ST_NEW && ST_EVENT < ST_NEW),
+                "the turnover states are the states from ST_NEW on");
   // Which voxel step (trace_step_lazy): the general kernels' guarded division in a branch of its own, and -- CHAIN -- in the fused ring
   // kernels of a bricked field the specialised step as it was before zero cosines fell out of its minimum: with the minimum these two
   // instantiations ran out of scalar registers by two and kept the wave-uniform `adaptEvent` as a lane mask in a vector register,
@@ -941,7 +951,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       // ============================================================================================== RAY MODE?
       // enough local-estimate rays to fill the wavefront (or no room for the next event phase, or no photons left)?
       const int work = DIRECT ? (int)(rdTail - rdHead) : (int)((qTail - qHeadEv) * (unsigned)P.nDir - qHeadSub) + (int)(rdTail - rdHead);
-      photonsLeft = __ballot(st != ST_DONE) != 0ull;
+      photonsLeft = __ballot(st != kStDone) != 0ull;
       if (work > 0 && (work >= (DIRECT ? kDirectEnter : 64) || !photonsLeft || wantSlots)) {
         wantSlots = false;
         // this lane's shadow ray: registers of the ray loop only (rays still under way when the wave leaves go back to the
@@ -1133,19 +1143,35 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
     const bool wantScat = st == ST_EVENT;
     // (STORE: the three states as ONE compare, so that the ballot below is that compare's own mask -- the three-way OR came out as
     // a lane mask turned into 0 / 1 in a vector register and compared again: six vector instructions at every pass of the loop)
-    constexpr unsigned kTurnStates = (1u << ST_EXIT) | (1u << ST_DROPPED) | (1u << ST_NEW);
-    const bool wantTurn = STORE ? ((kTurnStates >> (unsigned)st) & 1u) != 0u : (st == ST_EXIT || st == ST_DROPPED || st == ST_NEW);
+    constexpr unsigned kTurnStates = (1u << ST_EXIT) | (1u << kStDropped) | (1u << ST_NEW);
+    // (round 16, TURN_RANGE: ... in the STORE kernels' own numbering, where the three states are the last three, it is one compare indeed)
+    const bool wantTurn = TURN_RANGE ? st >= ST_NEW
+                                     : (STORE ? ((kTurnStates >> (unsigned)st) & 1u) != 0u : (st == ST_EXIT || st == kStDropped || st == ST_NEW));
     const unsigned long long scMask = __ballot(wantScat), tuMask = __ballot(wantTurn);
     const unsigned long long trMask = __ballot(st == ST_TRACE);
+    if constexpr (!PASS_BITS)
     if (scMask == 0ull && tuMask == 0ull && trMask == 0ull) break;   // (no photons left; any ray work has been done in ray mode above)
     int nSc = (int)__popcll(scMask), nTu = (int)__popcll(tuMask);
     // (STORE: the counts are 32-bit scalars from here on -- left as the 64-bit population counts they come from, their comparisons
     // with the quorums came out as v_cmp_gt_u64 on scalar pairs, two vector instructions of the expensive class at every pass)
     if constexpr (STORE) asm volatile("" : "+s"(nSc), "+s"(nTu));
-    bool runEvent = nSc + nTu > 0 && (nSc >= evThr || nTu >= kTurnForce || trMask == 0ull);
-    const bool doTurn = nTu >= kTurnMin || trMask == 0ull || nSc == 0;
-    const bool wantEvent = wantScat || (doTurn && wantTurn);
-    const unsigned long long evMask = __ballot(wantEvent);            // the lanes this event phase serves
+    // (round 16: stop, runEvent and doTurn as the bits of one 32-bit scalar -- pass_decision.hpp; as booleans each wave-uniform compare
+    // came out as s_cmp + s_cselect_b64 -1 / 0, joined as lane masks and copied to vcc: 24 scalar instructions in front of the step)
+    int pass = 0;
+    if constexpr (PASS_BITS || TURN_WORD) pass = pass_decision<kTurnMin, kTurnForce>(nSc, nTu, trMask == 0ull, evThr);
+    bool runEvent;
+    if constexpr (PASS_BITS) {
+      // (the loop still ends HERE, in front of the event branch: left from inside that branch -- a wave that stops has the event bit set --
+      // it had a second way out, and the compiler kept the photon in one register set at the head and another at the latch: twelve
+      // vector copies per step and seven spilled vector registers)
+      if ((pass & kPassStop) != 0) break;   // (no photons left)
+      runEvent = (pass & kPassEvent) != 0;
+    } else {
+      runEvent = nSc + nTu > 0 && (nSc >= evThr || nTu >= kTurnForce || trMask == 0ull);
+    }
+    const bool doTurn = TURN_WORD ? (pass & kPassTurn) != 0 : (nTu >= kTurnMin || trMask == 0ull || nSc == 0);
+    bool wantEvent = wantScat || (doTurn && wantTurn);
+    unsigned long long evMask = __ballot(wantEvent);            // the lanes this event phase serves
     if (DEFER && runEvent && (DIRECT ? kReady - (int)(rdTail - rdHead) : (int)(P.rayQueueCap - (int)(qTail - qHeadEv))) < nSc) {
       // every lane of the event phase may push one record: without room for all of them the rays are served first
       wantSlots = true;
@@ -1153,6 +1179,20 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       if (trMask == 0ull) continue;
     }
     if (runEvent) {
+      unsigned long long turnAll = doTurn ? ~0ull : 0ull;   // (the wave-uniform doTurn as a mask: no branch, no detour through a vector register)
+      if constexpr (TURN_WORD) {
+        // (round 16: ... as a real 64-bit word, all ones or none -- the decision's bit moved up to the sign and brought down again, opaque in
+        // between: seen through, every `mask & turnAll` came out as s_and_b64 with exec and two s_cselect_b32 ..., 0.  The lanes this
+        // phase serves are then scalar arithmetic on the head's masks, and a lane's own flag is its bit of that mask.  Made HERE: the
+        // compiler does not move the opaque step, and in front of the branch it ran at every pass)
+        int sign = (int)((unsigned)(pass & kPassTurn) << 29);
+        static_assert(kPassTurn == 4, "the shift above puts kPassTurn into the sign");
+        if constexpr (!PASS_BITS) sign = __builtin_amdgcn_readfirstlane(sign);   // (a measurement build: beside the boolean head the compiler takes the bit for a lane's)
+        asm volatile("" : "+s"(sign));
+        turnAll = (unsigned long long)(long long)(sign >> 31);
+        evMask = scMask | (tuMask & turnAll);
+        wantEvent = __builtin_amdgcn_inverse_ballot_w64(evMask);
+      }
       // The event phase reads the problem through a pointer into the kernarg segment (scalar loads where they are
       // needed) instead of keeping some sixty more values in scalar registers through the whole kernel: the kernel
       // wanted well over twice the scalar registers there are, and every spilled one comes back as a v_readlane,
@@ -1199,14 +1239,13 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       bool turnPhase = true;
       unsigned long long geTop = 0ull, leSurf = 0ull;      // STORE: lanes at or above the top / at or below the surface, any state
       unsigned long long topMask = 0ull, surfMask = 0ull;  // STORE: the lanes part A finds at the top / at the surface (none in a phase that skips it)
-      const unsigned long long turnAll = doTurn ? ~0ull : 0ull;   // (the wave-uniform doTurn as a mask: no branch, no detour through a vector register)
       if constexpr (STORE) {
         geTop = __ballot(r.z >= Pe.zMax); leSurf = __ballot(r.z <= surfaceZ);
-        turnPhase = (doTurn && tuMask != 0ull) || (scMask & (geTop | leSurf)) != 0ull;
+        turnPhase = (TURN_WORD ? (tuMask & turnAll) != 0ull : (doTurn && tuMask != 0ull)) || (scMask & (geTop | leSurf)) != 0ull;
       }
       if (turnPhase) {
       const bool isEv = wantEvent && (st == ST_EVENT || st == ST_EXIT);
-      const bool dropped = wantEvent && st == ST_DROPPED;                 // :488-489
+      const bool dropped = wantEvent && st == kStDropped;                 // :488-489
       const bool atTop = isEv && r.z >= Pe.zMax;                           // :499-514
       const bool atSurface = isEv && !atTop && r.z <= surfaceZ;           // :515-531
       const bool atBlack = atSurface && blackSurface;                     // ... and :560-562
@@ -1222,7 +1261,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
         const unsigned long long evExit = scMask | (__ballot(st == ST_EXIT) & turnAll);   // isEv, as a mask
         topMask = evExit & geTop;
         surfMask = evExit & ~topMask & leSurf;
-        wc.dropped += (unsigned)__popcll(__ballot(st == ST_DROPPED) & turnAll);
+        wc.dropped += (unsigned)__popcll(__ballot(st == kStDropped) & turnAll);
         wc.top += (unsigned)__popcll(topMask);
         wc.surf += (unsigned)__popcll(surfMask);
       } else {
@@ -1290,7 +1329,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
             if (__ballot(leaves) != 0ull) flush_lanes(leaves);
           }
           if (isNew) {
-            if (mine < 0) st = ST_DONE;   // (only when the launch has no chunks left)
+            if (mine < 0) st = kStDone;   // (only when the launch has no chunks left)
             else rng.start((uint64_t)(Ae.firstPhoton + mine), mineBatch);
           }
         }
@@ -1370,7 +1409,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
             startAvail = n;
           }
           if (isNew) {
-            if (mine < 0) st = ST_DONE;
+            if (mine < 0) st = kStDone;
             else RngInit<Rng>::start(rng, Ae, mine);
           }
         }
@@ -1398,7 +1437,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
         res.next += taken;
         wc.photons += (unsigned)taken;
         if (isNew) {
-          if (mine < 0) st = ST_DONE;
+          if (mine < 0) st = kStDone;
           else {
             if (slabs) mine = (long long)Ae.slabIds[mine];   // position in the sorted list -> photon number
             if constexpr (!BATCHED) RngInit<Rng>::start(rng, Ae, mine);
@@ -1410,7 +1449,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       // ---- part C: one random block per lane for this event, then the event itself
       bool didScatter = false, didRoulette = false, startedTrace = false;   // per-lane flags -> wave counters below
       bool fromStore = false;                                               // STORE: this lane's photon starts here, from its slot
-      if (wantEvent && st != ST_DONE) {
+      if (wantEvent && st != kStDone) {
         rng.begin_event();
         if constexpr (STORE) {
           // (position, cell and optical depth came from the slot in part B; the block just made is the photon's block 0 once more -- the
@@ -1768,13 +1807,13 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
             int next = sm.bottom ? (blackSurface ? ST_EXIT : ST_EVENT) : ST_TRACE;
             next = sm.top ? ST_EXIT : next;
             st = sm.reach ? ST_EVENT : next;
-            if constexpr (!(STEP_FORM & STEP_COLD_ERROR)) st = sm.error ? ST_DROPPED : st;
+            if constexpr (!(STEP_FORM & STEP_COLD_ERROR)) st = sm.error ? kStDropped : st;
           } else if (s != STEP_CONTINUE) {
-            st = s == STEP_DONE ? ST_EVENT : (s == STEP_ERROR ? ST_DROPPED : ((r.iz >= 1 || blackSurface) ? ST_EXIT : ST_EVENT));
+            st = s == STEP_DONE ? ST_EVENT : (s == STEP_ERROR ? kStDropped : ((r.iz >= 1 || blackSurface) ? ST_EXIT : ST_EVENT));
           }
           if constexpr ((STEP_FORM & STEP_COLD_ERROR) != 0) {   // the step's error exit: r.acc = -2 and the dropped state, as the early exit gave them
             if (__builtin_expect(__ballot(sm.error) != 0ull, 0))
-              if (sm.error) { r.acc = -2.0f; st = ST_DROPPED; }
+              if (sm.error) { r.acc = -2.0f; st = kStDropped; }
           }
           s = STEP_CONTINUE;   // (the state is set)
         } else
@@ -1786,7 +1825,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
         if (GENERAL && s == STEP_EXIT) finish_exit(P, r);
         // (an exit through the top, or onto a black surface, ends the photon: such lanes wait for the turnover quorum)
         if (s != STEP_CONTINUE)
-          st = s == STEP_DONE ? ST_EVENT : (s == STEP_ERROR ? ST_DROPPED : ((r.iz >= 1 || blackSurface) ? ST_EXIT : ST_EVENT));
+          st = s == STEP_DONE ? ST_EVENT : (s == STEP_ERROR ? kStDropped : ((r.iz >= 1 || blackSurface) ? ST_EXIT : ST_EVENT));
       }
       PROF_END(PH_STEP, nTracing);
 #ifdef I3RC_PROFILE_PHASES

@@ -87,6 +87,17 @@
 #ifndef I3RC_STEP_COLD_ERROR
 #define I3RC_STEP_COLD_ERROR 1       /* the error exit of the step (no workload takes it) behind one uniform branch, its defaults inside */
 #endif
+// round 16, the same six kernels: the scalar work of the loop's head and of the event phase's masks -- only how a pass is decided is
+// spelt anew, not what is decided; one switch per item, 0 = the kernels of round 15 (profiles/r16_pass_logic.txt)
+#ifndef I3RC_PASS_DECISION
+#define I3RC_PASS_DECISION 1         /* stop, runEvent and doTurn as the bits of one 32-bit scalar: pass_decision.hpp */
+#endif
+#ifndef I3RC_TURN_STATE_RANGE
+#define I3RC_TURN_STATE_RANGE 1      /* the lane states numbered so that the three turnover states end the range: `wantTurn` one compare */
+#endif
+#ifndef I3RC_TURN_ALL_WORD
+#define I3RC_TURN_ALL_WORD 1         /* doTurn as a 64-bit -1 / 0 word made once per event phase: every `mask & turnAll` one s_and_b64 */
+#endif
 #ifndef I3RC_PHOTON_STEP_AHEAD
 #define I3RC_PHOTON_STEP_AHEAD 64   /* off: measured -1.6 % (step cloud) ... +2.8 % (Landsat-36), -3 % on the radar field */
 #endif
