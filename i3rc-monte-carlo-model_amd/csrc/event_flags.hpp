@@ -19,17 +19,21 @@ enum EventFlag : unsigned {
   // A scattering needs the index of its cell: the kernels' `needCell` of a one-component domain -- the cells do not share their
   // single-scattering albedo, or share one below 1 (the absorption is tallied per cell), or do not share their table entry.
   kNeedCell = 4u,
+  // The launch can play Russian roulette: the caller asks for it, and some photon's weight can fall below 1 (kWeightStaysOne is clear).
+  kPlaysRoulette = 8u,
 };
 
 // uniformSsa: >= 0 the value every cell shares, < 0 (or NaN) per-cell values; uniformPf: >= 1 the table entry every cell shares, else 0;
 // brdfGrid: the surface's reflectance is looked up per reflection (DevProblem::useBDRF after a uniform grid has been folded into the
 // albedo); albedo: the Lambertian albedo the kernels multiply by otherwise.
-inline unsigned event_flags(float uniformSsa, int uniformPf, bool brdfGrid, float albedo) {
+// useRoulette: the caller's useRussianRoulette (DevProblem::useRR); the callers from before the bit existed leave it out.
+inline unsigned event_flags(float uniformSsa, int uniformPf, bool brdfGrid, float albedo, bool useRoulette = false) {
   unsigned f = 0u;
   const bool noAbsorption = uniformSsa >= 1.0f;
   if (noAbsorption) f |= kNoAbsorption;
   if (noAbsorption && !brdfGrid && albedo <= FLT_MIN) f |= kWeightStaysOne;
   if (!(uniformSsa >= 0.0f) || uniformSsa < 1.0f || uniformPf < 1) f |= kNeedCell;
+  if (useRoulette && (f & kWeightStaysOne) == 0u) f |= kPlaysRoulette;
   return f;
 }
 

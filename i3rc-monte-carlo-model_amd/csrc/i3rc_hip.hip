@@ -874,7 +874,7 @@ int make_problem(i3rc_hip_integrator *h, const LaunchDecision &d, DevProblem &P,
   // (the path histogram's launches have no radiance directions -- extra_tally_refused --: the pointer carries the bin table, BinTable)
   if (h->extra == EXTRA_PATH_BINS && h->nDir == 0) P.dirCos = (const float *)h->dBins.p;
   P.uniformSsa = h->uniformSsa; P.uniformPf = h->uniformPf;
-  P.eventFlags = event_flags(P.uniformSsa, P.uniformPf, P.useBDRF != 0, P.albedo);
+  P.eventFlags = event_flags(P.uniformSsa, P.uniformPf, P.useBDRF != 0, P.albedo, P.useRR != 0);
   P.tally = tally;
   const TallyView &V = h->view;
   P.oUp = (int)V.fluxUp; P.oDown = (int)V.fluxDown; P.oAbs = (int)V.fluxAbsorbed; P.oVol = (int)V.volumeAbsorption;

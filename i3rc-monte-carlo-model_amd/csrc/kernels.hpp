@@ -530,7 +530,9 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   constexpr bool FLAGS = STORE && I3RC_EVENT_FLAGS != 0;   // the event phase reads launch facts from DevProblem::eventFlags (event_flags.hpp)
   // ... and how their photon step spells its addresses and its outcome (StepForm, tracer.hpp): one switch of tuning.hpp per bit
   constexpr int STEP_FORM = !STORE ? 0 : (I3RC_STEP_BIASED_ADDRESS ? STEP_BIASED : 0) | (I3RC_STEP_STATE_SELECTS ? STEP_MASKS : 0) |
-                                         (I3RC_STEP_COLD_ERROR ? STEP_COLD_ERROR : 0);
+                                         (I3RC_STEP_COLD_ERROR ? STEP_COLD_ERROR : 0) | (I3RC_STEP_ADVANCE_MASKS ? STEP_ADVANCE_MASKS : 0);
+  // ... and (round 17) "this launch can play roulette" as one bit of that word (kPlaysRoulette), made on the host
+  constexpr bool ROULETTE_BIT = FLAGS && I3RC_ROULETTE_FLAG != 0;
   // ... and how the head of their loop decides a pass and hands the decision to the event phase: one switch of tuning.hpp each
   constexpr bool PASS_BITS = STORE && I3RC_PASS_DECISION != 0;   // stop / runEvent / doTurn as bits of one 32-bit scalar (pass_decision.hpp)
   constexpr bool TURN_WORD = STORE && I3RC_TURN_ALL_WORD != 0;   // doTurn as a 64-bit -1 / 0 word made once per event phase
@@ -1669,7 +1671,11 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
                 // the roulette's deviate, compares and count only where the launch can play and some lane of this phase does: the block
                 // had been made unconditional -- the conversion of spare() is three float64 instructions -- and masked afterwards, in
                 // every event phase of launches whose weights never leave 1
-                if (Pe.useRR && (Pe.eventFlags & kWeightStaysOne) == 0u && __ballot(w < 0.5f) != 0ull) {
+                // (ROULETTE_BIT: "can play" is the launch's, made on the host -- kPlaysRoulette -- and one bit test here)
+                bool canPlay;
+                if constexpr (ROULETTE_BIT) canPlay = (Pe.eventFlags & kPlaysRoulette) != 0u;
+                else canPlay = Pe.useRR && (Pe.eventFlags & kWeightStaysOne) == 0u;
+                if (canPlay && __ballot(w < 0.5f) != 0ull) {
                   if (w < 0.5f) {
                     didRoulette = true;
                     if (rng.spare() >= w / 1.0f) w = 0.0f; else w = 1.0f;
@@ -1760,7 +1766,8 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       // (STORE -- ray tracing, one component: a photon with an interaction due scatters unless part A found it at the top or at the surface)
       if constexpr (STORE) wc.scat += (unsigned)__popcll(scMask & ~(topMask | surfMask));
       else wc.scat += count_lanes(didScatter);
-      if constexpr (FLAGS) { if (Pe.useRR && (Pe.eventFlags & kWeightStaysOne) == 0u) wc.roul += count_lanes(didRoulette); }   // (... and whose weights can fall)
+      if constexpr (ROULETTE_BIT) { if ((Pe.eventFlags & kPlaysRoulette) != 0u) wc.roul += count_lanes(didRoulette); }   // (... and whose weights can fall)
+      else if constexpr (FLAGS) { if (Pe.useRR && (Pe.eventFlags & kWeightStaysOne) == 0u) wc.roul += count_lanes(didRoulette); }
       else
       if (!STORE || Pe.useRR) wc.roul += count_lanes(didRoulette);     // (STORE: only a launch that plays roulette pays for the count)
       if constexpr (!BATCHED && !STORE) wc.calls += count_lanes(startedTrace);   // (BATCHED, STORE: a batch's / launch's photon traces = its scatterings + surface arrivals + exits + drops)

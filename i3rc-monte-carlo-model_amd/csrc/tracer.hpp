@@ -603,8 +603,12 @@ __device__ __forceinline__ float cell_extinction_biased(const PR &P, uint32_t ld
 //                    CALLER gives it what the early exit gave -- r.acc = -2 and the dropped state -- behind one wave-uniform branch on
 //                    StepMasks::error, the defaults inside it; the value returned for such a lane means nothing.  Its position and
 //                    indices, which the early exit left alone, are then rubbish too, and nobody reads them: the photon is dropped and
-//                    its lane's next photon sets all of them anew.)
-enum StepForm { STEP_BIASED = 1, STEP_MASKS = 2, STEP_COLD_ERROR = 4 };
+//                    its lane's next photon sets all of them anew.
+//   STEP_ADVANCE_MASKS  "face reached" as `quotient <= adv` instead of `!reach && quotient <= step`: adv is 0 on an arriving lane and
+//                    `step` on every other, and a lane whose step is valid has step > 0 and every non-NaN quotient >= step, so the compare
+//                    is false where the lane arrives and the old one elsewhere (NaN compares false either way; a failed lane is the
+//                    caller's, as above).  The compare's own mask then serves the position's select: no scalar AND with !reach.)
+enum StepForm { STEP_BIASED = 1, STEP_MASKS = 2, STEP_COLD_ERROR = 4, STEP_ADVANCE_MASKS = 8 };
 struct StepMasks { uint32_t ldsBias; bool reach, top, bottom, error; };
 template <int GRID, bool CLEARMAP = false, bool BRANCHY = false, bool SHORT = false, bool LENGTH = false, bool CHAIN = false, bool AXES = false, int FORM = 0, class PR>
 __device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L, Ray &r, bool hasTarget, float *length = nullptr, unsigned *wrapAxes = nullptr,
@@ -684,7 +688,9 @@ __device__ __forceinline__ StepResult trace_step_lazy(const PR &P, const Lds &L,
   r.acc = reach ? rest : r.acc + tauCell;
 
   const float ax = r.x + adv * r.dx, ay = r.y + adv * r.dy, az = r.z + adv * r.dz;
-  const bool hx = !reach && stx <= step, hy = !reach && sty <= step, hz = !reach && stz <= step;   // face reached
+  bool hx, hy, hz;                                                                                 // face reached
+  if constexpr ((FORM & STEP_ADVANCE_MASKS) != 0) { hx = stx <= adv; hy = sty <= adv; hz = stz <= adv; }
+  else { hx = !reach && stx <= step; hy = !reach && sty <= step; hz = !reach && stz <= step; }
   // :1744-1769 the face position itself when the face is reached, else the advanced position; the index moves on
   // when the face is reached or the position ends within 2 spacing() of it
   bool bx, by, bz;

@@ -98,6 +98,15 @@
 #ifndef I3RC_TURN_ALL_WORD
 #define I3RC_TURN_ALL_WORD 1         /* doTurn as a 64-bit -1 / 0 word made once per event phase: every `mask & turnAll` one s_and_b64 */
 #endif
+// round 17, the same six kernels: scalar work that re-derives per phase what the launch decides once, or turns lane masks around with
+// scalar logic another spelling does not need -- no float operation changes; one switch per item, 0 = the kernels of round 16
+// (profiles/r17_scalar_relief.txt)
+#ifndef I3RC_ROULETTE_FLAG
+#define I3RC_ROULETTE_FLAG 1         /* "this launch can play roulette" as the bit kPlaysRoulette of DevProblem::eventFlags, not useRR and a second bit */
+#endif
+#ifndef I3RC_STEP_ADVANCE_MASKS
+#define I3RC_STEP_ADVANCE_MASKS 1    /* the step's face masks as `quotient <= advance` (0 on an arriving lane): no scalar AND with !reach */
+#endif
 #ifndef I3RC_PHOTON_STEP_AHEAD
 #define I3RC_PHOTON_STEP_AHEAD 64   /* off: measured -1.6 % (step cloud) ... +2.8 % (Landsat-36), -3 % on the radar field */
 #endif
