@@ -43,6 +43,7 @@ struct DevBuf {
     if (n) e = hipMemcpy(p, src, n, hipMemcpyHostToDevice);
     return e;
   }
+  void release() { if (p) { (void)hipFree(p); p = nullptr; } bytes = 0; }
   hipError_t alloc(size_t n) {
     if (p) { (void)hipFree(p); p = nullptr; }
     bytes = n;
@@ -75,6 +76,12 @@ struct i3rc_hip_integrator : ProblemFacts {   // (the facts every launch is deci
   DevBuf dXs, dYs, dBrdf;
   float brdf0 = 0.f;          // reflectance of the first surface cell (a 1 x 1 surface grid is a plain Lambertian albedo)
   DevBuf dDir;
+  // the first flight of a zenith sun (first_flight.hpp): the column table, made at the first launch that could use it (first_flight)
+  DevBuf dFlight;                // table[ny * nx][nz + 1]: the optical path after k downward steps from the start height
+  int flightState = 0;           // 0: not made yet, 1: made and fit, 2: no table (its sweep met what makes it unfit, or it is too large)
+  int flightLayer = 0;           // the start layer its kernel found (the photon kernels' izStart)
+  bool flightOn = true;          // i3rc_hip_set_first_flight_table
+  bool lastLanded = false;       // the most recent launch landed its photons from the table (i3rc_hip_last_first_flight)
   DevBuf dBins;                  // the path histogram's table as the kernels read it (BinTable, kernels.hpp): nBins, then the nBins + 1 edges
   std::vector<float> binEdges;   // ... and the edges' host copy (empty while the histogram is off)
 
@@ -669,6 +676,19 @@ int i3rc_hip_set_tuning(i3rc_hip_integrator *h, int evThreshold, int blocksPerCU
   return 0;
 }
 
+/* Test / measurement knob: plain launches of the specialised flux kernels land a zenith sun's photons from the column table (1, the
+ * default) or fly every photon step by step (0); the results are the same word for word.  I3RC_FIRST_FLIGHT_TABLE=0 in the
+ * environment is "off" for the process. */
+int i3rc_hip_set_first_flight_table(i3rc_hip_integrator *h, int on) {
+  if (!h) return 1;
+  drop_lookahead(h);
+  h->flightOn = on != 0;
+  return 0;
+}
+
+/* Test hook: 1 where the most recent launch landed its photons from the column table (the bit kFirstFlight of its eventFlags), else 0. */
+int i3rc_hip_last_first_flight(const i3rc_hip_integrator *h) { return h && h->lastLanded ? 1 : 0; }
+
 int i3rc_hip_set_light_threshold(i3rc_hip_integrator *h, int lanes) {
   if (!h) return 1;
   drop_lookahead(h);
@@ -841,7 +861,9 @@ void fill_geometry(const i3rc_hip_integrator *h, DevProblem &P) {
 }
 
 // The DevProblem of a launch that `d` has decided (not refused).  (stream: where the launch goes, tally: the buffer it adds to)
-int make_problem(i3rc_hip_integrator *h, const LaunchDecision &d, DevProblem &P, hipStream_t stream, double *tally) {
+int first_flight(i3rc_hip_integrator *h, const LaunchDecision &d, DevProblem &P, const RunArgs &A, hipStream_t stream);
+// (A: the launch's source, already uploaded -- what the first flight's eligibility reads of it)
+int make_problem(i3rc_hip_integrator *h, const LaunchDecision &d, DevProblem &P, const RunArgs &A, hipStream_t stream, double *tally) {
   fill_geometry(h, P);
   // (the kernels take the packed form of the decision's place, and no other)
   if (d.place != GRID_COLUMNS && d.place != GRID_COLBASE) P.colRec = nullptr;
@@ -881,7 +903,8 @@ int make_problem(i3rc_hip_integrator *h, const LaunchDecision &d, DevProblem &P,
   P.oInt = (int)V.intensityByComponent; P.oExc = (int)V.intensityExcess; P.oCnt = (int)V.counters;
   P.rayQueueCap = d.rayQueueCap;
   P.ldsTallies = d.ldsTallies; P.ldsVolume = d.ldsVolume; P.ldsIntensity = d.ldsIntensity; P.ldsGrid = d.ldsGrid | (d.ldsBins ? kLdsGridBinSums : 0);
-  return 0;
+  // (last: the bit kFirstFlight of eventFlags and, with it, the column table in dirCos -- first_flight, below)
+  return first_flight(h, d, P, A, stream);
 }
 
 // fluxAbsorbed(ix, iy) of a tally block = the sum of its column's volumeAbsorption (:644-647 add the same increment to both; the kernels
@@ -940,6 +963,71 @@ int upload_source(i3rc_hip_integrator *h, const i3rc_source *src, int64_t n, Run
   return 0;
 }
 
+// THE FIRST FLIGHT (first_flight.hpp): a launch that first_flight_eligible accepts gets the bit kFirstFlight in its eventFlags and the
+// column table in DevProblem::dirCos (a launch of a STORE kernel has no radiance directions: nobody else reads the pointer).
+// The table depends on the domain alone -- the field, the edges, the Directional start height -- and is made ONCE per integrator: at
+// the first launch that could use it, on that launch's stream, not at create.  Create does not know the source: most integrators of
+// an oblique sun, of radiances or of explicit photon streams would pay ncol * (nz + 1) words and a kernel for nothing.  The one wait
+// for the stream (the sweep's verdict decides the launch's bit on the host) falls into a driver's first batch; a driver keeps its
+// integrator for all its batches.  A table beyond kFlightTableMax bytes is not made.
+constexpr size_t kFlightTableMax = (size_t)256 << 20;
+// Makes the table on `stream` and waits for the sweep's verdict.  0: the table is there and `layer` is the start layer its kernel found,
+// `fit` whether a launch may land from it; else a HIP error, the table freed.
+hipError_t make_flight_table(i3rc_hip_integrator *h, const DevProblem &P, hipStream_t stream, int &layer, bool &fit) {
+#if I3RC_FIRST_FLIGHT_TABLE != 0
+  const size_t ncol = (size_t)P.nx * P.ny;
+  DevBuf info;
+  int words[2] = {0, 1};
+  hipError_t e = h->dFlight.alloc(sizeof(float) * ncol * (size_t)(P.nz + 1));
+  if (e == hipSuccess) e = info.alloc(sizeof(words));
+  if (e == hipSuccess) e = hipMemsetAsync(info.p, 0, sizeof(words), stream);
+  if (e == hipSuccess) {
+    const size_t lds = sizeof(float) * (size_t)(P.nx + P.ny + P.nz + 3);
+    hipLaunchKernelGGL(first_flight_table_kernel, dim3((unsigned)((ncol + 255) / 256)), dim3(256), lds, stream, P, (float *)h->dFlight.p, (int *)info.p);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(words, info.p, sizeof(words), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) { h->dFlight.release(); return e; }
+  layer = words[0]; fit = words[1] == 0;
+  return hipSuccess;
+#else
+  (void)h; (void)P; (void)stream; (void)layer; (void)fit;
+  return hipSuccess;
+#endif
+}
+// flightState: 0 no verdict yet -- the next launch that could use the table makes it, also after an attempt that ended in a HIP error
+// (out of memory, say: the launch then flies its photons as before, and nothing stays allocated) --, 1 made and fit, 2 for good no
+// table: too large, or its sweep met what makes it unfit (freed).
+int first_flight(i3rc_hip_integrator *h, const LaunchDecision &d, DevProblem &P, const RunArgs &A, hipStream_t stream) {
+  h->lastLanded = false;
+#if I3RC_FIRST_FLIGHT_TABLE != 0
+  const bool store = d.startStore && P.nDir == 0;
+  if (!h->flightOn || !EnvKnobs::process().firstFlight) return 0;
+  // (everything but the table's own verdict first: no table for a launch that could not use it)
+  if (!first_flight_eligible(store, A.srcKind, A.solarDx, A.solarDy, A.solarDz, 1, P.nx, P.ny, P.nz, true)) return 0;
+  if (h->flightState == 0 && P.totalExt != nullptr) {
+    const size_t bytes = sizeof(float) * (size_t)P.nx * P.ny * (size_t)(P.nz + 1);
+    if (bytes > kFlightTableMax) h->flightState = 2;
+    else {
+      bool fit = false;
+      if (make_flight_table(h, P, stream, h->flightLayer, fit) == hipSuccess) {
+        h->flightState = fit ? 1 : 2;
+        if (!fit) h->dFlight.release();
+      } else (void)hipGetLastError();   // (the error is the table's alone: this launch flies its photons as before, the next one tries again)
+    }
+  }
+  if (first_flight_eligible(store, A.srcKind, A.solarDx, A.solarDy, A.solarDz, h->flightLayer, P.nx, P.ny, P.nz, h->flightState == 1)) {
+    P.eventFlags |= kFirstFlight;
+    h->lastLanded = true;
+    P.dirCos = (const float *)h->dFlight.p;
+  }
+#else
+  (void)h; (void)d; (void)P; (void)A; (void)stream;
+#endif
+  return 0;
+}
+
 // A launch's decision, its DevProblem and its source, in the order a call reports what it refuses: the problem's completeness, the
 // source (upload_source), then LDS.
 int prepare_launch(i3rc_hip_integrator *h, const StreamKind &s, const i3rc_source *src, int64_t n, hipStream_t stream, double *tally,
@@ -948,7 +1036,7 @@ int prepare_launch(i3rc_hip_integrator *h, const StreamKind &s, const i3rc_sourc
   if (!L.d.refusal.empty() && L.d.early) return h->fail(L.d.refusal);
   if (upload_source(h, src, n, A)) return 1;
   if (!L.d.refusal.empty()) return h->fail(L.d.refusal);
-  return make_problem(h, L.d, L.P, stream, tally);
+  return make_problem(h, L.d, L.P, A, stream, tally);
 }
 
 // A production instantiation of photon_kernel: its template arguments after the stream -- the key a launch looks it up by --, the kernel
@@ -1144,6 +1232,10 @@ int launch(i3rc_hip_integrator *h, const Launch &L, const RunArgs &A, hipStream_
     // 0.5 % on the step cloud and 2-5 % on the radar / Landsat cases to the imbalance at the end of a launch.
     static const long long chunkMax = std::max(64ll, env_int("I3RC_CHUNK_MAX", 256));
     B.chunk = (int)std::min<long long>(chunkMax, std::max<long long>(64, A.nPhotons / (blocks * (threads / 64) * 8)));
+    // (a launch that lands first flights keeps a wave's landed steps in thirty bits between two hand-overs of its counters, which
+    // fall at every fourth refill at the latest and earlier once the sum passes 2^29: chunks of at most 2^16 photons of at most 1022
+    // steps keep what four refills add below 2^28 -- I3RC_CHUNK_MAX is a knob without a bound of its own)
+    if ((L.P.eventFlags & kFirstFlight) != 0u) B.chunk = std::min(B.chunk, 1 << 16);
     HIPCHK(h, hipMemsetAsync(A.workCounter, 0, sizeof(unsigned long long), stream));
     return 0;
   });

@@ -31,6 +31,7 @@
 #include "tally_block.hpp"
 #include "event_flags.hpp"
 #include "pass_decision.hpp"
+#include "first_flight.hpp"
 #include "tracer.hpp"
 #include "tuning.hpp"
 
@@ -484,6 +485,8 @@ constexpr int planned_waves() {
 // What a wave of a STORE kernel (below) needs only when it fills its start store, or where a lane takes a photon from it -- the start
 // layer, the reservoir's end, the count of its refills -- as four words of static LDS of the wave's own, instead of scalar registers
 // that the whole photon loop would carry (eight waves per SIMD leave each 96 of them, and the kernels want more: tests/test_build_isa.py).
+// (kRefills, where the kernel lands first flights -- FLIGHT --: the refills modulo four in the low two bits, above them the landed steps
+// since the wave's last hand-over of its counters)
 struct WaveStartState {
   enum Word { kLayer = 0, kEndLo = 1, kEndHi = 2, kRefills = 3, kWords = 4 };
   int *w = nullptr;
@@ -533,6 +536,9 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
                                          (I3RC_STEP_COLD_ERROR ? STEP_COLD_ERROR : 0) | (I3RC_STEP_ADVANCE_MASKS ? STEP_ADVANCE_MASKS : 0);
   // ... and (round 17) "this launch can play roulette" as one bit of that word (kPlaysRoulette), made on the host
   constexpr bool ROULETTE_BIT = FLAGS && I3RC_ROULETTE_FLAG != 0;
+  // ... and (round 18) land a zenith sun's photons at their first event where the wave makes their starts (first_flight.hpp; the bit
+  // kFirstFlight of that word says that the launch does, and DevProblem::dirCos -- a flux launch has no directions -- then carries the table)
+  constexpr bool FLIGHT = STORE && I3RC_FIRST_FLIGHT_TABLE != 0;
   // ... and how the head of their loop decides a pass and hands the decision to the event phase: one switch of tuning.hpp each
   constexpr bool PASS_BITS = STORE && I3RC_PASS_DECISION != 0;   // stop / runEvent / doTurn as bits of one 32-bit scalar (pass_decision.hpp)
   constexpr bool TURN_WORD = STORE && I3RC_TURN_ALL_WORD != 0;   // doTurn as a 64-bit -1 / 0 word made once per event phase
@@ -865,12 +871,19 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
       }
       raysSkipped = 0u;
     }
+    // FLIGHT: the steps of the first flights that the fill landed instead of stepping (WaveStartState::kRefills, its upper thirty bits)
+    uint32_t landedSteps = 0u;
+    if constexpr (FLIGHT) {
+      const unsigned word = (unsigned)__builtin_amdgcn_readfirstlane(startState.w[WaveStartState::kRefills]);
+      landedSteps = word >> 2;
+      startState.w[WaveStartState::kRefills] = (int)(word & 3u);
+    }
     if (!BATCHED && (threadIdx.x & 63) == 0) {   // (BATCHED flux kernels: per lane and batch, see flush_lanes)
       // (STORE: tracer calls are derived, not counted -- every trace ends in exactly one scattering, surface arrival, exit through the
       // top or tracer drop, each counted where the event phase serves it, and every trace has ended when the launch has: over a launch
       // the sum is the number of traces started, which is all the host ever sees of these hand-overs)
       const uint32_t calls = STORE ? wc.scat + wc.surf + wc.top + wc.dropped : wc.calls;
-      const uint32_t c[9] = {wc.photons, wc.dropped, wc.steps, wc.scat, wc.surf, wc.top, wc.roul, wc.shadow, calls};
+      const uint32_t c[9] = {wc.photons, wc.dropped, FLIGHT ? wc.steps + landedSteps : wc.steps, wc.scat, wc.surf, wc.top, wc.roul, wc.shadow, calls};
       const ColdArgs ka = cold_args();
       double *const counters = ka->P.tally + ka->P.oCnt;
 #pragma unroll
@@ -1349,12 +1362,29 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           int need = __popcll(newMask);
           int rank = lanes_below(newMask);
           long long mine = -1;
+          // FLIGHT: the launch lands its photons in the fill (wave-uniform), and what this lane's slot says of its photon -- the landing
+          // layer, 0 for "through the bottom", kFlightNotLanded for a photon that flies as before (first_flight.hpp)
+          // (the code travels in r.iz, which every new photon's start sets anyway: a register of its own was one too many)
+          bool flightLaunch = false;
+          if constexpr (FLIGHT) flightLaunch = (Pe.eventFlags & kFirstFlight) != 0u;
           for (;;) {   // (uniform: from the store; when that is short, a fill -- after a refill where the reservoir is empty -- and the rest)
             const int take = need < startAvail ? need : startAvail;
             if (isNew && mine < 0 && rank >= 0 && rank < take) {
               mine = res.next - startAvail + rank;   // (the store holds the startAvail photons in front of res.next)
+              if constexpr (FLIGHT) {
+                if (flightLaunch) {   // (the same four words, the index word in the landing's packing; a landed slot's last word is its height)
+                  const lds_float *const slot = startSlots + kStartWords * ((unsigned)mine & (unsigned)(kStartSlots - 1));
+                  const int cellWord = __float_as_int(slot[StartSlot::kCell]);
+                  r.x = slot[StartSlot::kX]; r.y = slot[StartSlot::kY]; r.target = slot[StartSlot::kDepth];
+                  r.ix = flight_ix(cellWord); r.iy = flight_iy(cellWord); r.iz = flight_code(cellWord);
+                } else {
+                  const StartSlot::Words s = StartSlot::load(startSlots + kStartWords * ((unsigned)mine & (unsigned)(kStartSlots - 1)));
+                  r.x = s.x; r.y = s.y; r.ix = s.ix; r.iy = s.iy; r.target = s.depth;
+                }
+              } else {
               const StartSlot::Words s = StartSlot::load(startSlots + kStartWords * ((unsigned)mine & (unsigned)(kStartSlots - 1)));
               r.x = s.x; r.y = s.y; r.ix = s.ix; r.iy = s.iy; r.target = s.depth;   // (the rest of the start: part C)
+              }
             }
             startAvail -= take;
             wc.photons += (unsigned)take;                         // numPhotonsProcessed :459
@@ -1364,9 +1394,11 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
             if (res.next >= end) {
               // (the other kernels' test: a reservoir that ends where the launch ends was the last one -- no further visit of the work counter)
               if (end >= cold_args()->A.nPhotons) break;
-              const unsigned refilled = (unsigned)__builtin_amdgcn_readfirstlane(startState.w[WaveStartState::kRefills]) + 1u;
+              unsigned refilled = (unsigned)__builtin_amdgcn_readfirstlane(startState.w[WaveStartState::kRefills]) + 1u;
+              // (FLIGHT: the count modulo four in the word's low two bits, the landed steps since the last hand-over above them)
+              if constexpr (FLIGHT) refilled = ((refilled - 1u) & ~3u) | (refilled & 3u);
               startState.w[WaveStartState::kRefills] = (int)refilled;
-              if ((refilled & 3u) == 0u || wc.steps > 0x40000000u) flush_counters();
+              if ((refilled & 3u) == 0u || wc.steps > 0x40000000u || (FLIGHT && refilled > 0x80000000u)) flush_counters();
               else adapt_thresholds();
               res.refill();
               end = res.end;
@@ -1406,6 +1438,54 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
               }
               StartSlot::store(startSlots + kStartWords * ((unsigned)i & (unsigned)(kStartSlots - 1)), x, y, ci, cj, depth);
             }
+            if constexpr (FLIGHT) {
+              // THE LANDING (first_flight.hpp): a zenith sun's photon goes straight down its start column until its first event, and the
+              // column's table says in which step its optical path passes its depth.  A pass of its own over the slot just written,
+              // read back from LDS: beside the Philox block the search did not fit the registers (fourteen spilled).  Not landed -- the
+              // slot's words as before, the code kFlightNotLanded --: a photon within two spacings of its forward x or y edge (the step's
+              // proximity rule would move its index after the first step and send it down the neighbouring column), and a landed height
+              // that the event phase would not take for a scattering.  The steps the tracer would have counted are summed apart from
+              // the wave's own count, which stays what it executed (adapt_thresholds), and join it where the counters are handed over.
+              if (flightLaunch) {
+                asm volatile("" ::: "memory");   // (the slot's words from LDS, not from the registers that made them)
+                lds_float *const slot = startSlots + kStartWords * (((unsigned)res.next + (threadIdx.x & 63u)) & (unsigned)(kStartSlots - 1));
+                const int cell = __float_as_int(slot[StartSlot::kCell]);
+                const int ci = cell & ((1 << StartSlot::kIyShift) - 1), cj = (int)((unsigned)cell >> StartSlot::kIyShift);
+                unsigned long long nearMask;
+                {
+                  const float x = slot[StartSlot::kX], y = slot[StartSlot::kY];
+                  nearMask = __ballot((fabsf(L.xE[ci] - x) <= two_spacingf(x)) | (fabsf(L.yE[cj] - y) <= two_spacingf(y)));
+                }
+                const auto &Pf = cold_args()->P;
+                const float depth = slot[StartSlot::kDepth];
+                const float *const table = Pf.dirCos;
+                const unsigned row = (__umul24((unsigned)(cj - 1), (unsigned)Pf.nx) + (unsigned)(ci - 1)) * (unsigned)(Pf.nz + 1);
+                const int layer0 = __builtin_amdgcn_readfirstlane(startState.w[WaveStartState::kLayer]);
+                const float zTop = Pf.zMax;
+                const float zFrom = Pf.z0 + (1.0f - spacingf(1.0f)) * (zTop - Pf.z0);
+                const FlightLanding f = first_flight_landing(
+                    [table, row](int k) { return *(const float *)((const char *)table + ((row + (unsigned)k) << 2)); }, [&](int iz) { return cell_extinction<GRID>(Pf, L, ci, cj, iz); }, L.zE, zFrom,
+                    layer0, -1.0f, depth, [](float rest, float e) {   // (finish_arrival's quotient)
+                      float part = exact_div(rest, e, refined_rcp(e));
+                      if (__builtin_expect(e < 1e-20f, 0)) part = rest / e;
+                      return part;
+                    });
+                const bool bottom = f.layer == kFlightBottom;
+                const bool lands = !__builtin_amdgcn_inverse_ballot_w64(nearMask) && (bottom || first_flight_lands(f.z, surfaceZ, zTop));
+                slot[StartSlot::kCell] = __int_as_float(flight_pack(ci, cj, lands ? f.layer : kFlightNotLanded));
+                if (lands && !bottom) slot[StartSlot::kDepth] = f.z;
+                // (the wave's sum bit by bit from ballots -- a lane's steps are at most kFlightMaxLayers, ten bits --, a scalar: a shuffle
+                // reduction's six lane addresses were hoisted out of the photon loop into six vector registers of their own)
+                const uint32_t mySteps = lands && (int)(threadIdx.x & 63) < n ? (uint32_t)f.steps : 0u;   // (only photons that exist)
+                uint32_t landedSteps = 0u;
+                static_assert(kFlightMaxLayers < (1 << 10), "a lane's landed steps fit ten bits");
+#pragma unroll
+                for (int b = 0; b < 10; ++b) landedSteps += (uint32_t)__popcll(__ballot(((mySteps >> b) & 1u) != 0u)) << b;
+                // (kept in the upper thirty bits of the wave's refill word -- the refills are counted modulo four -- and handed over with the
+                // wave's counters: one atomic per fill, from every wave of the chip on the counters' one line, cost the step cloud 17 %)
+                startState.w[WaveStartState::kRefills] = (int)((unsigned)__builtin_amdgcn_readfirstlane(startState.w[WaveStartState::kRefills]) + (landedSteps << 2));
+              }
+            }
             __builtin_amdgcn_wave_barrier();   // (the slots are read by other lanes of this wave: no reordering across the fill)
             res.next += n;
             startAvail = n;
@@ -1413,6 +1493,30 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           if (isNew) {
             if (mine < 0) st = kStDone;
             else RngInit<Rng>::start(rng, Ae, mine);
+          }
+          if constexpr (FLIGHT) {
+            // A lane that takes a LANDED photon: the photon stands where its first flight ended.  Its stream goes on with block 1 --
+            // block 0's three deviates (position, depth) were the fill's and are counted here -- so that the block part C makes in this
+            // same phase is its first scattering's, and the lane scatters now, as ST_EVENT; a photon that crossed the whole column is
+            // what the step leaves below the grid -- layer 0, ST_EXIT over a black surface, else ST_EVENT -- and sits this phase's
+            // part C out: finish_exit and part A serve it at its next visit.  Neither enters the ST_TRACE arm for its first flight.
+            // (These scatterings are not in the head's scMask: counted here, from the one compare's mask.)
+            if (flightLaunch) {
+              const bool taken = isNew && mine >= 0;
+              const bool landed = taken && r.iz != kFlightNotLanded;
+              const bool scatters = taken && (unsigned)(r.iz - 1) < (unsigned)(kFlightNotLanded - 1);
+              wc.scat += (unsigned)__popcll(__ballot(scatters));
+              if (landed) {
+                rng.block = 1u;
+                rng.count_draws(3u);
+                r.dx = Ae.solarDx; r.dy = Ae.solarDy; r.dz = Ae.solarDz;
+                order = 0;
+                w = 1.0f;
+                r.z = r.target; r.target = 0.0f;   // (the slot's last word: the landed height; no arrival is pending)
+                st = scatters ? ST_EVENT : (blackSurface ? ST_EXIT : ST_EVENT);
+                wantEvent = scatters;
+              }
+            }
           }
         }
       } else
@@ -1958,6 +2062,56 @@ __global__ void __launch_bounds__(256) trace_rays_kernel(const DevProblem P, lon
   tau[i] = r.acc;
   steps[i] = ns;
 }
+
+#if I3RC_FIRST_FLIGHT_TABLE != 0
+// The column table of the first flight (first_flight.hpp): table[column][k], k = 0 .. nz, the optical path after k downward steps from
+// the Directional start height, one thread per column -- by the tracer's own step from the kernels' own start state (x and y at the
+// cell's centre: with dx = dy = 0 nothing of the step reads them but the proximity rule), towards a target it never reaches, so that the
+// sums are the photon kernels' by construction.  info[0]: the start layer (the kernels' izStart); info[1] != 0: some sweep met what
+// makes the table unfit -- a start layer outside the grid, a step that failed (step <= 0, a NaN), an index that moved sideways or not
+// down by one, a sum that fell or is not finite -- and no launch may land photons from it.  Entries beyond the start layer repeat the
+// last sum (never read).  The field is read in its plain form (DevProblem::totalExt), whatever place the photon kernels read it at:
+// every packed form gives the field's words back bit for bit.
+__global__ void __launch_bounds__(256) first_flight_table_kernel(const DevProblem P, float *table, int *info) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  Lds L;
+  L.xE = (lds_float *)smem; L.yE = L.xE + P.nx + 1; L.zE = L.yE + P.ny + 1;
+  L.tUp = L.tDown = L.tVol = nullptr; L.dirCos = nullptr; L.ext = nullptr;
+  for (int i = threadIdx.x; i <= P.nx; i += blockDim.x) L.xE[i] = P.xE[i];
+  for (int i = threadIdx.x; i <= P.ny; i += blockDim.x) L.yE[i] = P.yE[i];
+  for (int i = threadIdx.x; i <= P.nz; i += blockDim.x) L.zE[i] = P.zE[i];
+  __syncthreads();
+  const int col = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (col >= P.nx * P.ny) return;
+  const float zStart = P.z0 + (1.0f - spacingf(1.0f)) * (P.zMax - P.z0);
+  int izStart = 1;
+  find_z<true>(P, L, zStart, izStart);
+  if (col == 0) info[0] = izStart;
+  float *const row = table + (size_t)col * (size_t)(P.nz + 1);
+  bool bad = izStart < 1 || izStart > P.nz;
+  float last = 0.0f;
+  row[0] = 0.0f;
+  int k = 1;
+  if (!bad) {
+    const int ix = col % P.nx + 1, iy = col / P.nx + 1;
+    Ray r;
+    r.x = 0.5f * (L.xE[ix - 1] + L.xE[ix]); r.y = 0.5f * (L.yE[iy - 1] + L.yE[iy]); r.z = zStart;
+    r.dx = 0.0f; r.dy = 0.0f; r.dz = -1.0f;
+    r.ix = ix; r.iy = iy; r.iz = izStart;
+    r.set_direction(L);
+    r.acc = 0.0f; r.target = kHuge;
+    for (; k <= izStart; ++k) {
+      const StepResult s = trace_step_lazy<GRID_GLOBAL>(P, L, r, true);
+      const bool ok = s == (k < izStart ? STEP_CONTINUE : STEP_EXIT) && r.iz == izStart - k && r.ix == ix && r.iy == iy && r.acc >= last && r.acc < kHuge;
+      if (!ok) { bad = true; break; }
+      last = r.acc;
+      row[k] = last;
+    }
+  }
+  for (; k <= P.nz; ++k) row[k] = last;
+  if (bad) atomicOr(&info[1], 1);
+}
+#endif
 
 // Test hook: exact_div / exact_sqrt against the IEEE operations they replace.
 __global__ void arith_check_kernel(long long n, const float *num, const float *den, unsigned long long *mismatch) {

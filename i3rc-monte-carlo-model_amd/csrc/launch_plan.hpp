@@ -38,9 +38,10 @@ struct EnvKnobs {
   int fusedPlaces = 11;      // I3RC_FUSED_TABLE_LDS_PLACES
   bool direct = true;        // I3RC_DIRECT=0 keeps the event ring for one radiance direction too
   bool cellRecords = true;   // I3RC_CELL_RECORDS (DevProblem::cellRec; 0: the kernels read the plain arrays)
+  bool firstFlight = true;   // I3RC_FIRST_FLIGHT_TABLE=0: no launch lands its photons from the column table (first_flight.hpp); no plan reads it
   static const EnvKnobs &process() {
     static const EnvKnobs k{env_on("I3RC_COLUMNS"), env_on("I3RC_LDS_TALLIES"), env_on("I3RC_TABLE_LDS"), (int)env_int("I3RC_TABLE_LDS_PLACES", 11),
-                            (int)env_int("I3RC_FUSED_TABLE_LDS_PLACES", 11), env_on("I3RC_DIRECT"), env_on("I3RC_CELL_RECORDS")};
+                            (int)env_int("I3RC_FUSED_TABLE_LDS_PLACES", 11), env_on("I3RC_DIRECT"), env_on("I3RC_CELL_RECORDS"), env_on("I3RC_FIRST_FLIGHT_TABLE")};
     return k;
   }
 };

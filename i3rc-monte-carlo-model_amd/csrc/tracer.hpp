@@ -83,6 +83,11 @@ struct DevProblem {
   // switches
   int useRayTracing, useRR, nDir, useHybrid, numOrdersOrig, useRRI, limitContrib;
   float zetaMin, maxContrib, maxExt;
+  // ONE pointer, three users, never two in one launch -- whoever adds a reader of it in a flux kernel has all three to keep apart:
+  //   radiance launches (nDir > 0): the directions, [nDir][3], staged to LDS by every workgroup (3 * nDir words: none of a flux launch);
+  //   path-histogram launches (photon_kernel<PhiloxBinStream, ...>, nDir == 0): the bin table (BinTable, kernels.hpp);
+  //   plain launches of a STORE kernel whose eventFlags carry kFirstFlight (nDir == 0, no extra tally): the first flight's column
+  //   table, [ny * nx][nz + 1] (first_flight.hpp; first_flight in i3rc_hip.hip sets bit and pointer together, and only there).
   const float *dirCos;                // [nDir][3] (global; staged to LDS)
   // single-component shortcuts (specialised kernel): a value every cell shares is passed in the kernarg segment
   float uniformSsa;                   // >= 0: ssa of every cell of component 1; < 0: per-cell values differ

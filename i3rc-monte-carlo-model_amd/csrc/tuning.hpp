@@ -107,6 +107,13 @@
 #ifndef I3RC_STEP_ADVANCE_MASKS
 #define I3RC_STEP_ADVANCE_MASKS 1    /* the step's face masks as `quotient <= advance` (0 on an arriving lane): no scalar AND with !reach */
 #endif
+// round 18, the same six kernels: the first flight of a zenith sun's photons -- straight down their start column -- from a table of the
+// column's cumulative optical path, looked up where the wave makes its photons' starts (first_flight.hpp; photon_kernel, FLIGHT); 0 = the
+// kernels of round 17.  One build runs a launch both ways: I3RC_FIRST_FLIGHT_TABLE=0 in the environment, or
+// i3rc_hip_set_first_flight_table (profiles/r18_first_flight.txt)
+#ifndef I3RC_FIRST_FLIGHT_TABLE
+#define I3RC_FIRST_FLIGHT_TABLE 1
+#endif
 #ifndef I3RC_PHOTON_STEP_AHEAD
 #define I3RC_PHOTON_STEP_AHEAD 64   /* off: measured -1.6 % (step cloud) ... +2.8 % (Landsat-36), -3 % on the radar field */
 #endif

@@ -646,6 +646,10 @@ class Integrator:
             return "?"
         return self._lib.i3rc_hip_last_kernel_name(self._h).decode()
 
+    def first_flight_landed(self):
+        """Did the most recent launch land its photons from the first-flight table (i3rc_hip_last_first_flight)?"""
+        return hasattr(self._lib, "i3rc_hip_last_first_flight") and bool(self._lib.i3rc_hip_last_first_flight(self._h))
+
     def last_plan(self):
         """The plan of the most recent launch (i3rc_hip_last_plan) as a dict of B.PLAN_NAMES; every value -1 before the first.  While the
         path histogram is on, also B.PLAN_BIN_NAME: its sums in LDS (1) or in global memory (0)."""
@@ -708,8 +712,9 @@ class Integrator:
     # -- test hooks
     KERNELS = {"auto": 0, "general": 1, "lane": 2, "ring": 3}
 
-    def set_tuning(self, evThreshold=0, blocksPerCU=0, forceGeneral=None, kernel=None, lightThreshold=None):
-        """Experiment knobs of the C ABI (i3rc_hip_set_tuning / i3rc_hip_select_kernel); kernel is one of KERNELS."""
+    def set_tuning(self, evThreshold=0, blocksPerCU=0, forceGeneral=None, kernel=None, lightThreshold=None, firstFlightTable=None):
+        """Experiment knobs of the C ABI (i3rc_hip_set_tuning / i3rc_hip_select_kernel); kernel is one of KERNELS.
+        firstFlightTable: land a zenith sun's photons from the column table (True, the library's default) or not (False)."""
         self._check(self._lib.i3rc_hip_set_tuning(self._h, int(evThreshold), int(blocksPerCU)), "set_tuning")
         if forceGeneral is not None:
             self._check(self._lib.i3rc_hip_force_general_kernel(self._h, int(bool(forceGeneral))), "set_tuning")
@@ -717,6 +722,8 @@ class Integrator:
             self._check(self._lib.i3rc_hip_select_kernel(self._h, self.KERNELS[kernel]), "set_tuning")
         if lightThreshold is not None:
             self._check(self._lib.i3rc_hip_set_light_threshold(self._h, int(lightThreshold)), "set_tuning")
+        if firstFlightTable is not None:
+            self._check(self._lib.i3rc_hip_set_first_flight_table(self._h, int(bool(firstFlightTable))), "set_tuning")
 
     GRID_PLACES = {"auto": 0, "linear": 1, "bricks": 2, "columns": 3}
 

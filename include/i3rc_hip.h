@@ -509,6 +509,12 @@ int i3rc_hip_set_tuning(i3rc_hip_integrator *h, int evThreshold, int blocksPerCU
 /* ... and lanes whose local-estimate (shadow) ray has ended before the wavefront runs its light phase (1..64;
  * 0 = default: adapted to the length of the rays, 70 / sqrt(steps per ray) within 16..32; radiance runs only). */
 int i3rc_hip_set_light_threshold(i3rc_hip_integrator *h, int lanes);
+/* ... and whether plain launches of the specialised flux kernels land the photons of a zenith sun at their first event from a table
+ * of each column's cumulative optical path (1, the default) or trace every first flight step by step (0): the same results word for
+ * word, counters included.  I3RC_FIRST_FLIGHT_TABLE=0 in the environment switches the table off for the process. */
+int i3rc_hip_set_first_flight_table(i3rc_hip_integrator *h, int on);
+/* Test hook: 1 where the most recent launch landed its photons from that table, else 0. */
+int i3rc_hip_last_first_flight(const i3rc_hip_integrator *h);
 
 /* A Directional batch longer than this many photons is cut into several kernel launches over consecutive photon
  * ranges (same result: every photon has its own random stream).  0 = default, 2^22 photons per compute unit (about

@@ -74,6 +74,35 @@ def run(g, case, place, tbl, general=False):
     return res
 
 
+# ---- launches whose weights only halve (absorption without roulette): the rules tests/test_gpu_scalar_relief.py states in its text,
+# here for the tests that share them (tests/test_gpu_first_flight.py).  A launch is (surface albedo, roulette, photons, ...), a
+# setting (domain, single-scattering albedo, ...).
+RERUNS = 3                       # runs of the general kernel where a launch's sums may depend on the order
+MAX_SPREAD = 16 * 2.0 ** -52     # what the reference's own runs may differ by, relative, in any word
+
+
+def weights_only_halve(setting, launch):
+    """absorption and no roulette: weights that halve without end"""
+    return setting[1] == 0.5 and not launch[1]
+
+
+def provably_exact(launch, counters):
+    """every partial sum of every tally word of the launch fits a float64: addends 2^-j with j <= scatterings + surfaceHits + 1 of
+    the whole launch, no word above 2 photons"""
+    return counters["scatterings"] + counters["surfaceHits"] + 1 + np.log2(2.0 * launch[2]) <= 53
+
+
+def spread_of(runs):
+    """largest relative difference of a word among runs of one launch; 0.0: equal word for word"""
+    worst = 0.0
+    for i in range(len(runs)):
+        for j in range(i):
+            bad = runs[i] != runs[j]
+            if bad.any():
+                worst = max(worst, float((np.abs(runs[i] - runs[j])[bad] / np.maximum(np.abs(runs[i][bad]), np.abs(runs[j][bad]))).max()))
+    return worst
+
+
 def main():
     out = {}
     for case in CASES:
