@@ -32,6 +32,7 @@ SYMBOLS = [
     "i3rc_hip_set_actinic_flux", "i3rc_hip_get_actinic_flux_layout", "i3rc_hip_normalise_actinic_flux",
     "i3rc_hip_set_path_lengths", "i3rc_hip_get_path_length_layout", "i3rc_hip_normalise_path_lengths",
     "i3rc_hip_set_path_histogram", "i3rc_hip_get_path_histogram_layout", "i3rc_hip_normalise_path_histogram",
+    "i3rc_hip_set_radiance_path_lengths", "i3rc_hip_get_radiance_path_length_layout", "i3rc_hip_normalise_radiance_path_lengths",
     "i3rc_hip_problem_facts", "i3rc_hip_plan_launch",
     "i3rc_hip_run_batches_diagnostic_moments", "i3rc_hip_get_diagnostic_moments_layout", "i3rc_hip_diagnostic_moments_layout_words",
     "i3rc_hip_set_path_spectrum", "i3rc_hip_get_path_moments_layout", "i3rc_hip_path_moments_layout_words", "i3rc_hip_run_batches_path_moments",
@@ -65,7 +66,7 @@ class MomentsLayout(C.Structure):
 
 # i3rc_diagnostic_moments_layout; without its first word, the words of i3rc_hip_diagnostic_moments_layout_words in order
 DIAGNOSTIC_MOMENTS_NAMES = ["levelFluxUp", "levelFluxDown", "meanLevelFluxUp", "meanLevelFluxDown", "actinicFlux", "meanActinicFlux", "total"]
-EXTRA_KINDS = {"none": 0, "levels": 1, "tracks": 2, "paths": 3, "bins": 4}   # (csrc/tally_block.hpp, ExtraTally; path lengths and the path histogram have their batch moments in a layout of their own, path_moments_layout below)
+EXTRA_KINDS = {"none": 0, "levels": 1, "tracks": 2, "paths": 3, "bins": 4, "radiance_paths": 5}   # (the radiance path lengths have no batch moments yet; csrc/tally_block.hpp, ExtraTally; path lengths and the path histogram have their batch moments in a layout of their own, path_moments_layout below)
 MAX_PATH_BINS = 1024   # (csrc/tally_block.hpp, kMaxPathBins)
 
 
@@ -121,7 +122,7 @@ SETUP_NAMES = ["nDir", "inverseTables", "forwardTables", "inverseSteps", "invers
                "surfaceNy", "surfaceSet", "extra", "kernelVariant", "gridPlace", "ldsTalliesOn"]
 ENV_DEFAULTS = {"I3RC_COLUMNS": 1, "I3RC_LDS_TALLIES": 1, "I3RC_TABLE_LDS": 1, "I3RC_TABLE_LDS_PLACES": 11, "I3RC_FUSED_TABLE_LDS_PLACES": 11,
                 "I3RC_DIRECT": 1, "I3RC_CELL_RECORDS": 1}
-STREAM_KINDS = {"plain": 0, "fused": 1, "replay": 2, "level": 3, "track": 4, "path": 5, "bins": 6}
+STREAM_KINDS = {"plain": 0, "fused": 1, "replay": 2, "level": 3, "track": 4, "path": 5, "bins": 6, "radiance_path": 7}
 PLAN_EXTRA_NAMES = ["ldsEstimate", "rayQueueCap", "threads"]
 
 
@@ -265,6 +266,10 @@ def load():
         L.i3rc_hip_set_path_histogram.argtypes = [H, C.c_int, fp]
         L.i3rc_hip_get_path_histogram_layout.argtypes = [H, lp, lp, lp, lp, lp, lp]
         L.i3rc_hip_normalise_path_histogram.argtypes = [H, dp, fp, fp, fp, fp]
+    if hasattr(L, "i3rc_hip_set_radiance_path_lengths"):   # (likewise)
+        L.i3rc_hip_set_radiance_path_lengths.argtypes = [H, C.c_int]
+        L.i3rc_hip_get_radiance_path_length_layout.argtypes = [H, lp, lp, lp]
+        L.i3rc_hip_normalise_radiance_path_lengths.argtypes = [H, dp, fp, fp]
     if hasattr(L, "i3rc_hip_plan_launch"):   # (likewise)
         L.i3rc_hip_problem_facts.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, fp, fp, ip, ip, ip, C.c_int]
         L.i3rc_hip_plan_launch.argtypes = [ip, ip, ip, ip, ip, C.c_int, C.c_char_p, C.c_int]

@@ -76,6 +76,7 @@ struct i3rc_hip_integrator : ProblemFacts {   // (the facts every launch is deci
   DevBuf dXs, dYs, dBrdf;
   float brdf0 = 0.f;          // reflectance of the first surface cell (a 1 x 1 surface grid is a plain Lambertian albedo)
   DevBuf dDir;
+  std::vector<float> dirHost;   // the directions as set (the radiance path tally refuses a launch with a direction that does not point upwards)
   // the first flight of a zenith sun (first_flight.hpp): the column table, made at the first launch that could use it (first_flight)
   DevBuf dFlight;                // table[ny * nx][nz + 1]: the optical path after k downward steps from the start height
   int flightState = 0;           // 0: not made yet, 1: made and fit, 2: no table (its sweep met what makes it unfit, or it is too large)
@@ -241,7 +242,8 @@ static const ExtraWords kExtraWords[] = {
     {"i3rc_hip_set_level_fluxes", "level fluxes", "are", "need", "them", "their", "the level fluxes'"},
     {"i3rc_hip_set_actinic_flux", "the actinic flux", "is", "needs", "it", "its", "the actinic flux's"},
     {"i3rc_hip_set_path_lengths", "path lengths", "are", "need", "them", "their", "the path lengths'"},
-    {"i3rc_hip_set_path_histogram", "the path histogram", "is", "needs", "it", "its", "the path histogram's"}};
+    {"i3rc_hip_set_path_histogram", "the path histogram", "is", "needs", "it", "its", "the path histogram's"},
+    {"i3rc_hip_set_radiance_path_lengths", "radiance path lengths", "are", "need", "them", "their", "the radiance path lengths'"}};
 
 // Switches one kind of the optional diagnostic tally on or off (i3rc_hip_set_level_fluxes, i3rc_hip_set_actinic_flux, i3rc_hip_set_path_lengths,
 // i3rc_hip_set_path_histogram -- whose block is sized by nBins: switching it on while it is on lays the block out anew, cleared).
@@ -553,7 +555,9 @@ int i3rc_hip_set_directions(i3rc_hip_integrator *h, int nDir, const float *dirCo
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (nDir > 0) HIPCHK(h, hipMemcpy(h->dDir.p, dirCos, sizeof(float) * 3 * nDir, hipMemcpyHostToDevice));
   h->nDir = nDir;
-  if (changed) return realloc_tally(h);
+  h->dirHost.clear();
+  if (nDir > 0) h->dirHost.assign(dirCos, dirCos + 3 * nDir);
+  if (changed) return realloc_tally(h);   // (the radiance path block is sized by nDir: laid out anew with the radiance fields)
   return 0;
 }
 
@@ -618,6 +622,16 @@ int i3rc_hip_get_path_length_layout(const i3rc_hip_integrator *h, int64_t *up1, 
   if (up2) *up2 = h->view.pathUp2;
   if (down1) *down1 = h->view.pathDown1;
   if (down2) *down2 = h->view.pathDown2;
+  if (total) *total = h->layout.total;
+  return 0;
+}
+
+int i3rc_hip_set_radiance_path_lengths(i3rc_hip_integrator *h, int on) { return set_extra_tally(h, EXTRA_RADIANCE_PATHS, on != 0); }
+
+int i3rc_hip_get_radiance_path_length_layout(const i3rc_hip_integrator *h, int64_t *path1, int64_t *path2, int64_t *total) {
+  if (!h) return 1;
+  if (path1) *path1 = h->view.radiancePath1;
+  if (path2) *path2 = h->view.radiancePath2;
   if (total) *total = h->layout.total;
   return 0;
 }
@@ -1055,6 +1069,7 @@ constexpr const char *rng_name() {
   else if constexpr (Rng::kExtra == EXTRA_TRACKS) return "PhiloxTrackStream";
   else if constexpr (Rng::kExtra == EXTRA_PATHS) return "PhiloxPathStream";
   else if constexpr (Rng::kExtra == EXTRA_PATH_BINS) return "PhiloxBinStream";
+  else if constexpr (Rng::kExtra == EXTRA_RADIANCE_PATHS) return "PhiloxRadiancePathStream";
   else if constexpr (Rng::kReplay) return "ReplayStream";
   else if constexpr (Rng::kBatched) return "PhiloxBatchStream";
   else return "PhiloxStream";
@@ -1084,7 +1099,9 @@ template <class Rng>
 const std::vector<KernelEntry> &stream_kernels() {
   static const std::vector<KernelEntry> list = [] {
     std::vector<KernelEntry> v;
-    if constexpr (Rng::kExtra != EXTRA_NONE) {   // an extra tally block: the general flux kernel, at every place
+    if constexpr (Rng::kExtra == EXTRA_RADIANCE_PATHS) {   // the radiance path tally: the general radiance kernel, at every place
+      add<Rng, true, true, false, false, false>(v, AllPlaces{});
+    } else if constexpr (Rng::kExtra != EXTRA_NONE) {   // an extra tally block: the general flux kernel, at every place
       add<Rng, false, true, false, false, false>(v, AllPlaces{});
     } else if constexpr (Rng::kBatched) {   // fused multi-batch launches
       add<Rng, false, false, false, false, false>(v, NoColbase{});   // flux, the common class
@@ -1126,10 +1143,28 @@ std::string no_bin_moments_text() {
   return "the path histogram has no batch statistics; the diagnostic moments' layout has no slot for it (switch it off, or call "
          "i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch; i3rc_hip_run_batches_path_moments gathers them in a layout of its own)";
 }
+// (nor have the radiance path lengths, yet)
+std::string no_radiance_path_moments_text() {
+  return "radiance path lengths have no batch statistics yet; no moments layout has a slot for them (switch them off, or call "
+         "i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)";
+}
 int extra_tally_refused(i3rc_hip_integrator *h, const char *who, bool batches) {
   if (h->extra == EXTRA_NONE) return 0;
   const ExtraWords &w = kExtraWords[h->extra];
   const std::string subject = std::string(who) + ": " + w.noun + " ";
+  if (h->extra == EXTRA_RADIANCE_PATHS) {   // the one kind of the general RADIANCE kernel
+    if (batches)
+      return h->fail(subject + "have no batch statistics yet and are tallied by plain launches only; fused or announced batches cannot give them "
+                               "(switch them off, or call i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)");
+    if (h->nDir < 1) return h->fail(subject + "are tallied by radiance launches only; no radiance direction is set (nDir = 0)");
+    for (int d = 0; d < h->nDir; ++d)
+      if (!(h->dirHost[3 * (size_t)d + 2] > 0.0f))
+        return h->fail(subject + "need upward radiance directions; direction " + std::to_string(d + 1) + " has uz <= 0 (its rays never reach the top)");
+    if (!traced(*h)) return h->fail(subject + "need ray tracing; max cross-section is in use (useRayTracing = 0)");
+    if (h->params.limitIntensityContributions)
+      return h->fail(subject + "cannot follow limited contributions; the redistributed excess has no path (limitIntensityContributions = 1)");
+    return 0;
+  }
   if (batches)
     return h->fail(subject + w.are + " tallied by plain launches only; fused or announced batches cannot give " + w.them + " (switch " + w.them +
                    " off, or call i3rc_hip_launch_batch / i3rc_hip_compute_batch per batch)");
@@ -1778,6 +1813,7 @@ int begin_batch_loop(i3rc_hip_integrator *h, const std::string &who, bool argsOk
   if (!h) return 1;
   if (!argsOk) return h->fail(who + ": bad arguments");
   if (paths) {
+    if (h->extra == EXTRA_RADIANCE_PATHS) return h->fail(who + ": " + no_radiance_path_moments_text());
     if (h->extra != EXTRA_PATHS && h->extra != EXTRA_PATH_BINS)
       return h->fail(who + ": no path tally is switched on (i3rc_hip_set_path_lengths or i3rc_hip_set_path_histogram first; "
                      "i3rc_hip_run_batches_diagnostic_moments serves the other diagnostic tallies)");
@@ -1788,6 +1824,7 @@ int begin_batch_loop(i3rc_hip_integrator *h, const std::string &who, bool argsOk
                    "i3rc_hip_run_batches_moments serves a loop without one)");
   if (diagnostic && h->extra == EXTRA_PATHS) return h->fail(who + ": " + no_path_moments_text());
   if (diagnostic && h->extra == EXTRA_PATH_BINS) return h->fail(who + ": " + no_bin_moments_text());
+  if (h->extra == EXTRA_RADIANCE_PATHS) return h->fail(who + ": " + no_radiance_path_moments_text());   // (every loop: fused, moments, diagnostic)
   if (src->kind != 0) return h->fail(who + ": Directional photon streams only (explicit streams differ from batch to batch)");
   if (nPhotons <= 0) return h->fail((diagnostic || paths ? who + ": " : "") + "setIllumination: must ask for non-negative number of photons.");
   if (extra_tally_refused(h, who.c_str(), !diagnostic && !paths)) return 1;
@@ -1906,6 +1943,8 @@ int i3rc_hip_get_diagnostic_moments_layout(const i3rc_hip_integrator *h, i3rc_di
   if (!h || !layout) return 1;
   if (h->extra == EXTRA_PATHS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_get_diagnostic_moments_layout: " + no_path_moments_text());
   if (h->extra == EXTRA_PATH_BINS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_get_diagnostic_moments_layout: " + no_bin_moments_text());
+  if (h->extra == EXTRA_RADIANCE_PATHS)
+    return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_get_diagnostic_moments_layout: " + no_radiance_path_moments_text());
   const ExtraMomentsLayout L = extra_moments_layout(h->extra, h->nx, h->ny, h->nz);
   layout->kind = (int64_t)h->extra;
   layout->levelFluxUp = L.levelFluxUp; layout->levelFluxDown = L.levelFluxDown; layout->meanLevelFluxUp = L.meanLevelFluxUp;
@@ -1938,6 +1977,8 @@ int i3rc_hip_path_moments_layout_words(int kind, int nx, int ny, int nBins, int 
 
 int i3rc_hip_get_path_moments_layout(const i3rc_hip_integrator *h, i3rc_path_moments_layout *layout) {
   if (!h || !layout) return 1;
+  if (h->extra == EXTRA_RADIANCE_PATHS)
+    return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_get_path_moments_layout: " + no_radiance_path_moments_text());
   if (h->extra != EXTRA_PATHS && h->extra != EXTRA_PATH_BINS)
     return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_get_path_moments_layout: no path tally is switched on");
   layout->kind = (int64_t)h->extra;
@@ -2090,7 +2131,7 @@ int i3rc_hip_run_replay(i3rc_hip_integrator *h, int64_t nPhotons, const i3rc_sou
                         int32_t *fateOrder, int32_t *drawsUsed) {
   if (!h) return 1;
   if (!src || !randoms || !drawStart || nPhotons <= 0) return h->fail("i3rc_hip_run_replay: bad arguments");
-  if (h->extra == EXTRA_TRACKS || h->extra == EXTRA_PATHS || h->extra == EXTRA_PATH_BINS) {
+  if (h->extra == EXTRA_TRACKS || h->extra == EXTRA_PATHS || h->extra == EXTRA_PATH_BINS || h->extra == EXTRA_RADIANCE_PATHS) {
     const ExtraWords &w = kExtraWords[h->extra];
     return h->fail(std::string("i3rc_hip_run_replay: ") + w.noun + " " + w.are + " tallied by the production stream's kernels only; the replay build has no such kernel (switch " +
                    w.them + " off)");
@@ -2335,6 +2376,18 @@ int i3rc_hip_normalise_path_lengths(const i3rc_hip_integrator *h, const double *
   return 0;
 }
 
+int i3rc_hip_normalise_radiance_path_lengths(const i3rc_hip_integrator *h, const double *t, float *radiancePathLength, float *radiancePathLengthSquared) {
+  if (!h || !t) return 1;
+  if (h->extra != EXTRA_RADIANCE_PATHS)
+    return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_radiance_path_lengths: radiance path lengths are not switched on");
+  const TallyView &V = h->view;
+  const size_t n = (size_t)h->nDir * h->nx * h->ny;
+  float *const out[2] = {radiancePathLength, radiancePathLengthSquared};   // (as the block is laid out)
+  for (int f = 0; f < 2; ++f)
+    for (size_t e = 0; out[f] && e < n; ++e) out[f][e] = normalised_extra_value(V, t, EXTRA_RADIANCE_PATHS, V.radiancePath1, (long long)(f * n + e));
+  return 0;
+}
+
 int i3rc_hip_normalise_path_histogram(const i3rc_hip_integrator *h, const double *t, float *up, float *pathUp, float *down, float *pathDown) {
   if (!h || !t) return 1;
   if (h->extra != EXTRA_PATH_BINS) return const_cast<i3rc_hip_integrator *>(h)->fail("i3rc_hip_normalise_path_histogram: the path histogram is not switched on");
@@ -2360,13 +2413,14 @@ int i3rc_hip_normalise_actinic_flux(const i3rc_hip_integrator *h, const double *
 namespace {
 // The launch of the general flux kernel under the tag of the handle's extra tally block, through the one path every plain launch
 // takes (defined last, so that these kernels are instantiated behind every other kernel of the library: the level kernels, then the
-// track kernels, then the path kernels, then the histogram kernels).
+// track kernels, then the path kernels, then the histogram kernels, then the radiance path kernels).
 int launch_extra(i3rc_hip_integrator *h, const Launch &L, const RunArgs &A, hipStream_t stream, bool timeIt) {
   switch (h->extra) {
     case EXTRA_LEVELS: return launch<PhiloxLevelStream>(h, L, A, stream, timeIt);
     case EXTRA_TRACKS: return launch<PhiloxTrackStream>(h, L, A, stream, timeIt);
     case EXTRA_PATHS: return launch<PhiloxPathStream>(h, L, A, stream, timeIt);
     case EXTRA_PATH_BINS: return launch<PhiloxBinStream>(h, L, A, stream, timeIt);
+    case EXTRA_RADIANCE_PATHS: return launch<PhiloxRadiancePathStream>(h, L, A, stream, timeIt);
     case EXTRA_NONE: break;
   }
   return h->fail("internal: no extra tally block is switched on");
@@ -2381,7 +2435,8 @@ const KernelEntry *find_kernel(const StreamKind &s, const KernelKey &key) {
                                          : s.extra == EXTRA_LEVELS ? stream_kernels<PhiloxLevelStream>()
                                          : s.extra == EXTRA_TRACKS ? stream_kernels<PhiloxTrackStream>()
                                          : s.extra == EXTRA_PATHS ? stream_kernels<PhiloxPathStream>()
-                                         : s.extra == EXTRA_PATH_BINS ? stream_kernels<PhiloxBinStream>() : stream_kernels<PhiloxStream>();
+                                         : s.extra == EXTRA_PATH_BINS ? stream_kernels<PhiloxBinStream>()
+                                         : s.extra == EXTRA_RADIANCE_PATHS ? stream_kernels<PhiloxRadiancePathStream>() : stream_kernels<PhiloxStream>();
   for (const KernelEntry &e : list)
     if (e.key == key) return &e;
   return nullptr;
@@ -2412,11 +2467,11 @@ int i3rc_hip_problem_facts(int nx, int ny, int nz, int ncomp, const float *xEdge
 
 /* Host only: what a launch of `kind` would be on a problem of these facts (i3rc_hip_problem_facts), this setup -- binding.SETUP_NAMES:
  * what the setters and the handle's knobs add -- and these switches of the process (binding.ENV_NAMES; NULL: the process's own).
- * kind: the stream (0 plain, 1 fused, 2 replay, 3 level tally, 4 track tally, 5 path tally, 6 path histogram), the kind of the source, the batches of a
+ * kind: the stream (0 plain, 1 fused, 2 replay, 3 level tally, 4 track tally, 5 path tally, 6 path histogram, 7 radiance path tally), the kind of the source, the batches of a
  * fused launch and -- read for stream 6 only -- the histogram's bins. */
 int i3rc_hip_plan_launch(const int32_t *facts, const int32_t *setup, const int32_t *env, const int32_t *kind, int32_t *out, int nout,
                          char *text, int ntext) {
-  if (!facts || !setup || !kind || !out || !text || ntext < 1 || kind[0] < 0 || kind[0] > 6 || facts[3] < 1) return 2;
+  if (!facts || !setup || !kind || !out || !text || ntext < 1 || kind[0] < 0 || kind[0] > 7 || facts[3] < 1) return 2;
   if (kind[0] == 6 && (kind[3] < 1 || kind[3] > kMaxPathBins)) return 2;
   ProblemFacts f;
   f.nx = facts[0]; f.ny = facts[1]; f.nz = facts[2]; f.ncomp = facts[3]; f.xyRegular = facts[4]; f.zRegular = facts[5]; f.empty = facts[6] != 0;
@@ -2433,7 +2488,7 @@ int i3rc_hip_plan_launch(const int32_t *facts, const int32_t *setup, const int32
   f.extra = (ExtraTally)setup[10]; f.kernelVariant = setup[11]; f.gridPlace = setup[12]; f.ldsTalliesOn = setup[13] != 0;
   f.pathBins = kind[0] == 6 ? kind[3] : 0;
   const StreamKind s = kind[0] == 2 ? stream_of<ReplayStream>() : kind[0] == 1 ? stream_of<PhiloxBatchStream>()
-                                                                : plain_stream(kind[0] == 3 ? EXTRA_LEVELS : kind[0] == 4 ? EXTRA_TRACKS : kind[0] == 5 ? EXTRA_PATHS : kind[0] == 6 ? EXTRA_PATH_BINS : EXTRA_NONE);
+                                                                : plain_stream(kind[0] == 3 ? EXTRA_LEVELS : kind[0] == 4 ? EXTRA_TRACKS : kind[0] == 5 ? EXTRA_PATHS : kind[0] == 6 ? EXTRA_PATH_BINS : kind[0] == 7 ? EXTRA_RADIANCE_PATHS : EXTRA_NONE);
   const LaunchDecision d = plan_launch(f, env_from_words(env), {s, kind[1]});
   const KernelEntry *kern = d.refusal.empty() ? find_kernel(s, d.key) : nullptr;
   const std::string say = !d.refusal.empty() ? d.refusal : kern ? kern->name : no_kernel_text(s.batched);

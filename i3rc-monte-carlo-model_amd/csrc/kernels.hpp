@@ -125,11 +125,27 @@ struct Tally {
   __device__ __forceinline__ void absorbed_sum(int cell, double sum) const { add_global(base() + P.oVol + cell, sum); }   // (a lane's run in one cell: photon_kernel)
 };
 
+// PATH MOMENTS OF THE LOCAL ESTIMATE (EXTRA_RADIANCE_PATHS, PhiloxRadiancePathStream): per radiance direction and column the sums of c L
+// and c L^2 over the contributions c that the launch adds to that radiance word, all components together -- radiancePath1 |
+// radiancePath2, [nDir][ny][nx] each, in the column where the ray leaves the top.  L is the photon's float64 path register at the event
+// (the register of the path tallies above) plus the ray's own length, which needs no tracing: a local-estimate ray runs straight to the
+// top, (zMax - z) / uz in float64 (the host refuses a direction with uz <= 0).  The products are formed in float64 and added with float64
+// atomics in global memory; a contribution of 0 adds nothing.
+__device__ __forceinline__ void radiance_path_add(double *block, int nDir, int ncol, int d, int col, float con, double length) {
+  const double cl = (double)con * length;
+  // (never outside the block, whatever the indices)
+  double *const at = block + (size_t)min((unsigned)d, (unsigned)(nDir - 1)) * (size_t)ncol + min((unsigned)col, (unsigned)(ncol - 1));
+  add_global(at, cl);
+  add_global(at + (size_t)nDir * (size_t)ncol, cl * length);
+}
+
 // computeIntensityContribution :1419-1611 for one event; adds straight into intensityByComponent.
-template <int GRID, class Rng, class PR>
+// (RPATHS: ... and the contribution's path moments into `pathBlock`, `pathLen` being the photon's path up to the event: radiance_path_add)
+template <int GRID, bool RPATHS = false, class Rng, class PR>
 __device__ __forceinline__ void intensity_contribution(const PR &P, const Lds &L, Rng &rng, NestedCounters &cnt,
                                                        float weight, float x, float y, float z, int ix, int iy, int iz,
-                                                       float dx, float dy, float dz, int component, int order) {
+                                                       float dx, float dy, float dz, int component, int order,
+                                                       double pathLen = 0.0, double *pathBlock = nullptr) {
   const int zIndexMax = P.nz + 1;
   const size_t ncol = (size_t)P.nx * P.ny;
   for (int d = 0; d < P.nDir; ++d) {
@@ -191,6 +207,10 @@ __device__ __forceinline__ void intensity_contribution(const PR &P, const Lds &L
     }
     const Tally<PR> tl{P, L, nullptr};
     tl.radiance(component, d, (r.iy - 1) * P.nx + (r.ix - 1), con);
+    if constexpr (RPATHS) {
+      if (con != 0.0f)
+        radiance_path_add(pathBlock, P.nDir, P.nx * P.ny, d, (r.iy - 1) * P.nx + (r.ix - 1), con, pathLen + ((double)P.zMax - (double)z) / (double)uz);
+    }
   }
 }
 
@@ -631,6 +651,12 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   constexpr bool PATH = Rng::kExtra == EXTRA_PATHS || BINS;
   static_assert(!PATH || (GENERAL && !INTENSITY && !TBL && !DIRECT && !MULTI && !STORE && !BATCHED && !REPLAY),
                 "path lengths: the general flux kernel, no start store, not batched");
+  // path moments of the local estimate (PhiloxRadiancePathStream): the lane keeps its photon's path as above, and the local estimate runs in
+  // the nested order, which takes it (intensity_contribution, RPATHS); tallied by the general radiance kernel only, no ray queue
+  constexpr bool RPATH = Rng::kExtra == EXTRA_RADIANCE_PATHS;
+  static_assert(!RPATH || (GENERAL && INTENSITY && !TBL && !DIRECT && !MULTI && !STORE && !BATCHED && !REPLAY),
+                "radiance path lengths: the general radiance kernel, not batched");
+  constexpr bool PATH_REG = PATH || RPATH;   // the lane carries the float64 path register
   static_assert(!MULTI || (!GENERAL && !TBL && !Rng::kReplay && (INTENSITY || BATCHED)), "MULTI: the widened class -- radiance kernels, and the fused flux kernels (plain flux launches of the class run the general flux kernel)");
   // Work counters of a fused launch.  Flux kernels: exact per batch, gathered per lane (below).  Radiance kernels have no
   // vector register to spare for that: their counters stay per WAVE and are handed to the batch whose photons the wave was
@@ -672,7 +698,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   int order = 0;
   int st = ST_NEW;
   int izFrom = 1;                     // LEVELS: the layer the photon's current segment began in
-  double pathLen = 0.0;               // PATH: the photon's geometric path since its start (path_add)
+  double pathLen = 0.0;               // PATH_REG: the photon's geometric path since its start (path_add, radiance_path_add)
   // Absorption where the tally goes to global memory: what a photon's CONSECUTIVE scatterings in one cell add to it leaves as one
   // atomic -- when the next scattering lies in another cell, or the photon ends (so that a fused launch's lane never holds a sum of
   // another batch's block).  In clouds whose cells are optically thick (an LES field: 55 m cells, free paths of 10 m) a photon is
@@ -790,7 +816,8 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
   // photon's own stream has 0 there): radiances do not depend on the schedule either.  Ray starts and ends use the
   // hardware log / exp / reciprocal (2 ulp): these are weights of a Monte Carlo estimate, not trajectories.
   // The replay build and max cross-section keep the reference's nested order (intensity_contribution).
-  constexpr bool DEFER = INTENSITY && !Rng::kReplay;
+  // (... and so does the radiance path tally: its contributions are made where the lane holds its photon's path)
+  constexpr bool DEFER = INTENSITY && !Rng::kReplay && Rng::kExtra != EXTRA_RADIANCE_PATHS;
   // (max cross-section moves the photon inside the event: nested order there)
 #ifdef I3RC_NESTED_BUILD
   // measurement build (tools/variant_bench.py build nested="-DI3RC_NESTED_BUILD"): the GENERAL kernels keep the reference's nested order
@@ -1232,7 +1259,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           finish_arrival<true>(r, &part);
           track_add(trackSums, extra_block(tally.base(), Pe.oCnt), cell_index(Pe, r.ix, r.iy, r.iz), Pe.nx * Pe.ny * Pe.nz, w, part);
         }
-      } else if constexpr (PATH) {   // ... or the last piece of the photon's path so far
+      } else if constexpr (PATH_REG) {   // ... or the last piece of the photon's path so far
         if (wantEvent && st == ST_EVENT && arrival_pending(r)) {
           float part = 0.0f;
           finish_arrival<true>(r, &part);
@@ -1587,7 +1614,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           order = 0;
           if (REPLAY) { fate = -1; fateCol = -1; fateW = 0.0f; }
           w = 1.0f;
-          if constexpr (PATH) pathLen = 0.0;
+          if constexpr (PATH_REG) pathLen = 0.0;
           r.x = Pe.x0 + px * (Pe.xMax - Pe.x0);
           r.y = Pe.y0 + py * (Pe.yMax - Pe.y0);
           r.z = Pe.z0 + pz * (Pe.zMax - Pe.z0);
@@ -1641,6 +1668,9 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
                 r.dx = sinTheta * __builtin_amdgcn_cosf(turn); r.dy = sinTheta * __builtin_amdgcn_sinf(turn); r.dz = mu;
               }
               if (defer) { pendingShadow = true; wI = w; evInfo = EventInfo::kSurface; }
+              else if constexpr (RPATH)
+                intensity_contribution<GRID, true>(Pe, L, rng, nested, w, r.x, r.y, r.z, r.ix, r.iy, r.iz, r.dx, r.dy, r.dz, 0, order, pathLen,
+                                                   extra_block(tally.base(), Pe.oCnt));
               else if (INTENSITY)
                 intensity_contribution<GRID>(Pe, L, rng, nested, w, r.x, r.y, r.z, r.ix, r.iy, r.iz, r.dx, r.dy, r.dz, 0, order);
               if constexpr (LEVELS) add_global(extra_block(tally.base(), Pe.oCnt) + c2, w);   // levelFluxUp[0]: the reflected weight, where it was reflected
@@ -1769,7 +1799,10 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
                 pendingShadow = true; wI = w;
                 inDx = r.dx; inDy = r.dy; inDz = r.dz;                     // incoming direction
                 evInfo = EventInfo::pack(comp, Pe.useHybrid && order <= Pe.numOrdersOrig, pfi);
-              } else if (INTENSITY)
+              } else if constexpr (RPATH)
+                intensity_contribution<GRID, true>(Pe, L, rng, nested, w, r.x, r.y, r.z, r.ix, r.iy, r.iz, r.dx, r.dy, r.dz, comp, order, pathLen,
+                                                   extra_block(tally.base(), Pe.oCnt));
+              else if (INTENSITY)
                 intensity_contribution<GRID>(Pe, L, rng, nested, w, r.x, r.y, r.z, r.ix, r.iy, r.iz, r.dx, r.dy, r.dz, comp, order);
               if constexpr (FLAGS) {
                 // the roulette's deviate, compares and count only where the launch can play and some lane of this phase does: the block
@@ -1896,7 +1929,7 @@ photon_kernel(const DevProblem P, const RunArgs A, const int evThreshold, const 
           float len = 0.0f;
           s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, true, CHAIN>(P, L, r, true, &len);
           if (s == STEP_CONTINUE || s == STEP_EXIT) track_add(trackSums, extra_block(P.tally, P.oCnt), cell, P.nx * P.ny * P.nz, w, len);
-        } else if constexpr (PATH) {   // the same piece, added to the photon's path
+        } else if constexpr (PATH_REG) {   // the same piece, added to the photon's path
           float len = 0.0f;
           s = trace_step_lazy<GRID, !INTENSITY, GENERAL, false, true, CHAIN>(P, L, r, true, &len);
           if (s == STEP_CONTINUE || s == STEP_EXIT) pathLen += (double)len;

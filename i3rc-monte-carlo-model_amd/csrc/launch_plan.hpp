@@ -220,7 +220,7 @@ inline bool direct_rays(const ProblemFacts &f, const EnvKnobs &env) {
 }
 
 // its stream -- what the Rng template argument of photon_kernel carries: plain (all false), fused, replay, level tally, track tally, path tally,
-// path histogram -- ...
+// path histogram, radiance path tally -- ...
 struct StreamKind {
   bool replay, batched;
   ExtraTally extra;
@@ -233,6 +233,7 @@ inline StreamKind plain_stream(ExtraTally extra) {   // (of a plain launch: the 
          : extra == EXTRA_TRACKS ? stream_of<PhiloxTrackStream>()
          : extra == EXTRA_PATHS  ? stream_of<PhiloxPathStream>()
          : extra == EXTRA_PATH_BINS ? stream_of<PhiloxBinStream>()
+         : extra == EXTRA_RADIANCE_PATHS ? stream_of<PhiloxRadiancePathStream>()
                                  : stream_of<PhiloxStream>();
 }
 // ... and the kind of its source (i3rc_source::kind, RunArgs::srcKind)
@@ -294,6 +295,20 @@ inline const char *incomplete(const ProblemFacts &f) {
   return nullptr;
 }
 
+// The radiance path tally (EXTRA_RADIANCE_PATHS) is filled by the general radiance kernel of a plain, traced launch with at least one
+// radiance direction: what the decision itself can see of that, as the text of the refusal behind the entry point's name, or null.
+// (the directions' cosines and the contribution limit are the handle's: i3rc_hip.hip, extra_tally_refused)
+inline const char *radiance_paths_refused(const ProblemFacts &f, const StreamKind &s) {
+  if (f.extra != EXTRA_RADIANCE_PATHS && s.extra != EXTRA_RADIANCE_PATHS) return nullptr;
+  if (s.batched)
+    return "radiance path lengths have no batch statistics yet and are tallied by plain launches only; fused or announced batches cannot give them "
+           "(switch them off, or call i3rc_hip_launch_batch per batch)";
+  if (s.replay) return "radiance path lengths are tallied by plain launches only; the replay stream cannot give them (switch them off)";
+  if (f.nDir < 1) return "radiance path lengths are tallied by radiance launches only; no radiance direction is set (nDir = 0)";
+  if (!traced(f)) return "radiance path lengths need ray tracing; max cross-section is in use (useRayTracing = 0)";
+  return nullptr;
+}
+
 // Dynamic LDS of one launch: the end of the kernel's own carve-up (lds_plan, tracer.hpp -- the function photon_kernel sets its
 // pointers from), for the instantiation that is about to run.
 inline size_t lds_bytes(const LaunchDecision &d, const StreamKind &s, bool direct, int nInv, bool tableInLds, bool startStore) {
@@ -314,6 +329,7 @@ inline LaunchDecision plan_launch(const ProblemFacts &f, const EnvKnobs &env, co
   const bool fused = s.batched, replay = s.replay;
   const auto refuse = [&d](const char *text, bool early) { d.refusal = text; d.early = early; return d; };
   if (const char *missing = incomplete(f)) return refuse(missing, true);
+  if (const char *paths = radiance_paths_refused(f, s)) return refuse((std::string("plan_launch: ") + paths).c_str(), true);
   d.nx = f.nx; d.ny = f.ny; d.nz = f.nz; d.ncomp = f.ncomp; d.nDir = f.nDir; d.clearNx = f.clearNx; d.clearShift = f.clearShift;
   // bricks pay off once the field no longer fits in one XCD's 4 MB of L2
   // (the clear-air map of a bricked field holds layer numbers in 16 bits: domains of more layers than that keep the linear field)
@@ -333,7 +349,8 @@ inline LaunchDecision plan_launch(const ProblemFacts &f, const EnvKnobs &env, co
     if (layout.total >= ((int64_t)1 << 31)) return refuse("tally buffer too large (2^31 elements or more)", true);
   }
   const size_t ncol = (size_t)f.nx * f.ny, ncell = ncol * f.nz;
-  const bool direct = direct_rays(f, env);
+  // (the radiance path tally's kernel has no one-direction form: it makes no ready rays at all, and keeps the ring kernels' carve-up)
+  const bool direct = direct_rays(f, env) && s.extra != EXTRA_RADIANCE_PATHS;
   LdsEstimate lds{sizeof(float) * ((f.nx + 1) + (f.ny + 1) + (f.nz + 1) + 3 * (size_t)f.nDir)};
   // radiance runs: every wave's ring of local-estimate events (one record serves the nDir rays of an event) and its
   // buffer of ready-made rays (photon_kernel, ray mode)
@@ -391,7 +408,8 @@ inline LaunchDecision plan_launch(const ProblemFacts &f, const EnvKnobs &env, co
   // class, the widened radiance kernels for radiance problems of the widened class, else the general kernel.
   KernelKey key{intensity, true, place, false, false, false};
   int threads = 256;
-  // (an extra tally block: the general flux kernel whatever the problem's class -- the key as it stands)
+  // (an extra tally block: the general flux kernel whatever the problem's class, the radiance path tally's the general radiance kernel --
+  // the key as it stands)
   if (!replay && s.extra == EXTRA_NONE) {   // (the replay build always runs the general kernel: it keeps the nested local estimate, no queue at all)
     bool simple, wide;
     if (fused) {

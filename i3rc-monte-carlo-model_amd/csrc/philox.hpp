@@ -188,6 +188,8 @@ struct PhiloxLevelStream : PhiloxStream { static constexpr ExtraTally kExtra = E
 struct PhiloxTrackStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_TRACKS; };
 struct PhiloxPathStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_PATHS; };
 struct PhiloxBinStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_PATH_BINS; };   // (nor does it contain "PhiloxPathStream")
+// ... and the one tag of the general RADIANCE kernel: path moments of the local estimate's contributions (nor does this name)
+struct PhiloxRadiancePathStream : PhiloxStream { static constexpr ExtraTally kExtra = EXTRA_RADIANCE_PATHS; };
 
 // Test stream: deviates come from a buffer (the reference's MT19937 floats); see i3rc_hip_run_replay.
 struct ReplayStream {

@@ -21,6 +21,7 @@ struct TallyView {
   // offsets in float64 elements (tally_layout below; the level block lies behind the counters, -1 while it is switched off)
   long long fluxUp, fluxDown, fluxAbsorbed, volumeAbsorption, intensityByComponent, intensityExcess, counters, levelUp, levelDown;
   long long pathUp1, pathUp2, pathDown1, pathDown2;   // the path-length block's four fields, [ny][nx] each (-1 unless the block is EXTRA_PATHS)
+  long long radiancePath1, radiancePath2;             // the radiance path block's two fields, [nDir][ny][nx] each (-1 unless the block is EXTRA_RADIANCE_PATHS)
   int nx, ny, nz, ncomp, nDir, xyRegular;
   int limitContrib;         // the excess of limited radiance contributions is redistributed (:327-347)
   const double *areaFrac;   // [nx * ny] column area / domain area (:358-366; read on irregular grids only)
@@ -36,12 +37,18 @@ enum ExtraTally {
   EXTRA_TRACKS,   // the actinic flux's track-length sums, [nz][ny][nx] (i3rc_hip_set_actinic_flux)
   EXTRA_PATHS,    // pathUp1 | pathUp2 | pathDown1 | pathDown2, [ny][nx] each: the sums of w L and w L^2 over the photons that fluxUp / fluxDown count,
                   // L the geometric path since the photon's start (i3rc_hip_set_path_lengths)
-  EXTRA_PATH_BINS // binUp | binPathUp | binDown | binPathDown, nBins + 1 words each, domain-wide: the sums of w and of w L over the same photons, by the
+  EXTRA_PATH_BINS, // binUp | binPathUp | binDown | binPathDown, nBins + 1 words each, domain-wide: the sums of w and of w L over the same photons, by the
                   // bin of L (path_bin below; the last word of each field is the overflow bin) (i3rc_hip_set_path_histogram)
+  EXTRA_RADIANCE_PATHS   // radiancePath1 | radiancePath2, [nDir][ny][nx] each: the sums of c L and c L^2 over the contributions c that a launch adds to
+                  // the radiance of a direction and column, summed over the components -- L the photon's geometric path up to the event plus
+                  // the local-estimate ray's length to the top of the domain (i3rc_hip_set_radiance_path_lengths).  The one kind that the
+                  // general RADIANCE kernel fills, and whose block is sized by nDir (radiance_path_block_words)
 };
 constexpr int kMaxPathBins = 1024;   // (i3rc_hip_set_path_histogram: 1 <= nBins <= 1024)
 I3RC_TALLY_FN long long extra_block_offset(long long countersOffset) { return countersOffset + I3RC_NUM_COUNTERS; }
 // ... and its length in float64 words (of the kinds the grid sizes: the path histogram's block is sized by its bins, path_bin_block_words)
+// (... and the radiance path block by the directions)
+I3RC_TALLY_FN long long radiance_path_block_words(int nDir, int nx, int ny) { return 2 * (long long)nDir * nx * ny; }
 I3RC_TALLY_FN long long extra_block_words(ExtraTally kind, int nx, int ny, int nz) {
   const long long ncol = (long long)nx * ny;
   return kind == EXTRA_LEVELS ? 2 * (nz + 1) * ncol : (kind == EXTRA_TRACKS ? ncol * nz : (kind == EXTRA_PATHS ? 4 * ncol : 0));
@@ -78,8 +85,9 @@ I3RC_TALLY_FN float normalised_path_bin(const double *raw, long long countersOff
 
 // The packed tally buffer of a grid: the fields of i3rc_tally_layout one behind the other, then the extra block, so that switching it
 // moves no other offset.  Fills L, and V's offsets and sizes (levelUp / levelDown: -1 unless the block is EXTRA_LEVELS; pathUp1 ...
-// pathDown2: -1 unless it is EXTRA_PATHS); returns the extra block's offset, -1 without one.  (nBins: the path histogram's, see
-// path_bin_block_words; its fields lie at path_bin_field from the offset returned -- the view has no words for them)
+// pathDown2: -1 unless it is EXTRA_PATHS; radiancePath1 / radiancePath2: -1 unless it is EXTRA_RADIANCE_PATHS); returns the extra block's
+// offset, -1 without one.  (nBins: the path histogram's, see path_bin_block_words; its fields lie at path_bin_field from the offset
+// returned -- the view has no words for them)
 inline long long tally_layout(int nx, int ny, int nz, int ncomp, int nDir, ExtraTally extra, i3rc_tally_layout &L, TallyView &V, int nBins = 0) {
   const long long ncol = (long long)nx * ny;
   long long o = 0;
@@ -91,7 +99,9 @@ inline long long tally_layout(int nx, int ny, int nz, int ncomp, int nDir, Extra
   L.intensityExcess = o; o += (long long)(ncomp + 1) * nDir;
   L.counters = o; o += I3RC_NUM_COUNTERS;
   const long long block = extra == EXTRA_NONE ? -1 : extra_block_offset(L.counters);
-  L.total = o + (extra == EXTRA_PATH_BINS ? path_bin_block_words(nBins) : extra_block_words(extra, nx, ny, nz));
+  L.total = o + (extra == EXTRA_PATH_BINS        ? path_bin_block_words(nBins)
+                 : extra == EXTRA_RADIANCE_PATHS ? radiance_path_block_words(nDir, nx, ny)
+                                                 : extra_block_words(extra, nx, ny, nz));
   V.fluxUp = L.fluxUp; V.fluxDown = L.fluxDown; V.fluxAbsorbed = L.fluxAbsorbed; V.volumeAbsorption = L.volumeAbsorption;
   V.intensityByComponent = L.intensityByComponent; V.intensityExcess = L.intensityExcess; V.counters = L.counters;
   V.levelUp = extra == EXTRA_LEVELS ? block : -1;
@@ -100,6 +110,8 @@ inline long long tally_layout(int nx, int ny, int nz, int ncomp, int nDir, Extra
   V.pathUp2 = extra == EXTRA_PATHS ? block + ncol : -1;
   V.pathDown1 = extra == EXTRA_PATHS ? block + 2 * ncol : -1;
   V.pathDown2 = extra == EXTRA_PATHS ? block + 3 * ncol : -1;
+  V.radiancePath1 = extra == EXTRA_RADIANCE_PATHS ? block : -1;
+  V.radiancePath2 = extra == EXTRA_RADIANCE_PATHS ? block + (long long)nDir * ncol : -1;
   V.nx = nx; V.ny = ny; V.nz = nz; V.ncomp = ncomp; V.nDir = nDir;
   return block;
 }
@@ -138,8 +150,10 @@ I3RC_TALLY_FN float normalised_actinic_flux(const TallyView &V, const double *ra
 
 // Element e of the kind's extra block (at `block`) as reportResults hands it out: the level fluxes (e counts through levelFluxUp |
 // levelFluxDown, level after level) and the path-length sums (e counts through pathUp1 | pathUp2 | pathDown1 | pathDown2) per photon of
-// the column, as fluxUp; the actinic flux also per unit of the layer's depth.  What i3rc_hip_normalise_level_fluxes / _actinic_flux /
-// _path_lengths fill their arrays with and what the diagnostic batch moments add up.
+// the column, as fluxUp; the actinic flux also per unit of the layer's depth; the radiance path sums (e counts through radiancePath1 |
+// radiancePath2, direction after direction) per photon of the column, as the radiance word they belong to (normalised_intensity without
+// an excess: the kind is refused with the contribution limit).  What i3rc_hip_normalise_level_fluxes / _actinic_flux / _path_lengths /
+// _radiance_path_lengths fill their arrays with and what the diagnostic batch moments add up.
 I3RC_TALLY_FN float normalised_extra_value(const TallyView &V, const double *raw, ExtraTally kind, long long block, long long e) {
   const long long ncol = (long long)V.nx * V.ny;
   if (kind == EXTRA_TRACKS) {

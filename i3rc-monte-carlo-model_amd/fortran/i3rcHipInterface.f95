@@ -283,6 +283,27 @@ module i3rcHipInterface
       type(c_ptr), value         :: pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown   ! (nx, ny) each
       integer(c_int)             :: rc
     end function
+    function i3rc_hip_set_radiance_path_lengths(h, on) bind(C, name = "i3rc_hip_set_radiance_path_lengths") result(rc)
+      import
+      type(c_ptr), value    :: h
+      integer(c_int), value :: on
+      integer(c_int)        :: rc
+    end function
+    function i3rc_hip_get_radiance_path_length_layout(h, path1, path2, total) &
+             bind(C, name = "i3rc_hip_get_radiance_path_length_layout") result(rc)
+      import
+      type(c_ptr), value      :: h
+      integer(c_int64_t)      :: path1, path2, total   ! offsets in float64 elements (-1: off), the buffer's total
+      integer(c_int)          :: rc
+    end function
+    function i3rc_hip_normalise_radiance_path_lengths(h, host, radiancePathLength, radiancePathLengthSquared) &
+             bind(C, name = "i3rc_hip_normalise_radiance_path_lengths") result(rc)
+      import
+      type(c_ptr), value         :: h
+      real(c_double), intent(in) :: host(*)
+      type(c_ptr), value         :: radiancePathLength, radiancePathLengthSquared   ! (nx, ny, nDir) each
+      integer(c_int)             :: rc
+    end function
     function i3rc_hip_set_path_histogram(h, nBins, edges) bind(C, name = "i3rc_hip_set_path_histogram") result(rc)
       import
       type(c_ptr), value        :: h

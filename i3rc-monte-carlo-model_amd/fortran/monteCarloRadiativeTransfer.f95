@@ -68,6 +68,11 @@ module monteCarloRadiativeTransfer
     ! length (squared) x incident flux (not in the reference)
     logical :: computePathLengths = .false.
     real, dimension(:, :, :),    pointer :: pathLengths => null()
+    ! ... and, with specifyParameters(computeRadiancePathLengths = .true.), the first two moments of the geometric path length of every
+    ! local-estimate radiance (nx, ny, nDir, 2): radiancePathLength, radiancePathLengthSquared, in units of length (squared) x
+    ! radiance (not in the reference); sized by the directions when a batch's results are unpacked
+    logical :: computeRadiancePathLengths = .false.
+    real, dimension(:, :, :, :), pointer :: radiancePaths => null()
     ! ... and, with specifyParameters(pathHistogramEdges = edges), the distribution of that path length over the bins the edges bound
     ! (nBins + 1, 4), the overflow bin last: pathHistogramUp, pathHistogramPathUp, pathHistogramDown, pathHistogramPathDown -- the bins'
     ! shares of the domain's mean fluxUp / fluxDown and those times the bins' mean paths (not in the reference)
@@ -187,7 +192,7 @@ contains
                                numOrdersOrigPhaseFunIntenCalcs,                        &
                                limitIntensityContributions, maxIntensityContribution,  &
                                status, computeLevelFluxes, computeActinicFlux, computePathLengths, pathHistogramEdges, &
-                               absorptionCoefficients)
+                               absorptionCoefficients, computeRadiancePathLengths)
     type(integrator),                   intent(inout) :: thisIntegrator
     real,                     optional, intent(in   ) :: surfaceAlbedo
     type(surfaceDescription), optional, intent(in   ) :: surfaceBDRF
@@ -208,6 +213,8 @@ contains
     logical,                  optional, intent(in   ) :: computeActinicFlux
     ! (likewise: the path-length moments of reflected and transmitted light, see reportResults)
     logical,                  optional, intent(in   ) :: computePathLengths
+    ! (likewise: the path-length moments of the local-estimate radiances, per view direction, see reportResults)
+    logical,                  optional, intent(in   ) :: computeRadiancePathLengths
     ! (likewise: the path-length histogram over these bin edges -- 0 first, strictly ascending --, see reportResults; an array of
     ! size 0 switches it off)
     real, dimension(:),       optional, intent(in   ) :: pathHistogramEdges
@@ -391,6 +398,13 @@ contains
         thisIntegrator%pathLengths = 0.
       end if
       thisIntegrator%computePathLengths = computePathLengths
+    end if
+    if(present(computeRadiancePathLengths)) then
+      if(.not. deviceCall(thisIntegrator, i3rc_hip_set_radiance_path_lengths(thisIntegrator%device, merge(1, 0, computeRadiancePathLengths)), &
+                          "specifyParameters", status)) return
+      ! (the two fields are sized by the directions of the batch they come from: unpackTallies)
+      if(associated(thisIntegrator%radiancePaths)) deallocate(thisIntegrator%radiancePaths)
+      thisIntegrator%computeRadiancePathLengths = computeRadiancePathLengths
     end if
     if(present(pathHistogramEdges)) then
       if(size(pathHistogramEdges) == 1) then
@@ -676,6 +690,17 @@ contains
       ok = deviceCall(thisIntegrator, i3rc_hip_normalise_path_lengths(thisIntegrator%device, raw,                           &
                       c_loc(thisIntegrator%pathLengths(1, 1, 1)), c_loc(thisIntegrator%pathLengths(1, 1, 2)),                &
                       c_loc(thisIntegrator%pathLengths(1, 1, 3)), c_loc(thisIntegrator%pathLengths(1, 1, 4))), caller, status)
+      if(.not. ok) return
+    end if
+    if(thisIntegrator%computeRadiancePathLengths .and. thisIntegrator%computeIntensity) then
+      if(associated(thisIntegrator%radiancePaths)) then
+        if(size(thisIntegrator%radiancePaths, 3) /= size(thisIntegrator%intensity, 3)) deallocate(thisIntegrator%radiancePaths)
+      end if
+      if(.not. associated(thisIntegrator%radiancePaths))                                                                  &
+        allocate(thisIntegrator%radiancePaths(size(thisIntegrator%intensity, 1), size(thisIntegrator%intensity, 2),        &
+                                              size(thisIntegrator%intensity, 3), 2))
+      ok = deviceCall(thisIntegrator, i3rc_hip_normalise_radiance_path_lengths(thisIntegrator%device, raw,                  &
+                      c_loc(thisIntegrator%radiancePaths(1, 1, 1, 1)), c_loc(thisIntegrator%radiancePaths(1, 1, 1, 2))), caller, status)
       if(.not. ok) return
     end if
     if(associated(thisIntegrator%pathHistogram)) then
@@ -1264,7 +1289,8 @@ contains
   subroutine reportResults(thisIntegrator, meanFluxUp, meanFluxDown, meanFluxAbsorbed, fluxUp, fluxDown, fluxAbsorbed, &
                            absorbedProfile, volumeAbsorption, meanIntensity, intensity, status, levelFluxUp, levelFluxDown, &
                            actinicFlux, pathLengthUp, pathLengthSquaredUp, pathLengthDown, pathLengthSquaredDown, &
-                           pathHistogramUp, pathHistogramPathUp, pathHistogramDown, pathHistogramPathDown)
+                           pathHistogramUp, pathHistogramPathUp, pathHistogramDown, pathHistogramPathDown, &
+                           radiancePathLength, radiancePathLengthSquared)
     type(integrator),                   intent(in   ) :: thisIntegrator
     real,                     optional, intent(  out) :: meanFluxUp, meanFluxDown, meanFluxAbsorbed
     real, dimension(:, :),    optional, intent(  out) :: fluxUp, fluxDown, fluxAbsorbed
@@ -1283,6 +1309,10 @@ contains
     ! (likewise) (nBins + 1), the overflow bin last: the sums of w and of w L over the same photons by the bin of L, per photon of the
     ! run and domain-wide: sum(pathHistogramUp) is the domain's mean fluxUp, pathHistogramPathUp / pathHistogramUp a bin's mean path
     real, dimension(:),       optional, intent(  out) :: pathHistogramUp, pathHistogramPathUp, pathHistogramDown, pathHistogramPathDown
+    ! (likewise) (nx, ny, nDir), as intensity: the sums of c L and c L**2 over the contributions c to the radiance of a direction and
+    ! column, L the photon's path to the event plus the ray's way to the top, normalised as intensity is: radiancePathLength /
+    ! intensity is the mean geometric path of that pixel's radiance
+    real, dimension(:, :, :), optional, intent(  out) :: radiancePathLength, radiancePathLengthSquared
     integer :: nColumns, d
 
     if(.not. associated(thisIntegrator%fluxUp)) then
@@ -1368,6 +1398,8 @@ contains
     if(present(pathLengthSquaredUp))   call copyPathField(2, pathLengthSquaredUp,   "pathLengthSquaredUp")
     if(present(pathLengthDown))        call copyPathField(3, pathLengthDown,        "pathLengthDown")
     if(present(pathLengthSquaredDown)) call copyPathField(4, pathLengthSquaredDown, "pathLengthSquaredDown")
+    if(present(radiancePathLength))        call copyRadiancePathField(1, radiancePathLength,        "radiancePathLength")
+    if(present(radiancePathLengthSquared)) call copyRadiancePathField(2, radiancePathLengthSquared, "radiancePathLengthSquared")
     if(present(pathHistogramUp))       call copyBinField(1, pathHistogramUp,       "pathHistogramUp")
     if(present(pathHistogramPathUp))   call copyBinField(2, pathHistogramPathUp,   "pathHistogramPathUp")
     if(present(pathHistogramDown))     call copyBinField(3, pathHistogramDown,     "pathHistogramDown")
@@ -1386,6 +1418,18 @@ contains
         to = thisIntegrator%pathHistogram(:, which)
       end if
     end subroutine copyBinField
+    subroutine copyRadiancePathField(which, to, name)
+      integer,                  intent(in ) :: which
+      real, dimension(:, :, :), intent(out) :: to
+      character(len = *),       intent(in ) :: name
+      if(.not. associated(thisIntegrator%radiancePaths)) then
+        call setStateToFailure(status, "reportResults: radiance path length information not available")
+      else if(any(shape(to) /= shape(thisIntegrator%radiancePaths(:, :, :, which)))) then
+        call setStateToFailure(status, "reportResults: " // name // " array is the wrong size")
+      else
+        to = thisIntegrator%radiancePaths(:, :, :, which)
+      end if
+    end subroutine copyRadiancePathField
     subroutine copyPathField(which, to, name)
       integer,               intent(in ) :: which
       real, dimension(:, :), intent(out) :: to
@@ -1477,6 +1521,15 @@ contains
         copy%computePathLengths = .true.
       end if
     end if
+    if(original%computeRadiancePathLengths) then
+      if(deviceCall(copy, i3rc_hip_set_radiance_path_lengths(copy%device, 1), "copy_Integrator", status)) then
+        if(associated(original%radiancePaths)) then
+          allocate(copy%radiancePaths(size(original%radiancePaths, 1), size(original%radiancePaths, 2), size(original%radiancePaths, 3), 2))
+          copy%radiancePaths = original%radiancePaths
+        end if
+        copy%computeRadiancePathLengths = .true.
+      end if
+    end if
     if(associated(original%pathHistogram)) then
       if(deviceCall(copy, i3rc_hip_set_path_histogram(copy%device, size(original%pathHistogramEdges) - 1, original%pathHistogramEdges), &
                     "copy_Integrator", status)) then
@@ -1528,9 +1581,11 @@ contains
     if(associated(thisIntegrator%levelFluxUp))          deallocate(thisIntegrator%levelFluxUp, thisIntegrator%levelFluxDown)
     if(associated(thisIntegrator%actinicFlux))          deallocate(thisIntegrator%actinicFlux)
     if(associated(thisIntegrator%pathLengths))          deallocate(thisIntegrator%pathLengths)
+    if(associated(thisIntegrator%radiancePaths))        deallocate(thisIntegrator%radiancePaths)
     if(associated(thisIntegrator%pathHistogram))        deallocate(thisIntegrator%pathHistogram, thisIntegrator%pathHistogramEdges)
     if(associated(thisIntegrator%absorptionCoefficients)) deallocate(thisIntegrator%absorptionCoefficients)
     thisIntegrator%computeLevelFluxes = .false.; thisIntegrator%computeActinicFlux = .false.; thisIntegrator%computePathLengths = .false.
+    thisIntegrator%computeRadiancePathLengths = .false.
     thisIntegrator%readyToCompute = .false.; thisIntegrator%computeIntensity = .false.
     thisIntegrator%useSurfaceBDRF = .false.
   end subroutine finalize_Integrator

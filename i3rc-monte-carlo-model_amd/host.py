@@ -176,6 +176,8 @@ class Domain:
 # ---------------------------------------------------------------------------------------------------------
 # the four results of the path-length tally, in the order of its block (i3rc_hip_normalise_path_lengths)
 PATH_LENGTH_NAMES = ("pathLengthUp", "pathLengthSquaredUp", "pathLengthDown", "pathLengthSquaredDown")
+# ... the two of the radiance path tally (i3rc_hip_normalise_radiance_path_lengths)
+RADIANCE_PATH_NAMES = ("radiancePathLength", "radiancePathLengthSquared")
 # ... and of the path histogram (i3rc_hip_normalise_path_histogram)
 PATH_HISTOGRAM_NAMES = ("pathHistogramUp", "pathHistogramPathUp", "pathHistogramDown", "pathHistogramPathDown")
 # ... and what the path moments add to them (i3rc_path_moments_layout): the column means and the domain's <L>, <L^2>; the spectrum's bounds
@@ -191,7 +193,8 @@ class Integrator:
                    "intensityPhis", "computeIntensity", "useRayTracing", "useRussianRoulette",
                    "useRussianRouletteForIntensity", "zetaMin", "useHybridPhaseFunsForIntenCalcs",
                    "hybridPhaseFunWidth", "numOrdersOrigPhaseFunIntenCalcs", "limitIntensityContributions",
-                   "maxIntensityContribution", "computeLevelFluxes", "computeActinicFlux", "computePathLengths", "pathHistogramEdges", "absorptionCoefficients")
+                   "maxIntensityContribution", "computeLevelFluxes", "computeActinicFlux", "computePathLengths", "pathHistogramEdges", "absorptionCoefficients",
+                   "computeRadiancePathLengths")
 
     def __init__(self, atmosphere, device=0):
         self._h = C.c_void_p()
@@ -223,6 +226,7 @@ class Integrator:
         self.computeLevelFluxes = False
         self.computeActinicFlux = False
         self.computePathLengths = False
+        self.computeRadiancePathLengths = False
         self.pathHistogramEdges = None       # (float32 edges while the path histogram is on)
         self.absorptionCoefficients = np.zeros(0, np.float32)   # (the spectrum of the path moments; empty: off)
         self._inv_size = [0] * self.ncomp
@@ -342,6 +346,12 @@ class Integrator:
             self.computePathLengths = bool(kw["computePathLengths"])
             self._results = None             # (the tally layout has changed)
 
+        if "computeRadiancePathLengths" in kw:
+            # the first two path-length moments of every local-estimate radiance (i3rc_hip_set_radiance_path_lengths): not in the reference
+            self._check(self._lib.i3rc_hip_set_radiance_path_lengths(self._h, int(bool(kw["computeRadiancePathLengths"]))), "specifyParameters")
+            self.computeRadiancePathLengths = bool(kw["computeRadiancePathLengths"])
+            self._results = None             # (the tally layout has changed)
+
         if "pathHistogramEdges" in kw:
             # the path-length distribution of reflected and transmitted light over these bin edges (i3rc_hip_set_path_histogram): not in
             # the reference.  None or an empty array switches it off.
@@ -367,6 +377,13 @@ class Integrator:
         off (i3rc_hip_get_path_histogram_layout)."""
         v = [C.c_int64(0) for _ in range(6)]
         self._check(self._lib.i3rc_hip_get_path_histogram_layout(self._h, *[C.byref(x) for x in v]), "path_histogram_layout")
+        return tuple(x.value for x in v)
+
+    def radiance_path_length_layout(self):
+        """(offsets of radiancePath1, radiancePath2, total) of the packed tally buffer, in float64 elements; each field is
+        [nDir][ny][nx]; the offsets are -1 while radiance path lengths are off (i3rc_hip_get_radiance_path_length_layout)."""
+        v = [C.c_int64(0) for _ in range(3)]
+        self._check(self._lib.i3rc_hip_get_radiance_path_length_layout(self._h, *[C.byref(x) for x in v]), "radiance_path_length_layout")
         return tuple(x.value for x in v)
 
     def path_length_layout(self):
@@ -487,6 +504,11 @@ class Integrator:
                 res[k] = np.zeros((self.ny, self.nx), np.float32)
             self._check(self._lib.i3rc_hip_normalise_path_lengths(self._h, raw.ctypes.data_as(B.dp), *[pf(res[k]) for k in PATH_LENGTH_NAMES]),
                         "computeRadiativeTransfer")
+        if self.computeRadiancePathLengths:
+            for k in RADIANCE_PATH_NAMES:
+                res[k] = np.zeros((nd, self.ny, self.nx), np.float32)
+            self._check(self._lib.i3rc_hip_normalise_radiance_path_lengths(self._h, raw.ctypes.data_as(B.dp),
+                                                                           *[pf(res[k]) for k in RADIANCE_PATH_NAMES]), "computeRadiativeTransfer")
         if self.pathHistogramEdges is not None:
             for k in PATH_HISTOGRAM_NAMES:
                 res[k] = np.zeros(self.pathHistogramEdges.size, np.float32)   # (nBins + 1: the overflow bin last)
@@ -666,7 +688,7 @@ class Integrator:
     # -- reportResults :711-826
     def reportResults(self, levelFluxUp=False, levelFluxDown=False, actinicFlux=False, pathLengthUp=False, pathLengthSquaredUp=False,
                       pathLengthDown=False, pathLengthSquaredDown=False, pathHistogramUp=False, pathHistogramPathUp=False,
-                      pathHistogramDown=False, pathHistogramPathDown=False):
+                      pathHistogramDown=False, pathHistogramPathDown=False, radiancePathLength=False, radiancePathLengthSquared=False):
         """levelFluxUp / levelFluxDown = True ask for the level fluxes, (nz + 1, ny, nx) each, level k at zPosition[k] (the shell's optional
         arguments of the same names): an error unless specifyParameters(computeLevelFluxes=True) came before the computation.
         pathLengthUp / pathLengthSquaredUp / pathLengthDown / pathLengthSquaredDown = True ask for the path-length moments of the
@@ -676,7 +698,11 @@ class Integrator:
         pathHistogramUp / pathHistogramPathUp / pathHistogramDown / pathHistogramPathDown = True ask for the path histogram, nBins + 1
         values each (the overflow bin last), per photon of the run and domain-wide: the sum of pathHistogramUp is the domain's mean
         fluxUp, pathHistogramPathUp / pathHistogramUp a bin's mean path.  An error unless specifyParameters(pathHistogramEdges=...)
-        came before the computation."""
+        came before the computation.
+        radiancePathLength / radiancePathLengthSquared = True ask for the path-length moments of the local-estimate radiances, in
+        intensity's own shape (nDir, ny, nx), in units of length (squared) x radiance: radiancePathLength / intensity is the mean
+        geometric path of a pixel's radiance.  An error unless specifyParameters(computeRadiancePathLengths=True) came before the
+        computation."""
         r = self._results
         if r is None:
             raise I3RCError("reportResults: no results available")
@@ -690,6 +716,9 @@ class Integrator:
         bins = [k for k, asked in zip(PATH_HISTOGRAM_NAMES, (pathHistogramUp, pathHistogramPathUp, pathHistogramDown, pathHistogramPathDown)) if asked]
         if bins and "pathHistogramUp" not in r:
             raise I3RCError("reportResults: path histogram information not available")
+        rpaths = [k for k, asked in zip(RADIANCE_PATH_NAMES, (radiancePathLength, radiancePathLengthSquared)) if asked]
+        if rpaths and "radiancePathLength" not in r:
+            raise I3RCError("reportResults: radiance path length information not available")
         ncol = r32(self.nx * self.ny)
         out = dict(meanFluxUp=r["fluxUp"].sum(dtype=np.float32) / ncol, meanFluxDown=r["fluxDown"].sum(dtype=np.float32) / ncol,
                    meanFluxAbsorbed=r["fluxAbsorbed"].sum(dtype=np.float32) / ncol,
@@ -705,7 +734,7 @@ class Integrator:
             out["levelFluxDown"] = r["levelFluxDown"]
         if actinicFlux:
             out["actinicFlux"] = r["actinicFlux"]
-        for k in paths + bins:
+        for k in paths + bins + rpaths:
             out[k] = r[k]
         return out
 

@@ -231,6 +231,36 @@ int i3rc_hip_get_path_length_layout(const i3rc_hip_integrator *h, int64_t *up1, 
 int i3rc_hip_normalise_path_lengths(const i3rc_hip_integrator *h, const double *hostTallies, float *pathLengthUp, float *pathLengthSquaredUp,
                                     float *pathLengthDown, float *pathLengthSquaredDown);
 
+/* PATH-LENGTH MOMENTS OF LOCAL-ESTIMATE RADIANCES, per view direction (not in the reference): for every radiance direction d and column
+ *   radiancePath1[d][iy][ix] = sum of c L      radiancePath2[d][iy][ix] = sum of c L^2
+ * over exactly the contributions c that a launch adds to the radiance of (d, column), all components together, in the column where the
+ * local-estimate ray leaves the top.  L = the photon's geometric path from its start to the event (the float64 sum of the tracer's
+ * float32 pieces, carried through reflections) + the ray's own length (zMax - z_event) / uz, formed in float64; with the local
+ * estimate's roulette c is the value the roulette leaves.  radiancePath1 / radiance is then the mean geometric path <L> of that pixel's
+ * radiance in the grid's length unit and radiancePath2 / radiance is <L^2>: the equivalence theorem for an instrument that looks in a
+ * direction, I(k) = I(0) <exp(-k L)>.
+ * The two arrays form a block of 2 nDir nx ny float64 words BEHIND the counters of the packed tally buffer, where any other kind's block
+ * would lie: the kinds are never on together, and each setter refuses while another is on.  No offset of i3rc_tally_layout moves.  The
+ * block is sized by nDir: i3rc_hip_set_directions lays the buffer out anew when nDir changes, as it always did (with a caller-bound
+ * buffer in use that is refused).  Switching reallocates the handle's own buffer (cleared); with a caller-bound buffer in use it is
+ * refused.  Off by default: nothing changes then.
+ * While the feature is on, a launch runs photon_kernel<PhiloxRadiancePathStream, true, true, GRID> -- the general radiance kernel with
+ * the local estimate in the reference's nested order, every ray traced where its event happens; several times slower than the ray
+ * queue -- and is refused, before anything is touched, when no radiance direction is set, when a direction has uz <= 0 (its rays never
+ * reach the top), when max cross-section is in use (useRayTracing = 0) or when contributions are limited
+ * (limitIntensityContributions: the redistributed excess has no path).  The kind has no batch statistics yet: i3rc_hip_run_batches,
+ * i3rc_hip_expect_batches, the three moments loops, i3rc_hip_get_diagnostic_moments_layout and i3rc_hip_run_replay are refused;
+ * i3rc_hip_compute_batch does not look ahead. */
+int i3rc_hip_set_radiance_path_lengths(i3rc_hip_integrator *h, int on);
+/* Offsets (float64 elements) of radiancePath1 and radiancePath2 in the packed buffer, -1 each while the feature is off, and the
+ * buffer's total (= layout.total).  Any of the three may be NULL. */
+int i3rc_hip_get_radiance_path_length_layout(const i3rc_hip_integrator *h, int64_t *path1, int64_t *path2, int64_t *total);
+/* The radiance's normalisation (i3rc_hip_normalise, intensity: per photon of the column, float64 rounded once to float32) of a host copy
+ * of the packed tallies: two arrays [nDir][ny][nx], in units of length x radiance and length^2 x radiance.  Either output may be NULL.
+ * Fails while the feature is off. */
+int i3rc_hip_normalise_radiance_path_lengths(const i3rc_hip_integrator *h, const double *hostTallies, float *radiancePathLength,
+                                             float *radiancePathLengthSquared);
+
 /* THE PATH-LENGTH HISTOGRAM of reflected and transmitted light (not in the reference): the distribution p(L) the two moments above
  * cannot give.  With nBins >= 1, plain flux launches also sort the light that fluxUp and fluxDown count into nBins bins of its
  * geometric path L, domain-wide, and an overflow bin: four fields of nBins + 1 float64 raw sums each,
